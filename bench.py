@@ -8,13 +8,16 @@ loop), 3-level Laplacian fusion with 200/100/50 damped Jacobi sweeps, u16 quanti
 resident in HBM before the timed region.  Per GPU the workload is BASELINE config C3 (batch 64);
 launched on 8 GPUs it is C4 (512 panoramas, 64 per GPU, no collective on the data path).
 
-    python bench.py [--gpus N --steps K --warmup W --batch B]
+    python bench.py [--gpus N --steps K --warmup W --batch B] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 Run directly with --gpus N > 1 it launches the N ranks itself (torch.distributed.run as a child,
 started before any GPU call; launch_ranks), so both forms print the same N-rank line.
 
-Rank 0 prints one JSON line.  `roofline` is for the dominant kernel (the Jacobi sweep) against
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline fields (value = panoramas/s, ms_per_step = one timed step); --dump-outputs DIR also
+writes the last timed step's results as .npy files.  Everything below is measured or checked
+only with --full.  `roofline` is for the dominant kernel (the Jacobi sweep) against
 its real roof, VALU issue: algorithmic FLOP (14 per pixel-update) per launch over its average
 hipEvent-measured launch time; `roofline_hbm` puts the same kernel's measured PMC traffic on the
 HBM roof and `effective_hbm` keeps SURVEY.md 8d's 12 B/update as an effective rate.
@@ -80,10 +83,57 @@ def parse():
                     help="every rank writes DIR/rank<r>.npz: the inputs (ground truth, baseline, "
                          "depth-net responses) and the fused u16 of one sampled panorama of its "
                          "batch, for an oracle check outside the bench (tests/test_gpu_c4.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else the "
+                         "record holds: the bit-exactness checks against a fresh one-process / "
+                         "one-GPU fusion, the per-stage rooflines, the metrics and smoothing "
+                         "timings, the C1/C2/C5 sub-records, the CPU baseline.  Without it the "
+                         "run times its steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as "
+                         "DIR/<name>.npy (float32; with N > 1 ranks <name>_rank<r>.npy): `fused`, "
+                         "the first panoramas of the batch's u16 result, `fused_sample`, a fixed "
+                         "seeded sample of pixels of the whole result, and `coeffs`, the "
+                         "registration coefficients; at most 64 MB in all")
     ap.add_argument("--stand-in", action="store_true",
                     help="test hook (tests/test_bench_dist.py): the launcher, seeding and timing "
                          "path with a CPU stand-in step over gloo; no GPU is touched")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.sample_dump and not args.full and not args.stand_in:
+        ap.error("--sample-dump belongs to the checks of --full")
+    return args
+
+
+DUMP_BUDGET = 60 << 20  # bytes of float32 a run's --dump-outputs may write, all ranks together
+
+
+def dump_outputs(path, out, coeffs, rank, world):
+    """--dump-outputs: the result of the last timed step as float32 .npy files.  `out` is the
+    fused u16 result ((B, H, W) or (H, W), int16 storage) and `coeffs` the registration
+    coefficients the same call filled.  The whole of `coeffs`, the leading panoramas of `out` that
+    fit half of this rank's share of DUMP_BUDGET, and a sample of pixels of all of `out` at
+    positions drawn once from a fixed seed (the same positions in every run) are written."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    budget = DUMP_BUDGET // world // 4  # float32 elements of this rank
+    flat = out.reshape(-1)
+    pano = out[0].numel() if out.dim() == 3 else flat.numel()
+    whole = min(flat.numel() // pano, budget // 2 // pano)
+    nsamp = min(flat.numel(), budget // 2 - coeffs.numel())
+    idx = (torch.from_numpy(np.random.default_rng(20261019).integers(0, flat.numel(), nsamp))
+           if nsamp < flat.numel() else None)
+
+    def u16(t):  # int16 storage of u16 values -> float32, on the host
+        return t.cpu().numpy().view(np.uint16).astype(np.float32)
+
+    arrays = {"coeffs": coeffs.detach().cpu().numpy().astype(np.float32),
+              "fused_sample": u16(flat if idx is None else flat[idx.to(flat.device)])}
+    if whole:
+        arrays["fused"] = u16(out[:whole] if out.dim() == 3 else out)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), a)
 
 
 def host_cpus():
@@ -190,7 +240,7 @@ def _metrics_traffic():
     return 3 * h + e if h is not None and e is not None else None
 
 
-def c5_measure(args, rank, world, local, dev, steps, warmup):
+def c5_measure(args, rank, world, local, dev, steps, warmup, checks=True, dump=None):
     """BASELINE config C5: one 8192x4096 panorama, 80 tiles of 1024^2 sharded over the ranks.
     Each rank warps and registers its own tiles (a sub-layout context writing into its slice of
     the full tile block).  --c5-shard rows (pf_dist.fuse_row_sharded): per level each rank sums
@@ -275,8 +325,10 @@ def c5_measure(args, rank, world, local, dev, steps, warmup):
                          device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump and rank == 0:  # the gathered panorama lives on rank 0 (coeffs: its own tiles' rows)
+        dump_outputs(dump, out, coeffs, 0, 1)
     bit_exact = None
-    if rank == 0:
+    if checks and rank == 0:
         # after the timed steps: the same panorama fused on this GPU alone (every tile warped
         # and registered here, pf_merge) must equal the sharded result bit for bit
         full = torch.zeros_like(tiles)
@@ -286,7 +338,7 @@ def c5_measure(args, rank, world, local, dev, steps, warmup):
         torch.cuda.synchronize()
         bit_exact = bool(torch.equal(ref, out))
     one_call = None
-    if world == 1:
+    if checks and world == 1:
         # the same panorama through the library's one-call path (pf_warp_depth + pf_merge on one
         # context, no per-level host orchestration): hipEvents, median of 5
         rall = panofuse.make_responses(resp_all, dev)
@@ -305,7 +357,7 @@ def c5_measure(args, rank, world, local, dev, steps, warmup):
                 ts_.append(e0.elapsed_time(e1))
         one_call = sorted(ts_)[len(ts_) // 2]
     model8 = None
-    if world == 1 and args.c5_shard == "rows":
+    if checks and world == 1 and args.c5_shard == "rows":
         model8 = c5_rehearsal(fz, lay, gt, emap, resp_all, coeffs, tiles, out, out_w, zr,
                               nlevels, dev, local, side=fside)
     nz = int((out != 0).sum().item())
@@ -405,7 +457,8 @@ def c5_rehearsal(fz, lay, gt, emap, resp_all, coeffs, tiles, out, out_w, zr, nle
 def run_c5(args, rank, world, local, dev, dist_on=False, comm_res=None):
     """bench.py --mode c5: the C5 line (c5_measure) on `world` ranks."""
     import torch.distributed as dist
-    r = c5_measure(args, rank, world, local, dev, args.steps, args.warmup)
+    r = c5_measure(args, rank, world, local, dev, args.steps, args.warmup, checks=args.full,
+                   dump=args.dump_outputs)
     elapsed, mine_s, bit_exact, nz = r["elapsed"], r["mine_s"], r["bit_exact"], r["nonzero_px"]
     if rank == 0:
         print(json.dumps({
@@ -435,7 +488,7 @@ def run_c5(args, rank, world, local, dev, dist_on=False, comm_res=None):
     if dist_on:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and not bit_exact:
+    if args.full and rank == 0 and not bit_exact:
         sys.exit("C5: the sharded result differs from the one-GPU fusion")
 
 
@@ -765,6 +818,44 @@ def run_stand_in(args, rank, world):
         dist.destroy_process_group()
 
 
+def headline(args, world, B, value, elapsed):
+    """The fields of the batch-mode line that the timed steps alone decide."""
+    if args.pipeline >= 2:
+        pipeline = (f"{args.pipeline} fusion lanes: batch k warped, registered and fused on lane "
+                    f"k % {args.pipeline} (own contexts, streams and buffers; each lane warps its "
+                    f"next batch on a second stream; Jacobi passes planned for {LANE_SHARE:.2f} "
+                    f"of the chip)")
+    elif args.pipeline:
+        pipeline = ("warp of batch k+1 on a second stream beside the fusion of batch k, from the "
+                    "end of its level-0 sweeps")
+    else:
+        pipeline = "off"
+    return {
+        "metric": METRIC,
+        "value": value,
+        "unit": "panoramas/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (box-room scenes; tiles from the E->P warp + synthetic depth-net "
+                "response; baseline = biased noisy u16 low-res scene)",
+        "config": {"workload": f"C3/C4: {B} panoramas per GPU per step, 2048x1024 output, "
+                               f"20 tiles of 512x512 (5x4 layout), 512x256 baseline",
+                   "global_batch": B * world, "out": "2048x1024", "tiles": "20x512x512",
+                   "parallelism": f"dp{world} (panorama sharding, no collective)",
+                   "pipeline": pipeline,
+                   "layout_caches": "tap maps, warp corner tables and level tables are built "
+                                    "once per layout and panorama size, outside the timed steps "
+                                    "(every step re-warps, re-registers and re-fuses the whole "
+                                    "batch)"},
+    }
+
+
 def main():
     args = parse()
     rc = launch_ranks(args)
@@ -833,6 +924,21 @@ def main():
     # hand-off wait timed out in any of them
     for c in ctxs:
         c.synchronize()
+    value = B * world * args.steps / elapsed
+    head = headline(args, world, B, value, elapsed)
+    if args.dump_outputs:  # the buffers the last timed step wrote (in lane mode: its lane's)
+        o_last, c_last = out, coeffs
+        if args.pipeline >= 2 and args.warmup + args.steps > 0:
+            _, _, o_last, c_last = lanes[(args.warmup + args.steps - 1) % args.pipeline]
+        dump_outputs(args.dump_outputs, o_last, c_last, rank, world)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(dict(head, backend=args.backend if world > 1 else None,
+                                  comm_check=comm_res)), flush=True)
+        if dist_on:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # Per-kernel roofline: the same steps again with the library's hipEvent stage timers on
     # (recorded on the stream the kernels run on).  With the timers on, the library runs each
     # batch unsplit (no half-batch stream overlap), so every stage's time is its own.
@@ -909,8 +1015,6 @@ def main():
               "workload": "C5 on one GPU: one 8192x4096 panorama, 80 tiles of 1024^2 (10x8), "
                           "2048x1024 baseline, 4 levels (bench.py --mode c5 at world 1)"}
 
-    total_panos = B * world * args.steps
-    value = total_panos / elapsed
     jms, jbytes, jlaunch = prof["jacobi"]
     achieved = jbytes / (jms * 1e-3) / 1e9 if jms > 0 else 0.0
     jtf = jbytes / 12.0 * 14.0 / (jms * 1e-3) / 1e12 if jms > 0 else 0.0
@@ -957,35 +1061,7 @@ def main():
 
     if rank == 0:
         line = {
-            "metric": METRIC,
-            "value": value,
-            "unit": "panoramas/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (box-room scenes; tiles from the E->P warp + synthetic depth-net "
-                    "response; baseline = biased noisy u16 low-res scene)",
-            "config": {"workload": f"C3/C4: {B} panoramas per GPU per step, 2048x1024 output, "
-                                   f"20 tiles of 512x512 (5x4 layout), 512x256 baseline",
-                       "global_batch": B * world, "out": "2048x1024", "tiles": "20x512x512",
-                       "parallelism": f"dp{world} (panorama sharding, no collective)",
-                       "pipeline": (f"{args.pipeline} fusion lanes: batch k warped, registered "
-                                    f"and fused on lane k % {args.pipeline} (own contexts, streams "
-                                    f"and buffers; each lane warps its next batch on a second "
-                                    f"stream; Jacobi passes planned for {LANE_SHARE:.2f} of the "
-                                    f"chip)" if args.pipeline >= 2 else
-                                    "warp of batch k+1 on a second stream beside the fusion "
-                                    "of batch k, from the end of its level-0 sweeps"
-                                    if args.pipeline else "off"),
-                       "layout_caches": "tap maps, warp corner tables and level tables are "
-                                        "built once per layout and panorama size, outside the "
-                                        "timed steps (every step re-warps, re-registers and "
-                                        "re-fuses the whole batch)"},
+            **head,
             # Headline: the dominant stage -- the Jacobi sweeps of one step, i.e. the resident
             # level-0 kernel (k_jres, all 200 sweeps in one launch) and the temporally blocked
             # passes of the finer levels (k_jlag) -- against its real roof, VALU issue:

@@ -35,8 +35,8 @@ def test_c4_eight_ranks_every_rank_checked(tmp_path):
         env.pop(k, None)
     dump = tmp_path / "samples"
     cmd = [sys.executable, "bench.py", "--gpus", str(WORLD), "--same-device", "--backend", "gloo",
-           "--batch", str(B), "--steps", str(STEPS), "--warmup", "1", "--prof-steps", "1",
-           "--no-cpu-baseline", "--no-extra-configs", "--sample-dump", str(dump)]
+           "--batch", str(B), "--steps", str(STEPS), "--warmup", "1", "--full", "--prof-steps",
+           "1", "--no-cpu-baseline", "--no-extra-configs", "--sample-dump", str(dump)]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=840, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

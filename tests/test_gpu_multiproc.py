@@ -36,7 +36,8 @@ def _port():
 def _launch(args, timeout=600):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2",
-           "--backend", "gloo", "--same-device", "--no-cpu-baseline", "--no-extra-configs"] + args
+           "--backend", "gloo", "--same-device", "--full", "--no-cpu-baseline",
+           "--no-extra-configs"] + args
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -79,8 +80,8 @@ def test_bench_gpus2_self_launch_same_device():
     """`bench.py --gpus 2` without torchrun launches two ranks itself."""
     B = 4
     r = _direct(["--gpus", "2", "--same-device", "--backend", "gloo", "--batch", str(B),
-                 "--steps", "2", "--warmup", "1", "--prof-steps", "1", "--no-cpu-baseline",
-                 "--no-extra-configs"])
+                 "--steps", "2", "--warmup", "1", "--full", "--prof-steps", "1",
+                 "--no-cpu-baseline", "--no-extra-configs"])
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -30,7 +30,7 @@ def _port():
 def _launch(args, timeout=400):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "1",
-           "--no-cpu-baseline", "--no-extra-configs"] + args
+           "--full", "--no-cpu-baseline", "--no-extra-configs"] + args
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=timeout, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

@@ -48,16 +48,16 @@ for s in $STEPS; do
       timeout -k 10 300 python -c 'import __graft_entry__ as g; g.smoke()' > $OUT/smoke.log 2>&1; rc=$?
       echo "smoke rc=$rc"; tail -3 $OUT/smoke.log; [ $rc -eq 0 ] || exit $rc ;;
     bench)
-      timeout -k 10 600 python bench.py > $OUT/bench.log 2>&1; rc=$?
+      timeout -k 10 600 python bench.py --full > $OUT/bench.log 2>&1; rc=$?
       echo "bench rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/bench.log; exit $rc; }; summ $OUT/bench.log bench ;;
     prof)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- \
-        python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/prof.log 2>&1; rc=$?
+        python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/prof.log 2>&1; rc=$?
       echo "prof rc=$rc"; tail -2 $OUT/prof.log | cut -c1-300; [ $rc -eq 0 ] || exit $rc ;;
     serial)
       rm -rf $OUT/serial; mkdir -p $OUT/serial
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/serial/prof -o run --output-format csv -- \
-        python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra-configs --pipeline 0 > $OUT/serial/bench.log 2>&1; rc=$?
+        python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extra-configs --pipeline 0 > $OUT/serial/bench.log 2>&1; rc=$?
       echo "serial rc=$rc"; [ $rc -eq 0 ] || exit $rc
       python3 tools/ktrace_levels.py $(find $OUT/serial/prof -name "run_kernel_trace.csv" | head -1) > $OUT/serial/levels.txt
       tail -12 $OUT/serial/levels.txt ;;
@@ -67,7 +67,7 @@ for s in $STEPS; do
           name=${v%%:*}; envs=${v#*:}; d=$OUT/serial_$name.$r; rm -rf $d; mkdir -p $d
           ( for kv in ${envs//,/ }; do [ -n "$kv" ] && export "$kv"; done
             timeout -k 10 300 rocprofv3 --kernel-trace -d $d/prof -o run --output-format csv -- \
-              python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra-configs --pipeline 0 ${BENCH_ARGS:-} > $d/bench.log 2>&1 ); rc=$?
+              python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extra-configs --pipeline 0 ${BENCH_ARGS:-} > $d/bench.log 2>&1 ); rc=$?
           [ $rc -eq 0 ] || { echo "$name rc=$rc"; tail -5 $d/bench.log; exit $rc; }
           python3 tools/ktrace_levels.py $(find $d/prof -name "run_kernel_trace.csv" | head -1) > $d/levels.txt
           echo "== $name.$r"; cat $d/levels.txt
@@ -76,10 +76,10 @@ for s in $STEPS; do
     pmc)
       bash tools/pmc_round.sh; rc=$?; [ $rc -eq 0 ] || exit $rc ;;
     c5)
-      timeout -k 10 300 python bench.py --mode c5 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_c5.log 2>&1; rc=$?
+      timeout -k 10 300 python bench.py --full --mode c5 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_c5.log 2>&1; rc=$?
       echo "c5 rc=$rc"; tail -c 800 $OUT/bench_c5.log; [ $rc -eq 0 ] || exit $rc ;;
     c4)
-      timeout -k 10 600 python3 bench.py --gpus 8 --same-device --backend gloo --steps 3 --warmup 1 \
+      timeout -k 10 600 python3 bench.py --full --gpus 8 --same-device --backend gloo --steps 3 --warmup 1 \
         --no-cpu-baseline --no-extra-configs --prof-steps 1 > $OUT/c4_8rank.log 2>&1; rc=$?
       echo "c4 rc=$rc"; tail -c 1200 $OUT/c4_8rank.log; [ $rc -eq 0 ] || exit $rc ;;
     rgb)
@@ -103,7 +103,7 @@ for s in $STEPS; do
                  "GRBM_GUI_ACTIVE SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS SQ_ACTIVE_INST_LDS"; do
         i=$((i + 1))
         timeout -k 5 -s KILL 120 rocprofv3 --pmc $set -d $OUT/jsq/p$i -o run --output-format csv -- \
-          python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs --pipeline 0 > $OUT/jsq/p$i.log 2>&1; rc=$?
+          python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs --pipeline 0 > $OUT/jsq/p$i.log 2>&1; rc=$?
         [ $rc -eq 0 ] || { echo "jsq pass $i rc=$rc"; tail -3 $OUT/jsq/p$i.log; exit $rc; }
       done
       python3 tools/pmc_summary.py "$OUT/jsq/p*/*counter_collection.csv" | grep -A14 -E "k_jlag|k_jres" > $OUT/jsq/summary.txt
@@ -114,7 +114,7 @@ for s in $STEPS; do
         for v in ${VARIANTS:-base:}; do
           name=${v%%:*}; envs=${v#*:}
           ( for kv in ${envs//,/ }; do [ -n "$kv" ] && export "$kv"; done
-            timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra-configs ${BENCH_ARGS:-} \
+            timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra-configs ${BENCH_ARGS:-} \
               > $OUT/ab/$name.$r.log 2>&1 ); rc=$?
           [ $rc -eq 0 ] || { echo "$name rc=$rc"; tail -5 $OUT/ab/$name.$r.log; exit $rc; }
           summ $OUT/ab/$name.$r.log $name
