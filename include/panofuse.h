@@ -333,6 +333,32 @@ int pf_error_metrics(pf_ctx* ctx, const float* gt, int gw, int gh, int gc, const
 #define PF_METRICS_SEQUENTIAL 1
 int pf_set_metrics_order(pf_ctx* ctx, int order);
 
+/* ---- edge-fidelity metrics: ErrorLaplacian (Depth.cpp:2636-2953) ----
+ * Error of the 3x3 Laplacian (mse, mae), of Sobel X and Sobel Y (mae) and of the 5x5 LoG filter
+ * (mae) between gt [batch][gh][gw][gc] (channel 0) and a given map of w x h pixels: a float map
+ * [batch][h][w][given_c] (channel 0) or the u16 result given16 [batch][h][w], read as
+ * (float)v / 65535.0f -- exactly one of the two.  Per given pixel (x, y) the gt taps sit at
+ * X = (int)((float)x * ((float)gw / (float)w)), Y likewise; the 3x3 samples run over
+ * [1, w-2] x [1, h-2], the 5x5 samples over [2, w-3] x [2, h-3].  Taps are floats widened to
+ * double and the filters are evaluated in fp64 in the reference's operand order, so every
+ * per-pixel term and every count is the reference's; the means are fixed-order fp64 tree sums
+ * (deterministic; within 2 * w*h * 2^-53 relative of the exact sum of the terms).  A sample
+ * counts when its gt taps are valid ((double)tap >= 1e-4): the five cross taps (Laplacian), all
+ * 25 (LoG), and for Sobel the reference's list as written (Depth.cpp:2747-2748 never tests
+ * val[1][0] and val[2][0]).  A mean over no sample is NaN (0 / 0), as in the reference; maps
+ * narrower or shorter than 3 are legal and give exactly that.
+ * out: DEVICE array of batch pf_edge_metrics.  gt_lap / given_lap / lap_ae: DEVICE double
+ * [batch][h][w] planes or NULL -- the gt Laplacian, the given map's Laplacian and their absolute
+ * error (Depth.cpp:2666-2683, :2737-2742), zero where the Laplacian sample is invalid or outside
+ * the inner region.  Stream-ordered. */
+typedef struct pf_edge_metrics {
+    double lap_mse, lap_mae, sobelx_mae, sobely_mae, lap5_mae;
+    int64_t n_lap, n_sobel, n_lap5;
+} pf_edge_metrics;                       /* 64 bytes */
+int pf_error_laplacian(pf_ctx* ctx, const float* gt, int gw, int gh, int gc, const float* given,
+                       const uint16_t* given16, int w, int h, int given_c, int batch,
+                       pf_edge_metrics* out, double* gt_lap, double* given_lap, double* lap_ae);
+
 /* Depth2DepthTransform of one map (Depth.cpp:245-274): channel 0 of npix pixels of a DEVICE
  * buffer with `channels` interleaved channels, X = clamp(v, 1e-4, 1-1e-4),
  * v' = clamp01(a X^3 + b X^2 + c X + d) in the reference's fp32 order; abcd is a HOST float[4]. */

@@ -15,6 +15,7 @@
  *   SolveDepthAll                                                      Depth.h:306-307
  *   SolveDepthBySmoothing                                              Depth.h:309
  *   ErrorData / ErrorEmap                                              Depth.h:313-316
+ *   ErrorLaplacian                                                     Depth.h:321-323
  *   SphericalToWorld / WorldToSpherical                                Depth.h:326-329
  *   Save16BitPNG                                                       Depth.cpp:27-32
  *   g_zenith_range                                                     Depth.cpp:22
@@ -29,8 +30,8 @@
  * and glibc calls (csrc/pf_geom.hpp), bit-identical to it; the per-pixel path runs on the GPU.
  *
  * Not provided: SolveDisparityToDepth (declared, never defined: Depth.h:293) and
- * SolveDepthToDepth2 (never called), ErrorCompare / ErrorLaplacian, the triangulation/subdivision
- * members (vertices, faces, subd_*: never used on the path).
+ * SolveDepthToDepth2 (never called), ErrorCompare, the triangulation/subdivision members
+ * (vertices, faces, subd_*: never used on the path).
  */
 #pragma once
 
@@ -246,6 +247,25 @@ bool ErrorEmap(EquirectangularMap& emap_gt, EquirectangularMap& emap_given, floa
                float& delta3, int align_way, bool cap_depth,
                Vec2f* least_square_shift = nullptr, float* median_shift_factor = nullptr);
 
+/* Edge-fidelity errors between a ground-truth map and a given map, both loaded with
+ * EquirectangularMap::Load (Depth.cpp:2636-2953): mse and mae of the 3x3 Laplacian, mae of
+ * Sobel X, Sobel Y and of the 5x5 LoG filter, computed on the GPU (pf_error_laplacian) and
+ * printed as the reference's "[ErrorLap] ..." line.  The three file-name arguments are accepted
+ * and ignored: the reference's own writing of those images is commented out (Depth.cpp:2779-2830),
+ * so it never produces them either.  (pf_error_laplacian returns the three Laplacian maps as
+ * device planes for callers that want them.) */
+bool ErrorLaplacian(std::string& gt_filename, std::string& baseline_filename,
+                    double& Laplacian_mse, double& Laplacian_mae, double& SobelX_mae,
+                    double& SobelY_mae, double& Laplacian5x5_mae,
+                    std::string* gt_Laplacian_fn = nullptr,
+                    std::string* baseline_Laplacian_fn = nullptr,
+                    std::string* Laplacian_ae_fn = nullptr);
+/* The same for maps already in memory; counts (optional): long long[3] = the numbers of
+ * Laplacian, Sobel and 5x5 samples behind the means. */
+bool ErrorLaplacian(EquirectangularMap& emap_gt, EquirectangularMap& emap_baseline,
+                    double& Laplacian_mse, double& Laplacian_mae, double& SobelX_mae,
+                    double& SobelY_mae, double& Laplacian5x5_mae, long long* counts = nullptr);
+
 /* spherical coord. (radians) to 3d position (Depth.cpp:2955-2958) */
 Vec3f SphericalToWorld(float azimuth, float zenith);
 /* 3d position to spherical coord.; p is normalized in place (Depth.cpp:2960-2971) */
@@ -257,6 +277,8 @@ Vec2f WorldToSpherical(Vec3f& p);
  * "png" (MiDaS naming, Main.cpp:570-573), "jpg" (LeReS naming, :576-578) or "auto"; the LeReS
  * layout of Main.cpp:788-843 is used.  shard / nshards: this process takes the panoramas
  * shard, shard + nshards, ... of the sorted folder (one process per GPU, no communication).
+ * With PF_EDGE_METRICS=1 in the environment (panofuse_main --edge-metrics) each panorama also
+ * gets <raw>.edges.txt: ErrorLaplacian of the result and of the baseline against the gt.
  * Returns the process exit code. */
 int pf_create_depth_panoramas(const std::string& rgb_folder, const std::string& gt_folder,
                               const std::string& baseline_folder,

@@ -2539,6 +2539,55 @@ int pf_error_metrics(pf_ctx* c, const float* gt, int gw, int gh, int gc, const f
     return PF_OK;
 }
 
+int pf_error_laplacian(pf_ctx* c, const float* gt, int gw, int gh, int gc, const float* given,
+                       const uint16_t* given16, int w, int h, int given_c, int batch,
+                       pf_edge_metrics* out, double* gt_lap, double* given_lap, double* lap_ae)
+{
+    if (!c) return PF_EINVAL;
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, PF_EHIP, "hipSetDevice failed");
+    if (!gt || !out || (!given == !given16))
+        return fail(c, PF_EINVAL,
+                    "pf_error_laplacian: need gt, out and exactly one of given/given16");
+    if (gw < 1 || gh < 1 || gc < 1 || w < 1 || h < 1 || (given && given_c < 1))
+        return fail(c, PF_EINVAL, "pf_error_laplacian: bad shape gt %dx%dx%d given %dx%dx%d", gw,
+                    gh, gc, w, h, given_c);
+    if (batch <= 0 || batch > 65535) return fail(c, PF_EINVAL, "batch %d out of range", batch);
+    if ((long long)w * h >= (1ll << 31) || (long long)gw * gh * gc >= (1ll << 31) ||
+        (given && (long long)w * h * given_c >= (1ll << 31)))
+        return fail(c, PF_EINVAL, "pf_error_laplacian: map too large");
+    EdgeJob j;
+    j.gt = gt;
+    j.gw = gw;
+    j.gh = gh;
+    j.gc = gc;
+    j.given = given;
+    j.given16 = given16;
+    j.w = w;
+    j.h = h;
+    j.gc_given = given16 ? 1 : given_c;
+    j.batch = batch;
+    j.gt_lap = gt_lap;
+    j.given_lap = given_lap;
+    j.lap_ae = lap_ae;
+    const long long rows = ((long long)h + EDGE_TILE_Y - 1) / EDGE_TILE_Y;
+    const long long cols = ((long long)w + EDGE_TILE_X - 1) / EDGE_TILE_X;
+    if (rows > 65535 || rows * cols * batch >= (1ll << 31))
+        return fail(c, PF_EINVAL, "pf_error_laplacian: %dx%d x %d panoramas: too many tiles", w, h,
+                    batch);
+    int rc;
+    if ((rc = ensure(c, c->metrics_ws, edge_workspace_bytes(j))))
+        return rc;
+    // algorithmic bytes: one read of gt (4 B, channel 0) and of the given map (2 B u16 / 4 B
+    // f32), plus 8 B per pixel for each requested plane
+    const int planes = (gt_lap ? 1 : 0) + (given_lap ? 1 : 0) + (lap_ae ? 1 : 0);
+    StageTimer t(c, PF_STAGE_METRICS,
+                 batch * ((double)gw * gh * 4.0 + (double)w * h * ((given16 ? 2.0 : 4.0) + 8.0 * planes)),
+                 2);
+    launch_edge(c->stream, j, c->metrics_ws.p, out);
+    HIPCHK(c, hipGetLastError());
+    return PF_OK;
+}
+
 int pf_depth_transform(pf_ctx* c, float* data, long long npix, int channels, const float* abcd)
 {
     if (!c) return PF_EINVAL;

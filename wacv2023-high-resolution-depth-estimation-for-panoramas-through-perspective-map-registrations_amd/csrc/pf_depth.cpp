@@ -571,6 +571,67 @@ bool ErrorEmap(EquirectangularMap& gt, EquirectangularMap& given, float& mse, fl
     return true;
 }
 
+// ---- ErrorLaplacian (Depth.cpp:2636-2953) ----
+namespace {
+bool run_edge(EquirectangularMap& gt, EquirectangularMap& given, pf_edge_metrics& m)
+{
+    pf_ctx* c = facade_ctx();
+    if (!c || !gt.data || !given.data) return false;
+    const size_t ng = (size_t)gt.width * gt.height * gt.channels;
+    const size_t nv = (size_t)given.width * given.height * given.channels;
+    DevMem dg(ng * sizeof(float)), dv(nv * sizeof(float)), dm(sizeof(pf_edge_metrics));
+    if (!upload(dg, gt.data, ng) || !upload(dv, given.data, nv) || !dm.ok) return false;
+    if (!pf_ok(c, pf_error_laplacian(c, dg.as<float>(), gt.width, gt.height, gt.channels,
+                                     dv.as<float>(), nullptr, given.width, given.height,
+                                     given.channels, 1, dm.as<pf_edge_metrics>(), nullptr,
+                                     nullptr, nullptr),
+               "pf_error_laplacian"))
+        return false;
+    return hip_ok(hipMemcpy(&m, dm.p, sizeof(m), hipMemcpyDeviceToHost), "edge metrics download");
+}
+}  // namespace
+
+bool ErrorLaplacian(EquirectangularMap& emap_gt, EquirectangularMap& emap_baseline,
+                    double& Laplacian_mse, double& Laplacian_mae, double& SobelX_mae,
+                    double& SobelY_mae, double& Laplacian5x5_mae, long long* counts)
+{
+    pf_edge_metrics m;
+    if (!run_edge(emap_gt, emap_baseline, m)) return false;
+    Laplacian_mse = m.lap_mse;
+    Laplacian_mae = m.lap_mae;
+    SobelX_mae = m.sobelx_mae;
+    SobelY_mae = m.sobely_mae;
+    Laplacian5x5_mae = m.lap5_mae;
+    if (counts) {
+        counts[0] = m.n_lap;
+        counts[1] = m.n_sobel;
+        counts[2] = m.n_lap5;
+    }
+    std::cout << "[ErrorLap] Lap_mse:" << Laplacian_mse << " Lap_mae:" << Laplacian_mae
+              << " SobelX:" << SobelX_mae << " SobelY:" << SobelY_mae
+              << " Lap5x5:" << Laplacian5x5_mae << std::endl;  // Depth.cpp:2950-2951
+    return true;
+}
+
+bool ErrorLaplacian(std::string& gt_filename, std::string& baseline_filename,
+                    double& Laplacian_mse, double& Laplacian_mae, double& SobelX_mae,
+                    double& SobelY_mae, double& Laplacian5x5_mae, std::string*, std::string*,
+                    std::string*)
+{
+    EquirectangularMap emap_gt;
+    if (!emap_gt.Load(gt_filename)) {
+        std::cout << "cannot load emap_gt? " << gt_filename << std::endl;
+        return false;
+    }
+    EquirectangularMap emap_baseline;
+    if (!emap_baseline.Load(baseline_filename)) {
+        std::cout << "cannot load emap_baseline? " << baseline_filename << std::endl;
+        return false;
+    }
+    return ErrorLaplacian(emap_gt, emap_baseline, Laplacian_mse, Laplacian_mae, SobelX_mae,
+                          SobelY_mae, Laplacian5x5_mae);
+}
+
 bool MergeDepthMaps(std::string& emap_fn, std::vector<std::string>& pmap_fns,
                     std::string& out_fn, std::vector<Vec4f>& fovs, std::vector<Vec4f>& ranges,
                     int out_width, Vec2f& zr, std::string* gt_fn, Metrics* metrics,
@@ -722,6 +783,38 @@ void pf_leres_layout(std::vector<Vec4f>& fovs, std::vector<Vec4f>& ranges)
                                    (float)PF_D2R(rz[b][1])));
 }
 
+// The opt-in edge metrics of mode 0: ErrorLaplacian of the written result and of the baseline
+// against the gt, one `name: %f` line per value in the style of Metrics::Save.
+static bool save_edge_metrics(std::string gt_fn, std::string base_fn, std::string result_fn,
+                              const std::string& txt_fn)
+{
+    using DepthNamespace::EquirectangularMap;
+    EquirectangularMap gt, base, result;
+    if (!gt.Load(gt_fn) || !base.Load(base_fn) || !result.Load(result_fn)) return false;
+    double g[5], r[5];
+    long long ng[3], nr[3];
+    if (!DepthNamespace::ErrorLaplacian(gt, base, g[0], g[1], g[2], g[3], g[4], ng) ||
+        !DepthNamespace::ErrorLaplacian(gt, result, r[0], r[1], r[2], r[3], r[4], nr))
+        return false;
+    FILE* fp = std::fopen(txt_fn.c_str(), "w+");
+    if (!fp) {
+        std::cout << "fopen failed?" << std::endl;
+        return false;
+    }
+    const char* names[5] = {"lap_mse", "lap_mae", "sobelx_mae", "sobely_mae", "lap5_mae"};
+    const char* counts[3] = {"n_lap", "n_sobel", "n_lap5"};
+    for (int k = 0; k < 5; ++k) {
+        std::fprintf(fp, "%s_given: %f\n", names[k], g[k]);
+        std::fprintf(fp, "%s_result: %f\n", names[k], r[k]);
+    }
+    for (int k = 0; k < 3; ++k) {
+        std::fprintf(fp, "%s_given: %lld\n", counts[k], ng[k]);
+        std::fprintf(fp, "%s_result: %lld\n", counts[k], nr[k]);
+    }
+    std::fclose(fp);
+    return true;
+}
+
 int pf_create_depth_panoramas(const std::string& rgb_folder, const std::string& gt_folder,
                               const std::string& baseline_folder,
                               const std::string& result_folder, const std::string& tile_dir,
@@ -729,6 +822,9 @@ int pf_create_depth_panoramas(const std::string& rgb_folder, const std::string& 
                               int nshards)
 {
     namespace fs = std::filesystem;
+    // PF_EDGE_METRICS=1 (panofuse_main --edge-metrics): <raw>.edges.txt beside .aligned.txt
+    const char* em = std::getenv("PF_EDGE_METRICS");
+    const bool edge_metrics = em && em[0] == '1';
     std::vector<Vec4f> fovs, ranges;
     pf_leres_layout(fovs, ranges);
     std::vector<std::string> rgb;  // AllFilesInFolder (Main.cpp:50-83): files only
@@ -791,6 +887,8 @@ int pf_create_depth_panoramas(const std::string& rgb_folder, const std::string& 
             return 1;
         }
         m.Save((join(result_folder, rawname) + ".aligned.txt").c_str());
+        if (edge_metrics && !save_edge_metrics(gt, base, out, join(result_folder, rawname) + ".edges.txt"))
+            std::cout << "[CreateDepthPanorma] no edge metrics for #" << i << std::endl;
         all.push_back(m);
         std::cout << "time_Reg:" << tr << " time_Laplacian:" << tl << std::endl;
     }

@@ -419,6 +419,17 @@ void launch_smooth(hipStream_t s, const TileGeom* geom, int ntiles, const int2* 
                    const float* coeffs, int w, int h, int h0, int h1, int iters, float* buf,
                    int batch);
 
+// (float)u / 65535.0f, correctly rounded, without the division sequence: one multiply by the
+// reciprocal and one fma refinement.  Exhaustively equal to the division for every u in
+// [0, 65535] (checked on the host with glibc fmaf: tests/test_oracle_metrics.py).
+__device__ __forceinline__ float u16_unit(uint32_t u)
+{
+    const float rcp = 1.0f / 65535.0f;
+    const float x = (float)u;
+    const float q = x * rcp;
+    return fmaf(fmaf(-q, 65535.0f, x), rcp, q);
+}
+
 // Accuracy metrics (pf_metrics.hip).
 struct MetricsJob {
     const float* gt;
@@ -433,5 +444,19 @@ struct MetricsJob {
 size_t metrics_workspace_bytes(const MetricsJob& j);
 void launch_d2d_map(hipStream_t s, float* data, long long npx, int c, const float* abcd);
 void launch_metrics(hipStream_t s, const MetricsJob& j, void* ws, pf_metrics* out);
+
+// Edge-fidelity metrics (pf_edge.hip): ErrorLaplacian, Depth.cpp:2636-2953.
+constexpr int EDGE_TILE_X = 128, EDGE_TILE_Y = 32;  // given-map pixels per block
+struct EdgeJob {
+    const float* gt;
+    int gw, gh, gc;
+    const float* given;
+    const uint16_t* given16;
+    int w, h, gc_given, batch;
+    double *gt_lap, *given_lap, *lap_ae;  // optional [batch][h][w] planes (NULL: not written)
+};
+bool edge_staged(const EdgeJob& j);  // gt of the given map's size: both tiles staged in LDS
+size_t edge_workspace_bytes(const EdgeJob& j);
+void launch_edge(hipStream_t s, const EdgeJob& j, void* ws, pf_edge_metrics* out);
 
 }  // namespace pf

@@ -1,8 +1,11 @@
 // panofuse_main -- the reference's command line (Main.cpp:864-895) for the fusion path:
 //   panofuse_main 0 <rgb_dir> <gt_dir> <baseline_dir> <result_dir> [--tiles DIR]
 //                 [--ext auto|jpg|png] [--width W] [--device D] [--shard R/N]
-//                 [--metrics-order tree|sequential]
+//                 [--metrics-order tree|sequential] [--edge-metrics]
 //   panofuse_main export <rgb_dir> <tile_dir> [--device D]
+//   panofuse_main lap <gt_file> <given_file> [--device D]
+// "lap" is the reference's ErrorLaplacian (Depth.cpp:2636-2953) on two image files: its
+// "[ErrorLap] ..." line, then one line with the three sample counts.
 // "export" is the tile render of mode 0 (Main.cpp:399-430, SaveCubeMap :242-326) on the GPU:
 // each RGB panorama becomes the 15 LeReS perspective tiles the depth network consumes.
 // Mode 0 = CreateDepthPanoramas (Main.cpp:331-687) minus the OpenGL tile export: the perspective
@@ -11,6 +14,8 @@
 // --metrics-order: the .aligned.txt means in the reference's row-major float order (sequential,
 // the default: the digits Main.cpp prints) or in the fp64-tree order (tree: deterministic, within
 // ~1e-3 relative of the reference's float sums).
+// --edge-metrics (opt-in, takes no value): also write <raw>.edges.txt per panorama, the
+// ErrorLaplacian values of the result and of the baseline against the gt.
 #include "../../include/pf_depth.h"
 
 #include <hip/hip_runtime.h>
@@ -26,8 +31,9 @@ int main(int argc, char* argv[])
         std::cout << "usage: " << argv[0]
                   << " 0 <rgb_dir> <gt_dir> <baseline_dir> <result_dir> [--tiles DIR]"
                      " [--ext auto|jpg|png] [--width W] [--device D] [--shard R/N]"
-                     " [--metrics-order tree|sequential]\n       "
-                  << argv[0] << " export <rgb_dir> <tile_dir> [--device D]" << std::endl;
+                     " [--metrics-order tree|sequential] [--edge-metrics]\n       "
+                  << argv[0] << " export <rgb_dir> <tile_dir> [--device D]\n       "
+                  << argv[0] << " lap <gt_file> <given_file> [--device D]" << std::endl;
         return 0;
     }
     const std::string cmd(argv[1]);
@@ -44,6 +50,34 @@ int main(int argc, char* argv[])
         }
         return pf_export_rgb_tiles(argv[2], argv[3]);
     }
+    if (cmd == "lap") {
+        if (argc < 4) {
+            std::cout << "usage: " << argv[0] << " lap <gt_file> <given_file> [--device D]"
+                      << std::endl;
+            return 1;
+        }
+        const int dev = argc >= 6 && std::string(argv[4]) == "--device" ? std::atoi(argv[5]) : 0;
+        if (hipSetDevice(dev) != hipSuccess) {
+            std::cout << "no HIP device " << dev << std::endl;
+            return 1;
+        }
+        std::string gt_fn(argv[2]), given_fn(argv[3]);
+        DepthNamespace::EquirectangularMap gt, given;
+        if (!gt.Load(gt_fn)) {
+            std::cout << "cannot load emap_gt? " << gt_fn << std::endl;
+            return 1;
+        }
+        if (!given.Load(given_fn)) {
+            std::cout << "cannot load emap_baseline? " << given_fn << std::endl;
+            return 1;
+        }
+        double v[5];
+        long long n[3];
+        if (!DepthNamespace::ErrorLaplacian(gt, given, v[0], v[1], v[2], v[3], v[4], n)) return 1;
+        std::cout << "[ErrorLap] n_lap:" << n[0] << " n_sobel:" << n[1] << " n_lap5:" << n[2]
+                  << std::endl;
+        return 0;
+    }
     if (cmd != "0") return 0;  // Main.cpp:889-893: other commands do nothing
     if (argc < 6) {
         std::cout << "[CreateDepthPanormas] error: need argc>=6" << std::endl;
@@ -51,8 +85,15 @@ int main(int argc, char* argv[])
     }
     std::string tiles = "test_images", ext = "auto";
     int width = 2048, device = 0, shard = 0, nshards = 1;
-    for (int i = 6; i + 1 < argc; i += 2) {
-        const std::string k(argv[i]), v(argv[i + 1]);
+    for (int i = 6; i < argc; i += 2) {
+        const std::string k(argv[i]);
+        if (k == "--edge-metrics") {  // a flag without a value
+            setenv("PF_EDGE_METRICS", "1", 1);  // read by pf_create_depth_panoramas
+            --i;
+            continue;
+        }
+        if (i + 1 >= argc) break;
+        const std::string v(argv[i + 1]);
         if (k == "--tiles") tiles = v;
         else if (k == "--ext") ext = v;
         else if (k == "--width") width = std::atoi(v.c_str());

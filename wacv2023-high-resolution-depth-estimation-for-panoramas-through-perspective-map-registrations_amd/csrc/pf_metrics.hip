@@ -51,17 +51,6 @@ struct MArgs {
 
 // Depth.cpp:2033-2053 (ErrorData) / :2248-2268 (ErrorEmap): band row, nearest gt pixel, skip
 // invalid gt, cap at 10 m.
-// (float)u / 65535.0f, correctly rounded, without the division sequence: one multiply by the
-// reciprocal and one fma refinement.  Exhaustively equal to the division for every u in
-// [0, 65535] (checked on the host with glibc fmaf: tests/test_oracle_metrics.py).
-__device__ __forceinline__ float u16_unit(uint32_t u)
-{
-    const float rcp = 1.0f / 65535.0f;
-    const float x = (float)u;
-    const float q = x * rcp;
-    return fmaf(fmaf(-q, 65535.0f, x), rcp, q);
-}
-
 __device__ __forceinline__ bool finish_px(const MArgs& a, bool abs_skip, float& v0, float& v1)
 {
     const float t = abs_skip ? fabsf(v0) : v0;

@@ -32,7 +32,7 @@ EXPORTS = [
     "pf_probe_warp_coords", "pf_probe_rgb_taps", "pf_debug_smooth_fault",
     "pf_fuse_partial_rows", "pf_fuse_coverage_rows", "pf_fuse_normalize_rows",
     "pf_fuse_tile_rows", "pf_rows_add", "pf_fuse_level", "pf_fuse_targets",
-    "pf_rows_add_batch", "pf_set_jacobi_share",
+    "pf_rows_add_batch", "pf_set_jacobi_share", "pf_error_laplacian",
 ]
 NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
           "pf_debug_smooth_fault", "pf_fuse_partial_rows", "pf_fuse_coverage_rows",
@@ -99,6 +99,7 @@ def load():
     L.pf_register_joint.argtypes = [vp, vp, ip, ip, ip, vp, ip, fp, fp, ip, vp, vp, vp]
     L.pf_error_metrics.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, ip, ip, ip, fp, fp, ip, ip,
                                    vp]
+    L.pf_error_laplacian.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, ip, ip, ip, vp, vp, vp, vp]
     L.pf_set_solver.argtypes = [vp, ip]
     L.pf_fuse_normalize.argtypes = [vp, vp, vp, ip, ip, fp, fp, ip, vp]
     L.pf_fuse_multicover.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, ip, vp,
@@ -170,6 +171,9 @@ def _emap_dims(emap):
 # pf_metrics field order (include/panofuse.h)
 METRIC_KEYS = ("mse", "mae", "mre", "mselog", "delta1", "delta2", "delta3", "median_shift",
                "ls_s", "ls_o", "gt_median", "given_median")
+# pf_edge_metrics field order (include/panofuse.h): five doubles, three int64 counts
+EDGE_KEYS = ("lap_mse", "lap_mae", "sobelx_mae", "sobely_mae", "lap5_mae")
+EDGE_COUNTS = ("n_lap", "n_sobel", "n_lap5")
 
 
 class Fuser:
@@ -315,6 +319,42 @@ class Fuser:
             d["n"], d["nlog"] = int(o[b, 12]), int(o[b, 13])
             res.append(d)
         return res
+
+    def edge_metrics_async(self, gt, given, out, gt_lap=None, given_lap=None, lap_ae=None):
+        """pf_error_laplacian into out (int64 [B,8] device tensor = B pf_edge_metrics), no sync.
+        gt_lap / given_lap / lap_ae: optional float64 [B,h,w] device tensors for the maps."""
+        import torch
+        gw, gh, gc = _emap_dims(gt)
+        B, h, w = given.shape[:3]
+        if given.dtype in (torch.int16, torch.uint16):
+            gf, g16, gvc = None, _ptr(given), 1
+        else:
+            gf, g16, gvc = _ptr(given), None, (given.shape[3] if given.dim() == 4 else 1)
+        self._check(self.L.pf_error_laplacian(self.h, _ptr(gt), gw, gh, gc, gf, g16, w, h, gvc,
+                                              B, _ptr(out), _ptr(gt_lap), _ptr(given_lap),
+                                              _ptr(lap_ae)))
+
+    def edge_metrics(self, gt, given, maps=False):
+        """ErrorLaplacian (Depth.cpp:2636-2953) of given (int16/uint16 [B,h,w] result bits, or
+        float32 [B,h,w] / [B,h,w,c]) against gt float32 [B,gh,gw] or [B,gh,gw,gc].  Returns a
+        list (one per panorama) of dicts of EDGE_KEYS + EDGE_COUNTS; with maps=True also the
+        three float64 [B,h,w] device tensors (gt Laplacian, given Laplacian, absolute error)."""
+        import torch
+        B, h, w = given.shape[:3]
+        out = torch.zeros((B, 8), dtype=torch.int64, device=gt.device)
+        planes = [torch.empty((B, h, w), dtype=torch.float64, device=gt.device)
+                  for _ in range(3)] if maps else [None, None, None]
+        self.edge_metrics_async(gt, given, out, *planes)
+        self.synchronize()
+        o = out.cpu()
+        f = o[:, :5].contiguous().view(torch.float64)
+        res = []
+        for b in range(B):
+            d = {k: float(f[b, i]) for i, k in enumerate(EDGE_KEYS)}
+            for i, k in enumerate(EDGE_COUNTS):
+                d[k] = int(o[b, 5 + i])
+            res.append(d)
+        return (res, *planes) if maps else res
 
     def probe_taps(self, out_w, zr, level):
         import torch
