@@ -359,6 +359,47 @@ int pf_error_laplacian(pf_ctx* ctx, const float* gt, int gw, int gh, int gc, con
                        const uint16_t* given16, int w, int h, int given_c, int batch,
                        pf_edge_metrics* out, double* gt_lap, double* given_lap, double* lap_ae);
 
+/* ---- two-map comparison: ErrorCompare (Depth.cpp:2460-2634; Depth.h:318-319) ----
+ * Scores a given map [batch][h][w][given_c] (channel 0) against gt [batch][gh][gw][gc] (channel 0)
+ * and makes the 8-bit picture the reference saves.  All arithmetic is fp32, one rounding per
+ * operation; conv(a, C) is DispDepthConversion of a C-channel map: where (double)fabsf(v) >= 1e-5,
+ * v = 1.0f / v, C times over (the reference loops over the channels but converts channel 0 each
+ * time, so a 3-channel map is inverted three times and a 2-channel map twice).
+ *   disp_depth == 0 (depth against depth): m = ErrorEmap(gt, given, align_way, cap_depth);
+ *     shifted = (unsigned char)(max(v, 0) * 255.0f) of the given map, depth = the given map's
+ *     channel 0; fit_s = fit_o = 0, vmin = FLT_MAX, vmax = -FLT_MAX, n_nonblack = 0.
+ *   disp_depth != 0 (the given map is a disparity, e.g. a mono360 PFM):
+ *     1. gt_disp = conv(gt, gc);
+ *     2. {fit_s, fit_o} = the least-squares {s, o} of ErrorEmap(gt_disp, given, 2, no cap);
+ *     3. v = given * fit_s + fit_o (multiply, then add);  4. v = conv(v, given_c);
+ *     5. v < 0 -> 0, v > 10 -> 10: the `depth` plane;
+ *     6. m = ErrorEmap(gt, v, align_way, cap_depth);
+ *     7. vmin / vmax over the pixels with (double)fabsf(v) >= 1e-4 ("non-black"), from
+ *        FLT_MAX / -FLT_MAX;  8. those pixels become (v - vmin) / (vmax - vmin);
+ *     9. shifted = (unsigned char)(max(v, 0) * 255.0f).
+ * Where the reference's behaviour is undefined: a product above 255 saturates to 255; NaN becomes 0
+ * in the u8 plane; every comparison otherwise follows IEEE as the source reads, so a NaN is not
+ * black (it counts in n_nonblack), does not move vmin / vmax and stays NaN in the depth plane; the
+ * facade writes no file for a null file name in disparity mode.
+ * The order set by pf_set_metrics_order applies to both inner ErrorEmap calls.  given is not
+ * written.  out: DEVICE array of batch pf_compare; depth: DEVICE float [batch][h][w] or NULL;
+ * shifted: DEVICE uint8 [batch][h][w] or NULL.  Stream-ordered, no host round trip: the fit and
+ * vmin / vmax stay on the device between the kernels. */
+typedef struct pf_compare {
+    pf_metrics m;            /* the final ErrorEmap call */
+    float fit_s, fit_o;      /* disparity fit {s, o}; 0, 0 in depth mode */
+    float vmin, vmax;        /* FLT_MAX, -FLT_MAX when no pixel qualified or in depth mode */
+    int32_t n_nonblack;      /* pixels that were normalised */
+    int32_t reserved[3];
+} pf_compare;                /* 96 bytes */
+int pf_error_compare(pf_ctx* ctx, const float* gt, int gw, int gh, int gc, const float* given,
+                     int w, int h, int given_c, int batch, float zr0, float zr1, int disp_depth,
+                     int align_way, int cap_depth, pf_compare* out, float* depth,
+                     uint8_t* shifted);
+/* EquirectangularMap::DispDepthConversion (Depth.cpp:587-610) in place: conv(data, channels) on
+ * channel 0 of npix pixels of a DEVICE buffer with `channels` interleaved channels. */
+int pf_disp_depth_convert(pf_ctx* ctx, float* data, long long npix, int channels);
+
 /* Depth2DepthTransform of one map (Depth.cpp:245-274): channel 0 of npix pixels of a DEVICE
  * buffer with `channels` interleaved channels, X = clamp(v, 1e-4, 1-1e-4),
  * v' = clamp01(a X^3 + b X^2 + c X + d) in the reference's fp32 order; abcd is a HOST float[4]. */

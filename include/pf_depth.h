@@ -5,7 +5,8 @@
  * -lpanofuse_depth -lpanofuse; the arithmetic runs in the HIP kernels of libpanofuse.
  *
  * Entry points and the reference interface each one replaces:
- *   EquirectangularMap::{Load, LoadPfm, ValueAtCoord, ValueAtXY, Avg}   Depth.h:9-59
+ *   EquirectangularMap::{Load, LoadPfm, ValueAtCoord, ValueAtXY, Avg,
+ *                        DispDepthConversion, Save8bit}                Depth.h:9-59
  *   PerspectiveMap::{Load, SetWindow, Value, ValueAtXY, ToSphericalCoord, SphericalTo2D,
  *                    Contain, Azimuth/ZenithMin/Max, Depth2DepthTransform} and the cached
  *                    window members middle/hedge/vedge/corner0-3    Depth.h:61-158
@@ -15,6 +16,7 @@
  *   SolveDepthAll                                                      Depth.h:306-307
  *   SolveDepthBySmoothing                                              Depth.h:309
  *   ErrorData / ErrorEmap                                              Depth.h:313-316
+ *   ErrorCompare                                                       Depth.h:318-319
  *   ErrorLaplacian                                                     Depth.h:321-323
  *   SphericalToWorld / WorldToSpherical                                Depth.h:326-329
  *   Save16BitPNG                                                       Depth.cpp:27-32
@@ -30,8 +32,9 @@
  * and glibc calls (csrc/pf_geom.hpp), bit-identical to it; the per-pixel path runs on the GPU.
  *
  * Not provided: SolveDisparityToDepth (declared, never defined: Depth.h:293) and
- * SolveDepthToDepth2 (never called), ErrorCompare, the triangulation/subdivision members
- * (vertices, faces, subd_*: never used on the path).
+ * SolveDepthToDepth2 (never called), MedianScaling and EquirectangularMap::CopyInvalidPixels
+ * (nothing in the reference calls them), the triangulation/subdivision members (vertices, faces,
+ * subd_*: never used on the path).
  */
 #pragma once
 
@@ -155,6 +158,9 @@ typedef Imath::Vec4<float> Vec4f;
 extern Vec2f g_zenith_range; /* Depth.cpp:22 Vec2f(D2R(26), D2R(154)) */
 
 bool Save16BitPNG(unsigned short* data, int width, int height, const char* filename);
+/* A one-channel 8-bit PNG with the bytes of stbi_write_png(filename, width, height, 1, data,
+ * width), the call that ErrorCompare and Save8bit make (Depth.cpp:2596, :632). */
+bool Save8BitPNG(const unsigned char* data, int width, int height, const char* filename);
 
 namespace DepthNamespace {
 
@@ -174,6 +180,14 @@ public:
     float ValueAtCoord(float azimuth, float zenith);
     float ValueAtXY(int x, int y);
     double Avg();
+    /* disparity <-> depth (Depth.cpp:587-610) on the GPU (pf_disp_depth_convert): channel 0 becomes
+     * 1 / v where (double)fabsf(v) >= 1e-5 -- once per channel of the map, as the reference's loop
+     * over the channels converts channel 0 each time */
+    void DispDepthConversion();
+    /* channel 0, clamped to 0..1, as (unsigned char)(v * 255.0f) in a one-channel 8-bit PNG with
+     * stbi_write_png's bytes (Depth.cpp:612-635); NaN becomes 0.  Returns false when the file
+     * cannot be written (the reference returns true regardless). */
+    bool Save8bit(std::string& filename);
 };
 
 class PerspectiveMap {
@@ -246,6 +260,35 @@ bool ErrorEmap(EquirectangularMap& emap_gt, EquirectangularMap& emap_given, floa
                float& mae, float& mre, float& mse_log, float& delta1, float& delta2,
                float& delta3, int align_way, bool cap_depth,
                Vec2f* least_square_shift = nullptr, float* median_shift_factor = nullptr);
+
+/* Two-file comparison (Depth.cpp:2460-2634), on the GPU (pf_error_compare, whose comment in
+ * panofuse.h has the chain step by step).  The gt is loaded with Load(fn), the baseline with
+ * Load(fn, true) (a mono360 PFM is flipped and normalised to 0..1); a load failure prints the
+ * reference's "cannot load emap_gt? ..." / "cannot load emap_baseline? ..." and returns false
+ * before any GPU call.  DispDepthCompare == false: ErrorEmap(gt, baseline, align_way, cap_depth),
+ * and with a file name the baseline as an 8-bit PNG.  DispDepthCompare == true: the baseline is a
+ * disparity; it is least-squares-aligned to the gt's disparity, converted to depth, clipped to
+ * [0, 10], scored with ErrorEmap(align_way, cap_depth), and its non-black pixels, normalised to
+ * their min..max (printed as "DispDepthCompare emap_baseline minmax:..."), are written as an
+ * 8-bit PNG, followed by "[ErrorCompare] <ret> saved shifted emap:...".
+ * Where the reference's behaviour is undefined, this is the rule: a null shifted_filename in
+ * disparity mode writes no file (the reference passes it to stbi_write_png); a product above 255
+ * saturates to 255; NaN becomes 0 in the 8-bit plane; every comparison otherwise follows IEEE as
+ * the source reads, so a NaN is not black, does not move the min / max and stays NaN in the depth
+ * plane. */
+bool ErrorCompare(std::string& gt_filename, std::string& baseline_filename, bool DispDepthCompare,
+                  float& mse, float& mae, float& mre, float& mselog, float& delta1, float& delta2,
+                  float& delta3, int align_way, bool cap_depth,
+                  const char* shifted_filename = nullptr);
+/* The same for maps already in memory (neither is modified).  fit: the disparity fit {s, o};
+ * minmax: {vmin, vmax} of the non-black pixels; shifted: the 8-bit plane [height][width] of the
+ * baseline; n_nonblack: the number of pixels that were normalised (nothing is written to a file,
+ * nothing is printed). */
+bool ErrorCompare(EquirectangularMap& emap_gt, EquirectangularMap& emap_baseline,
+                  bool DispDepthCompare, float& mse, float& mae, float& mre, float& mselog,
+                  float& delta1, float& delta2, float& delta3, int align_way, bool cap_depth,
+                  Vec2f* fit = nullptr, Vec2f* minmax = nullptr,
+                  std::vector<unsigned char>* shifted = nullptr, int* n_nonblack = nullptr);
 
 /* Edge-fidelity errors between a ground-truth map and a given map, both loaded with
  * EquirectangularMap::Load (Depth.cpp:2636-2953): mse and mae of the 3x3 Laplacian, mae of

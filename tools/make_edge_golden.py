@@ -64,7 +64,10 @@ def make_pair(rng, gshape, vshape):
     return g16, v16
 
 
-def build_harness(ref, d):
+def build_harness(ref, d, harness=None):
+    """Compile the reference's Depth.cpp with a harness (tools/edge_ref_harness.cpp unless another
+    path is given) into d; returns the executable."""
+    harness = harness or os.path.join(ROOT, "tools", "edge_ref_harness.cpp")
     shim = os.path.join(d, "shim")
     os.makedirs(os.path.join(shim, "opencv2"))
     open(os.path.join(shim, "windows.h"), "w").write(WINDOWS_H)
@@ -75,15 +78,15 @@ def build_harness(ref, d):
                     "-DEIGEN_INCLUDE_DIR=" + os.path.join(ref, "eigen"), "-DCXSPARSE=OFF",
                     "-DLAPACK=OFF", "-DSUITESPARSE=OFF", "-DMINIGLOG=ON", "-DGFLAGS=OFF",
                     "-DBUILD_TESTING=OFF"], check=True, stdout=subprocess.DEVNULL)
-    exe = os.path.join(d, "edge_ref")
+    exe = os.path.join(d, os.path.splitext(os.path.basename(harness))[0])
     inc = [shim, ref, os.path.join(ref, "ilmbase22", "include"),
            os.path.join(ref, "ceres-solver", "include"), os.path.join(ceres, "config"),
            os.path.join(ref, "ceres-solver", "internal", "ceres", "miniglog"),
            os.path.join(ref, "eigen")]
     subprocess.run(["g++", "-std=c++14", "-O2", "-fopenmp", "-w", "-DERROR=ERROR_",
                     "-ffunction-sections", "-fdata-sections"] + ["-I" + i for i in inc] +
-                   [os.path.join(ROOT, "tools", "edge_ref_harness.cpp"),
-                    os.path.join(ref, "Depth.cpp"), "-Wl,--gc-sections", "-o", exe], check=True)
+                   [harness, os.path.join(ref, "Depth.cpp"), "-Wl,--gc-sections", "-o", exe],
+                   check=True)
     return exe
 
 

@@ -91,6 +91,10 @@ struct pf_ctx {
     std::vector<WarpPatch> wpatch_grid_h;  // the layout's plain 32x32 patch grid
     // workspace
     DevBuf buf[3], lnorm, coeffs, lsum_ws, metrics_ws, reg_sums, reg_active;
+    // pf_error_compare: the fit's and the final call's pf_metrics, the min / max cells, the gt
+    // disparity plane and (when the caller passes none) the depth plane; apart from metrics_ws,
+    // which the two inner pf_error_metrics calls size for themselves
+    DevBuf cmp_ws;
     // SolveDepthBySmoothing (pf_smooth.hip): boxes, grid tables, per-pixel source and mask
     DevBuf sm_box, sm_cols, sm_rows, sm_src, sm_mask;
     // its compacted pixel list (k_smooth_iter_list), cached for one (boxes, size, band) key
@@ -358,7 +362,7 @@ void pf_destroy(pf_ctx* c)
                      &c->wmap, &c->wfxy, &c->wpatch, &c->wunits, &c->metrics_ws, &c->reg_sums,
                      &c->reg_active, &c->sm_box, &c->sm_cols, &c->sm_rows, &c->sm_src,
                      &c->sm_mask, &c->seed_ecol, &c->seed_erow, &c->jres_x, &c->jres_sync,
-                     &c->sm_sync, &c->sm_list, &c->sm_off};
+                     &c->sm_sync, &c->sm_list, &c->sm_off, &c->cmp_ws};
     for (DevBuf* b : all) release(*b);
     for (int l = 0; l < 4; l++) {
         release(c->lc.box[l]);
@@ -2584,6 +2588,91 @@ int pf_error_laplacian(pf_ctx* c, const float* gt, int gw, int gh, int gc, const
                  batch * ((double)gw * gh * 4.0 + (double)w * h * ((given16 ? 2.0 : 4.0) + 8.0 * planes)),
                  2);
     launch_edge(c->stream, j, c->metrics_ws.p, out);
+    HIPCHK(c, hipGetLastError());
+    return PF_OK;
+}
+
+int pf_error_compare(pf_ctx* c, const float* gt, int gw, int gh, int gc, const float* given, int w,
+                     int h, int given_c, int batch, float zr0, float zr1, int disp_depth,
+                     int align_way, int cap_depth, pf_compare* out, float* depth, uint8_t* shifted)
+{
+    if (!c) return PF_EINVAL;
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, PF_EHIP, "hipSetDevice failed");
+    if (!gt || !given || !out) return fail(c, PF_EINVAL, "pf_error_compare: need gt, given and out");
+    if (gw < 1 || gh < 1 || gc < 1 || w < 1 || h < 1 || given_c < 1)
+        return fail(c, PF_EINVAL, "pf_error_compare: bad shape gt %dx%dx%d given %dx%dx%d", gw, gh,
+                    gc, w, h, given_c);
+    if (batch <= 0 || batch > 65535) return fail(c, PF_EINVAL, "batch %d out of range", batch);
+    if (align_way < 0 || align_way > 2) return fail(c, PF_EINVAL, "align_way %d", align_way);
+    // a block indexes up to 1024 units past the last pixel in an int
+    const long long lim = (1ll << 31) - 4096;
+    if ((long long)w * h >= lim || (long long)gw * gh * gc >= lim || (long long)w * h * given_c >= lim)
+        return fail(c, PF_EINVAL, "pf_error_compare: map too large");
+    const int n = w * h, ng = gw * gh;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_fit = 0, o_m = o_fit + up(sizeof(pf_metrics) * batch),
+                 o_cells = o_m + up(sizeof(pf_metrics) * batch),
+                 o_gtd = o_cells + up(sizeof(uint32_t) * CMP_CELLS * batch),
+                 o_depth = o_gtd + (disp_depth ? up(sizeof(float) * (size_t)ng * batch) : 0),
+                 total = o_depth + (disp_depth && !depth ? up(sizeof(float) * (size_t)n * batch) : 0);
+    int rc;
+    if ((rc = ensure(c, c->cmp_ws, total))) return rc;
+    char* ws = (char*)c->cmp_ws.p;
+    pf_metrics* fit = (pf_metrics*)(ws + o_fit);
+    pf_metrics* m = (pf_metrics*)(ws + o_m);
+    uint32_t* cells = (uint32_t*)(ws + o_cells);
+    if (!disp_depth) {
+        // Depth.cpp:2606-2630: ErrorEmap, then the given map itself as 8 bits
+        if ((rc = pf_error_metrics(c, gt, gw, gh, gc, given, nullptr, w, h, given_c, batch, zr0, zr1,
+                                   align_way, cap_depth, m)))
+            return rc;
+        StageTimer t(c, PF_STAGE_METRICS,
+                     (double)batch * n * (4.0 + (shifted ? 1.0 : 0.0) + (depth ? 4.0 : 0.0)), 2);
+        if (shifted || depth) launch_cmp_quant(c->stream, given, given_c, n, batch, nullptr, shifted, depth);
+        launch_cmp_final(c->stream, m, nullptr, nullptr, batch, out);
+        HIPCHK(c, hipGetLastError());
+        return PF_OK;
+    }
+    float* gt_disp = (float*)(ws + o_gtd);
+    float* dplane = depth ? depth : (float*)(ws + o_depth);
+    {   // Depth.cpp:2481-2487: the gt's disparity, one channel
+        StageTimer t(c, PF_STAGE_METRICS, (double)batch * ng * 8.0, 2);
+        launch_cmp_conv(c->stream, gt, gc, gt_disp, 1, ng, gc, batch);
+        launch_cmp_init(c->stream, cells, batch);
+        HIPCHK(c, hipGetLastError());
+    }
+    // Depth.cpp:2492: the least-squares fit of the given disparity to the gt's, no cap
+    if ((rc = pf_error_metrics(c, gt_disp, gw, gh, 1, given, nullptr, w, h, given_c, batch, zr0, zr1,
+                               2, 0, fit)))
+        return rc;
+    {   // Depth.cpp:2495-2527: affine, to depth, clip; and the min / max of :2537-2551
+        StageTimer t(c, PF_STAGE_METRICS, (double)batch * n * (4.0 * given_c + 4.0), 1);
+        launch_cmp_fused(c->stream, given, given_c, n, batch, fit, dplane, cells);
+        HIPCHK(c, hipGetLastError());
+    }
+    // Depth.cpp:2530: the metrics proper, depth against depth
+    if ((rc = pf_error_metrics(c, gt, gw, gh, gc, dplane, nullptr, w, h, 1, batch, zr0, zr1,
+                               align_way, cap_depth, m)))
+        return rc;
+    StageTimer t(c, PF_STAGE_METRICS, shifted ? (double)batch * n * 5.0 : 0.0, shifted ? 2 : 1);
+    if (shifted) launch_cmp_quant(c->stream, dplane, 1, n, batch, cells, shifted, nullptr);
+    launch_cmp_final(c->stream, m, fit, cells, batch, out);
+    HIPCHK(c, hipGetLastError());
+    return PF_OK;
+}
+
+int pf_disp_depth_convert(pf_ctx* c, float* data, long long npix, int channels)
+{
+    if (!c) return PF_EINVAL;
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, PF_EHIP, "hipSetDevice failed");
+    if (!data || npix < 0 || channels < 1)
+        return fail(c, PF_EINVAL, "pf_disp_depth_convert: bad arguments");
+    const long long chunk = 1ll << 30;  // pixels per launch (a multiple of 4: the alignment holds)
+    for (long long p0 = 0; p0 < npix; p0 += chunk) {
+        float* p = data + p0 * channels;
+        launch_cmp_conv(c->stream, p, channels, p, channels, (int)std::min(chunk, npix - p0),
+                        channels, 1);
+    }
     HIPCHK(c, hipGetLastError());
     return PF_OK;
 }

@@ -188,6 +188,16 @@ bool Save16BitPNG(unsigned short* data, int width, int height, const char* filen
     return true;
 }
 
+bool Save8BitPNG(const unsigned char* data, int width, int height, const char* filename)
+{
+    std::string err;
+    if (!pfio::save_png8_stb(filename, data, width, height, 1, err)) {
+        std::cout << "[Save8BitPNG] " << err << std::endl;
+        return false;
+    }
+    return true;
+}
+
 namespace DepthNamespace {
 
 // ---- EquirectangularMap (Depth.cpp:277-575) ----
@@ -281,6 +291,34 @@ double EquirectangularMap::Avg()  // Depth.cpp:563-583
     if (count == 0) return 0;
     avg /= (float)count;
     return avg;
+}
+
+void EquirectangularMap::DispDepthConversion()  // Depth.cpp:587-610
+{
+    pf_ctx* c = facade_ctx();
+    if (!c || !data) return;
+    const size_t n = (size_t)width * height * channels;
+    DevMem d(n * sizeof(float));
+    if (!upload(d, data, n)) return;
+    if (!pf_ok(c, pf_disp_depth_convert(c, d.as<float>(), (long long)width * height, channels),
+               "pf_disp_depth_convert") ||
+        !pf_ok(c, pf_synchronize(c), "pf_synchronize"))
+        return;
+    hip_ok(hipMemcpy(data, d.p, n * sizeof(float), hipMemcpyDeviceToHost), "download");
+}
+
+bool EquirectangularMap::Save8bit(std::string& filename)  // Depth.cpp:612-635
+{
+    if (!data) return false;
+    std::vector<uint8_t> d((size_t)width * height);
+    for (size_t i = 0; i < d.size(); ++i) {
+        float val = data[i * channels];
+        if (val < 0) val = 0;
+        if (val > 1) val = 1;
+        const float p = val * 255.0f;
+        d[i] = p != p ? 0 : (uint8_t)p;  // NaN: 0 (undefined in the reference)
+    }
+    return Save8BitPNG(d.data(), width, height, filename.c_str());
 }
 
 // ---- PerspectiveMap (Depth.cpp:45-274) ----
@@ -568,6 +606,84 @@ bool ErrorEmap(EquirectangularMap& gt, EquirectangularMap& given, float& mse, fl
                      align_way, cap_depth, m))
         return false;
     fill(m, mse, mae, mre, mselog, d1, d2, d3, ls, shift);
+    return true;
+}
+
+// ---- ErrorCompare (Depth.cpp:2460-2634) ----
+namespace {
+bool run_compare(EquirectangularMap& gt, EquirectangularMap& given, bool disp, int align_way,
+                 bool cap_depth, pf_compare& r, std::vector<unsigned char>* shifted)
+{
+    pf_ctx* c = facade_ctx();
+    if (!c || !gt.data || !given.data) return false;
+    const size_t ng = (size_t)gt.width * gt.height * gt.channels;
+    const size_t npx = (size_t)given.width * given.height, nv = npx * given.channels;
+    DevMem dg(ng * sizeof(float)), dv(nv * sizeof(float)), dr(sizeof(pf_compare)),
+        ds(shifted ? npx : 0);
+    if (!upload(dg, gt.data, ng) || !upload(dv, given.data, nv) || !dr.ok || !ds.ok) return false;
+    if (!pf_ok(c, pf_error_compare(c, dg.as<float>(), gt.width, gt.height, gt.channels,
+                                   dv.as<float>(), given.width, given.height, given.channels, 1,
+                                   g_zenith_range[0], g_zenith_range[1], disp ? 1 : 0, align_way,
+                                   cap_depth ? 1 : 0, dr.as<pf_compare>(), nullptr,
+                                   shifted ? ds.as<uint8_t>() : nullptr),
+               "pf_error_compare"))
+        return false;
+    if (!hip_ok(hipMemcpy(&r, dr.p, sizeof(r), hipMemcpyDeviceToHost), "compare download"))
+        return false;
+    if (shifted) {
+        shifted->resize(npx);
+        if (!hip_ok(hipMemcpy(shifted->data(), ds.p, npx, hipMemcpyDeviceToHost), "shifted download"))
+            return false;
+    }
+    return true;
+}
+}  // namespace
+
+bool ErrorCompare(EquirectangularMap& emap_gt, EquirectangularMap& emap_baseline,
+                  bool DispDepthCompare, float& mse, float& mae, float& mre, float& mselog,
+                  float& delta1, float& delta2, float& delta3, int align_way, bool cap_depth,
+                  Vec2f* fit, Vec2f* minmax, std::vector<unsigned char>* shifted, int* n_nonblack)
+{
+    pf_compare r;
+    if (!run_compare(emap_gt, emap_baseline, DispDepthCompare, align_way, cap_depth, r, shifted))
+        return false;
+    fill(r.m, mse, mae, mre, mselog, delta1, delta2, delta3, nullptr, nullptr);
+    if (fit) *fit = Vec2f(r.fit_s, r.fit_o);
+    if (minmax) *minmax = Vec2f(r.vmin, r.vmax);
+    if (n_nonblack) *n_nonblack = r.n_nonblack;
+    return true;
+}
+
+bool ErrorCompare(std::string& gt_filename, std::string& baseline_filename, bool DispDepthCompare,
+                  float& mse, float& mae, float& mre, float& mselog, float& delta1, float& delta2,
+                  float& delta3, int align_way, bool cap_depth, const char* shifted_filename)
+{
+    EquirectangularMap emap_gt;
+    if (!emap_gt.Load(gt_filename)) {
+        std::cout << "cannot load emap_gt? " << gt_filename << std::endl;
+        return false;
+    }
+    EquirectangularMap emap_baseline;
+    if (!emap_baseline.Load(baseline_filename, true /*mono360*/)) {
+        std::cout << "cannot load emap_baseline? " << baseline_filename << std::endl;
+        return false;
+    }
+    Vec2f minmax;
+    std::vector<unsigned char> shifted;
+    if (!ErrorCompare(emap_gt, emap_baseline, DispDepthCompare, mse, mae, mre, mselog, delta1,
+                      delta2, delta3, align_way, cap_depth, nullptr, &minmax,
+                      shifted_filename ? &shifted : nullptr))
+        return false;
+    if (DispDepthCompare)  // Depth.cpp:2552
+        std::cout << "DispDepthCompare emap_baseline minmax:(" << minmax[0] << " " << minmax[1]
+                  << ")" << std::endl;
+    if (shifted_filename) {
+        // stbi_write_png's return value: 1 on success, 0 on failure
+        const int ret = Save8BitPNG(shifted.data(), emap_baseline.width, emap_baseline.height,
+                                    shifted_filename) ? 1 : 0;
+        std::cout << "[ErrorCompare] " << ret << " saved shifted emap:" << shifted_filename
+                  << std::endl;  // Depth.cpp:2599, :2628
+    }
     return true;
 }
 

@@ -382,4 +382,198 @@ bool save_png8(const std::string& fn, const uint8_t* data, int w, int h, int c, 
     return write_png(fn, data, w, h, c, 8, err);
 }
 
+// ---- the byte stream of stbi_write_png (stb_image_write v1.15, its defaults) ----
+// The reference writes its 8-bit pictures with stbi_write_png (Depth.cpp:2596, :2626, :632), whose
+// file is not what zlib makes of the same pixels: per row it takes the PNG filter (none, sub, up,
+// average, Paeth; the row above row 0 reads as zeros) with the smallest sum of |signed byte|, the
+// lowest type on a tie -- where the reference's build counts the byte 0x80 as -128, not 128: its
+// Main.cpp:13-20 includes the writer after ILMBase.h's `using namespace Imath`, so the writer's
+// abs((signed char)x) binds to Imath's abs<T>, which returns a signed char (a plain build of the
+// writer picks other filters on rows where that byte occurs) -- and it deflates with its own matcher into one fixed-Huffman block behind
+// the header bytes 0x78 0x5e.  The matcher, restated: positions are hashed by their next three
+// bytes into 16384 buckets of at most 16 entries (a full bucket drops its older half before the
+// next entry goes in); at position i the longest match (3..258 bytes, window 32767) among the
+// bucket's entries wins, the most recent on a tie; position i then joins its bucket; the match
+// is dropped for a literal when some entry of position i + 1's bucket matches longer there;
+// positions inside an emitted match are never entered; the last three bytes are literals.
+namespace {
+
+struct BitSink {
+    std::vector<uint8_t> out;
+    uint32_t acc = 0;
+    int nbits = 0;
+    void put(uint32_t v, int n)  // n bits of v, least significant first
+    {
+        acc |= v << nbits;
+        nbits += n;
+        while (nbits >= 8) {
+            out.push_back((uint8_t)acc);
+            acc >>= 8;
+            nbits -= 8;
+        }
+    }
+    void code(uint32_t c, int n)  // a Huffman code: most significant bit first
+    {
+        uint32_t r = 0;
+        for (int k = 0; k < n; ++k) r |= ((c >> k) & 1u) << (n - 1 - k);
+        put(r, n);
+    }
+    void symbol(int sym)  // the fixed literal/length code of RFC 1951, 3.2.6
+    {
+        if (sym <= 143) code(0x30 + sym, 8);
+        else if (sym <= 255) code(0x190 + sym - 144, 9);
+        else if (sym <= 279) code(sym - 256, 7);
+        else code(0xc0 + sym - 280, 8);
+    }
+};
+
+uint32_t hash3(const uint8_t* p)
+{
+    uint32_t h = p[0] + (p[1] << 8) + (p[2] << 16);
+    h ^= h << 3;
+    h += h >> 5;
+    h ^= h << 4;
+    h += h >> 17;
+    h ^= h << 25;
+    h += h >> 6;
+    return h & 16383u;
+}
+
+int match_len(const uint8_t* a, const uint8_t* b, int limit)
+{
+    int n = 0;
+    while (n < limit && n < 258 && a[n] == b[n]) ++n;
+    return n;
+}
+
+std::vector<uint8_t> stb_deflate(const std::vector<uint8_t>& in)
+{
+    // RFC 1951, 3.2.5: base length / distance of each code and its extra bits
+    static const int len_base[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43,
+                                     51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
+    static const int len_extra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4,
+                                      4, 4, 4, 5, 5, 5, 5, 0};
+    static const int dist_base[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257,
+                                      385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193,
+                                      12289, 16385, 24577};
+    static const int dist_extra[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9,
+                                       9, 10, 10, 11, 11, 12, 12, 13, 13};
+    constexpr int kKeep = 8;  // a bucket of 2 * kKeep entries drops its older half
+    const int n = (int)in.size();
+    const uint8_t* d = in.data();
+    BitSink bs;
+    bs.out.push_back(0x78);
+    bs.out.push_back(0x5e);
+    bs.put(1, 1);  // final block
+    bs.put(1, 2);  // fixed Huffman codes
+    std::vector<std::vector<int>> bucket(16384);
+    int i = 0;
+    while (i < n - 3) {
+        std::vector<int>& b = bucket[hash3(d + i)];
+        int best = 3, at = -1;
+        for (int pos : b)
+            if (pos > i - 32768) {
+                const int m = match_len(d + pos, d + i, n - i);
+                if (m >= best) {
+                    best = m;
+                    at = pos;
+                }
+            }
+        if ((int)b.size() == 2 * kKeep) b.erase(b.begin(), b.begin() + kKeep);
+        b.push_back(i);
+        if (at >= 0)
+            for (int pos : bucket[hash3(d + i + 1)])
+                if (pos > i - 32767 && match_len(d + pos, d + i + 1, n - i - 1) > best) {
+                    at = -1;
+                    break;
+                }
+        if (at < 0) {
+            bs.symbol(d[i]);
+            ++i;
+            continue;
+        }
+        int k = 0;
+        while (k < 28 && best >= len_base[k + 1]) ++k;
+        bs.symbol(257 + k);
+        if (len_extra[k]) bs.put((uint32_t)(best - len_base[k]), len_extra[k]);
+        const int dist = i - at;
+        k = 0;
+        while (k < 29 && dist >= dist_base[k + 1]) ++k;
+        bs.code((uint32_t)k, 5);
+        if (dist_extra[k]) bs.put((uint32_t)(dist - dist_base[k]), dist_extra[k]);
+        i += best;
+    }
+    for (; i < n; ++i) bs.symbol(d[i]);
+    bs.symbol(256);
+    if (bs.nbits) bs.put(0, 8 - bs.nbits);
+    const uLong ad = adler32(adler32(0L, Z_NULL, 0), d, (uInt)n);
+    for (int sh = 24; sh >= 0; sh -= 8) bs.out.push_back((uint8_t)(ad >> sh));
+    return bs.out;
+}
+
+// One row through PNG filter `type` (the row above row 0 and the pixel left of pixel 0 are zero).
+void filter_row(const uint8_t* row, const uint8_t* up, int bytes, int bpp, int type, uint8_t* out)
+{
+    for (int i = 0; i < bytes; ++i) {
+        const int a = i >= bpp ? row[i - bpp] : 0, b = up ? up[i] : 0,
+                  c = (up && i >= bpp) ? up[i - bpp] : 0;
+        const int pred = type == 0 ? 0 : type == 1 ? a : type == 2 ? b : type == 3 ? (a + b) >> 1
+                                                                                  : paeth(a, b, c);
+        out[i] = (uint8_t)(row[i] - pred);
+    }
+}
+
+}  // namespace
+
+bool save_png8_stb(const std::string& fn, const uint8_t* data, int w, int h, int c,
+                   std::string& err)
+{
+    if (c < 1 || c > 4 || w < 1 || h < 1) return err = "save_png8_stb: bad shape", false;
+    const int bytes = w * c;
+    std::vector<uint8_t> raw((size_t)(bytes + 1) * h), line(bytes);
+    for (int y = 0; y < h; ++y) {
+        const uint8_t* row = data + (size_t)bytes * y;
+        const uint8_t* up = y ? row - bytes : nullptr;
+        int best_type = 0, best_sum = 0x7fffffff;
+        for (int type = 0; type < 5; ++type) {
+            filter_row(row, up, bytes, c, type, line.data());
+            int sum = 0;
+            // (signed char)abs: 0x80 stays -128 (see above)
+            for (int i = 0; i < bytes; ++i)
+                sum += line[i] == 0x80 ? -128 : std::abs((int)(int8_t)line[i]);
+            if (sum < best_sum) {
+                best_sum = sum;
+                best_type = type;
+            }
+        }
+        uint8_t* dst = &raw[(size_t)(bytes + 1) * y];
+        dst[0] = (uint8_t)best_type;
+        filter_row(row, up, bytes, c, best_type, dst + 1);
+    }
+    const std::vector<uint8_t> z = stb_deflate(raw);
+    std::vector<uint8_t> f(kSig, kSig + 8);
+    auto be32 = [&](uint32_t v) {
+        for (int sh = 24; sh >= 0; sh -= 8) f.push_back((uint8_t)(v >> sh));
+    };
+    auto chunk = [&](const char* type, const uint8_t* d, size_t len) {
+        be32((uint32_t)len);
+        const size_t at = f.size();
+        f.insert(f.end(), type, type + 4);
+        if (len) f.insert(f.end(), d, d + len);
+        be32((uint32_t)crc32(0L, f.data() + at, (uInt)(len + 4)));
+    };
+    const uint8_t ctype = c == 1 ? 0 : c == 2 ? 4 : c == 3 ? 2 : 6;
+    const uint8_t ihdr[13] = {(uint8_t)(w >> 24), (uint8_t)(w >> 16), (uint8_t)(w >> 8), (uint8_t)w,
+                              (uint8_t)(h >> 24), (uint8_t)(h >> 16), (uint8_t)(h >> 8), (uint8_t)h,
+                              8, ctype, 0, 0, 0};
+    chunk("IHDR", ihdr, 13);
+    chunk("IDAT", z.data(), z.size());
+    chunk("IEND", nullptr, 0);
+    FILE* fp = std::fopen(fn.c_str(), "wb");
+    if (!fp) return err = "cannot open " + fn + " for writing", false;
+    const bool ok = std::fwrite(f.data(), 1, f.size(), fp) == f.size();
+    if (std::fclose(fp) != 0 || !ok) return err = "write failed: " + fn, false;
+    return true;
+}
+
 }  // namespace pfio

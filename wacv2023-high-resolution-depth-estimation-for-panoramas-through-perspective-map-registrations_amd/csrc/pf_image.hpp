@@ -38,6 +38,12 @@ bool save_png16(const std::string& fn, const uint16_t* data, int w, int h, std::
 bool decode_jpeg(const std::vector<uint8_t>& f, Image& out, std::string& err);
 bool save_png8(const std::string& fn, const uint8_t* data, int w, int h, int c,
                std::string& err);
+// The same pixels as the file stbi_write_png(fn, w, h, c, data, w * c) writes, byte for byte
+// (stb_image_write v1.15 defaults as the reference's program builds it: its row-filter choice,
+// with the byte 0x80 costing -128, and its own fixed-Huffman deflate); what ErrorCompare and
+// Save8bit save (Depth.cpp:2596, :632).
+bool save_png8_stb(const std::string& fn, const uint8_t* data, int w, int h, int c,
+                   std::string& err);
 // JPEG writer (pf_jpeg.cpp): the byte stream of stbi_write_jpg (c = 1..4 channels, rows
 // top-first; flip = stbi_flip_vertically_on_write), as the reference's tile export calls it
 // (Main.cpp:319-320: flipped, quality = width*3, i.e. 100: every quantiser 1, 4:4:4).

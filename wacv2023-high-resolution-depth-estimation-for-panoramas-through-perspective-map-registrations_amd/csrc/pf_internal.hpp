@@ -459,4 +459,24 @@ bool edge_staged(const EdgeJob& j);  // gt of the given map's size: both tiles s
 size_t edge_workspace_bytes(const EdgeJob& j);
 void launch_edge(hipStream_t s, const EdgeJob& j, void* ws, pf_edge_metrics* out);
 
+// Two-map comparison (pf_compare.hip): the per-pixel steps of ErrorCompare, Depth.cpp:2460-2634,
+// around the two ErrorEmap calls.  Every plane is [batch][n] with n < 2^31 pixels per panorama.
+// Per panorama the cells hold {min bits, max bits, count, 0} of the non-black depth values.
+constexpr int CMP_CELLS = 4;
+// DispDepthConversion (Depth.cpp:587-610) of channel 0 of in [batch][n][in_c], `times` times
+// over, to out [batch][n][out_c] (in == out with in_c == out_c converts in place).
+void launch_cmp_conv(hipStream_t s, const float* in, int in_c, float* out, int out_c, int n,
+                     int times, int batch);
+void launch_cmp_init(hipStream_t s, uint32_t* cells, int batch);
+// depth[b][i] = clip(conv(given[b][i][0] * s + o, given_c times), 0, 10) with {s, o} =
+// fit[b].ls_s, fit[b].ls_o read on the device; min / max / count of the non-black values to cells.
+void launch_cmp_fused(hipStream_t s, const float* given, int given_c, int n, int batch,
+                      const pf_metrics* fit, float* depth, uint32_t* cells);
+// shifted[b][i] = u8 of channel 0 of src [batch][n][src_c]; with cells the non-black values are
+// normalised by the panorama's min / max first; copy (optional): channel 0 as read.
+void launch_cmp_quant(hipStream_t s, const float* src, int src_c, int n, int batch,
+                      const uint32_t* cells, uint8_t* shifted, float* copy);
+void launch_cmp_final(hipStream_t s, const pf_metrics* m, const pf_metrics* fit,
+                      const uint32_t* cells, int batch, pf_compare* out);
+
 }  // namespace pf

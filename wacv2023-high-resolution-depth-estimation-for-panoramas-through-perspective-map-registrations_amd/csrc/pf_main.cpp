@@ -4,6 +4,13 @@
 //                 [--metrics-order tree|sequential] [--edge-metrics]
 //   panofuse_main export <rgb_dir> <tile_dir> [--device D]
 //   panofuse_main lap <gt_file> <given_file> [--device D]
+//   panofuse_main cmp <gt_file> <given_file> [--disp] [--align 0|1|2] [--no-cap] [--save FILE]
+//                 [--device D] [--metrics-order tree|sequential]
+// "cmp" is the reference's ErrorCompare (Depth.cpp:2460-2634) on two image files, the given one
+// loaded the mono360 way: depth against depth by default (align 1, cap on), with --disp the given
+// map is a disparity that is least-squares-aligned to the gt's first.  It prints
+// "CMP mse mae mre mselog delta1 delta2 delta3" at %.9g, with --disp also
+// "FIT s o vmin vmax n_nonblack", and with --save writes the 8-bit PNG the reference saves.
 // "lap" is the reference's ErrorLaplacian (Depth.cpp:2636-2953) on two image files: its
 // "[ErrorLap] ..." line, then one line with the three sample counts.
 // "export" is the tile render of mode 0 (Main.cpp:399-430, SaveCubeMap :242-326) on the GPU:
@@ -24,6 +31,7 @@
 #include <cstdlib>
 #include <iostream>
 #include <string>
+#include <vector>
 
 int main(int argc, char* argv[])
 {
@@ -33,7 +41,11 @@ int main(int argc, char* argv[])
                      " [--ext auto|jpg|png] [--width W] [--device D] [--shard R/N]"
                      " [--metrics-order tree|sequential] [--edge-metrics]\n       "
                   << argv[0] << " export <rgb_dir> <tile_dir> [--device D]\n       "
-                  << argv[0] << " lap <gt_file> <given_file> [--device D]" << std::endl;
+                  << argv[0] << " lap <gt_file> <given_file> [--device D]\n       "
+                  << argv[0]
+                  << " cmp <gt_file> <given_file> [--disp] [--align 0|1|2] [--no-cap] [--save FILE]"
+                     " [--device D] [--metrics-order tree|sequential]"
+                  << std::endl;
         return 0;
     }
     const std::string cmd(argv[1]);
@@ -76,6 +88,83 @@ int main(int argc, char* argv[])
         if (!DepthNamespace::ErrorLaplacian(gt, given, v[0], v[1], v[2], v[3], v[4], n)) return 1;
         std::cout << "[ErrorLap] n_lap:" << n[0] << " n_sobel:" << n[1] << " n_lap5:" << n[2]
                   << std::endl;
+        return 0;
+    }
+    if (cmd == "cmp") {
+        if (argc < 4) {
+            std::cout << "usage: " << argv[0]
+                      << " cmp <gt_file> <given_file> [--disp] [--align 0|1|2] [--no-cap]"
+                         " [--save FILE] [--device D] [--metrics-order tree|sequential]"
+                      << std::endl;
+            return 1;
+        }
+        bool disp = false, cap = true;
+        int align = 1, dev = 0;
+        std::string save;
+        for (int i = 4; i < argc; ++i) {
+            const std::string k(argv[i]);
+            if (k == "--disp") disp = true;
+            else if (k == "--no-cap") cap = false;
+            else if (i + 1 >= argc) {
+                std::cout << "option " << k << " needs a value" << std::endl;
+                return 2;
+            }
+            else if (k == "--align") align = std::atoi(argv[++i]);
+            else if (k == "--save") save = argv[++i];
+            else if (k == "--device") dev = std::atoi(argv[++i]);
+            else if (k == "--metrics-order") {
+                const std::string v(argv[++i]);
+                if (v != "tree" && v != "sequential") {
+                    std::cout << "bad --metrics-order " << v << " (want tree or sequential)"
+                              << std::endl;
+                    return 2;
+                }
+                setenv("PF_METRICS_ORDER", v.c_str(), 1);  // read when the facade's context is made
+            }
+            else {
+                std::cout << "unknown option " << k << std::endl;
+                return 2;
+            }
+        }
+        if (align < 0 || align > 2) {
+            std::cout << "bad --align " << align << " (want 0, 1 or 2)" << std::endl;
+            return 2;
+        }
+        // the loads come first: a file that does not load ends the command before any GPU call
+        std::string gt_fn(argv[2]), given_fn(argv[3]);
+        DepthNamespace::EquirectangularMap gt, given;
+        if (!gt.Load(gt_fn)) {
+            std::cout << "cannot load emap_gt? " << gt_fn << std::endl;
+            return 1;
+        }
+        if (!given.Load(given_fn, true /*mono360*/)) {
+            std::cout << "cannot load emap_baseline? " << given_fn << std::endl;
+            return 1;
+        }
+        if (hipSetDevice(dev) != hipSuccess) {
+            std::cout << "no HIP device " << dev << std::endl;
+            return 1;
+        }
+        float v[7];
+        Vec2f fit, minmax;
+        int n_nonblack = 0;
+        std::vector<unsigned char> shifted;
+        if (!DepthNamespace::ErrorCompare(gt, given, disp, v[0], v[1], v[2], v[3], v[4], v[5], v[6],
+                                          align, cap, &fit, &minmax, save.empty() ? nullptr : &shifted,
+                                          &n_nonblack))
+            return 1;
+        std::printf("CMP %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", v[0], v[1], v[2], v[3], v[4], v[5],
+                    v[6]);
+        if (disp)
+            std::printf("FIT %.9g %.9g %.9g %.9g %d\n", fit[0], fit[1], minmax[0], minmax[1],
+                        n_nonblack);
+        std::fflush(stdout);
+        if (!save.empty()) {
+            const bool ok = Save8BitPNG(shifted.data(), given.width, given.height, save.c_str());
+            std::cout << "[ErrorCompare] " << (ok ? 1 : 0) << " saved shifted emap:" << save
+                      << std::endl;
+            if (!ok) return 1;
+        }
         return 0;
     }
     if (cmd != "0") return 0;  // Main.cpp:889-893: other commands do nothing

@@ -33,6 +33,7 @@ EXPORTS = [
     "pf_fuse_partial_rows", "pf_fuse_coverage_rows", "pf_fuse_normalize_rows",
     "pf_fuse_tile_rows", "pf_rows_add", "pf_fuse_level", "pf_fuse_targets",
     "pf_rows_add_batch", "pf_set_jacobi_share", "pf_error_laplacian",
+    "pf_error_compare", "pf_disp_depth_convert",
 ]
 NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
           "pf_debug_smooth_fault", "pf_fuse_partial_rows", "pf_fuse_coverage_rows",
@@ -100,6 +101,9 @@ def load():
     L.pf_error_metrics.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, ip, ip, ip, fp, fp, ip, ip,
                                    vp]
     L.pf_error_laplacian.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, ip, ip, ip, vp, vp, vp, vp]
+    L.pf_error_compare.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, ip, ip, fp, fp, ip, ip, ip, vp,
+                                   vp, vp]
+    L.pf_disp_depth_convert.argtypes = [vp, vp, C.c_longlong, ip]
     L.pf_set_solver.argtypes = [vp, ip]
     L.pf_fuse_normalize.argtypes = [vp, vp, vp, ip, ip, fp, fp, ip, vp]
     L.pf_fuse_multicover.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, ip, vp,
@@ -174,6 +178,9 @@ METRIC_KEYS = ("mse", "mae", "mre", "mselog", "delta1", "delta2", "delta3", "med
 # pf_edge_metrics field order (include/panofuse.h): five doubles, three int64 counts
 EDGE_KEYS = ("lap_mse", "lap_mae", "sobelx_mae", "sobely_mae", "lap5_mae")
 EDGE_COUNTS = ("n_lap", "n_sobel", "n_lap5")
+# pf_compare (include/panofuse.h): a pf_metrics (16 words), four floats, n_nonblack, 3 reserved
+COMPARE_WORDS = 24
+COMPARE_FLOATS = ("fit_s", "fit_o", "vmin", "vmax")
 
 
 class Fuser:
@@ -355,6 +362,50 @@ class Fuser:
                 d[k] = int(o[b, 5 + i])
             res.append(d)
         return (res, *planes) if maps else res
+
+    def compare_async(self, gt, given, zr, out, disp_depth, align_way=1, cap_depth=True,
+                      depth=None, shifted=None):
+        """pf_error_compare into out (int32 [B,24] device tensor = B pf_compare), no sync.
+        depth: optional float32 [B,h,w], shifted: optional uint8 [B,h,w] device tensors."""
+        gw, gh, gc = _emap_dims(gt)
+        B, h, w = given.shape[:3]
+        gvc = given.shape[3] if given.dim() == 4 else 1
+        self._check(self.L.pf_error_compare(self.h, _ptr(gt), gw, gh, gc, _ptr(given), w, h, gvc,
+                                            B, float(zr[0]), float(zr[1]), int(bool(disp_depth)),
+                                            int(align_way), int(cap_depth), _ptr(out),
+                                            _ptr(depth), _ptr(shifted)))
+
+    def compare(self, gt, given, zr, disp_depth, align_way=1, cap_depth=True, planes=False):
+        """ErrorCompare (Depth.cpp:2460-2634) of given (float32 [B,h,w] or [B,h,w,c]: a depth
+        map, or with disp_depth a disparity map) against gt float32 [B,gh,gw] or [B,gh,gw,gc].
+        Returns a list (one per panorama) of dicts of METRIC_KEYS + n, nlog, fit_s, fit_o, vmin,
+        vmax, n_nonblack; with planes=True also the float32 depth plane and the uint8 shifted
+        plane, both [B,h,w] device tensors."""
+        import torch
+        B, h, w = given.shape[:3]
+        out = torch.zeros((B, COMPARE_WORDS), dtype=torch.int32, device=gt.device)
+        depth = torch.empty((B, h, w), dtype=torch.float32, device=gt.device) if planes else None
+        shifted = torch.empty((B, h, w), dtype=torch.uint8, device=gt.device) if planes else None
+        self.compare_async(gt, given, zr, out, disp_depth, align_way, cap_depth, depth, shifted)
+        self.synchronize()
+        o = out.cpu()
+        f = o.view(torch.float32)
+        res = []
+        for b in range(B):
+            d = {k: float(f[b, i]) for i, k in enumerate(METRIC_KEYS)}
+            d["n"], d["nlog"] = int(o[b, 12]), int(o[b, 13])
+            for i, k in enumerate(COMPARE_FLOATS):
+                d[k] = float(f[b, 16 + i])
+            d["n_nonblack"] = int(o[b, 20])
+            res.append(d)
+        return (res, depth, shifted) if planes else res
+
+    def disp_depth_convert(self, t, channels=1):
+        """DispDepthConversion (Depth.cpp:587-610) in place on a float32 device tensor: channel 0
+        of its pixels, `channels` interleaved values each (the last dimension when > 1), is
+        inverted `channels` times where (double)|v| >= 1e-5.  No sync."""
+        self._check(self.L.pf_disp_depth_convert(self.h, _ptr(t), t.numel() // channels,
+                                                 int(channels)))
 
     def probe_taps(self, out_w, zr, level):
         import torch
