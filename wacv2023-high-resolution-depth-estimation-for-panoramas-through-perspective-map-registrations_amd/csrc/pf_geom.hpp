@@ -1,6 +1,6 @@
 // pf_geom.hpp -- host fp32 geometry of the reference's projection, with Imath Vec2/Vec3<float>
 // semantics (ImathVec.h:1145-1180 Vec2 length, :1467-1486 dot/cross, :1631-1700 length/lengthTiny
-// and normalize-by-division).  Shared by the library's layout setup (pf_api.hip) and the
+// and normalize-by-division).  Shared by the library's layout setup (pf_layout.hip) and the
 // DepthNamespace facade (pf_depth.cpp) so both produce the reference's bits; compiled with
 // -ffp-contract=off (no fused multiply-adds), glibc sincosf/tanf/atan2f as the g++ build of
 // Depth.cpp calls them.
