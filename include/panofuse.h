@@ -109,6 +109,34 @@ int pf_fuse(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, const float*
 int pf_merge(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, const float* tiles,
              int batch, int out_w, float zr0, float zr1, float* coeffs, uint16_t* out);
 
+/* Disparity tiles (MiDaS / DPT: relative inverse depth in 0-1).  The reference declares
+ * SolveDisparityToDepth (Depth.h:293-294) without defining it; this is its model
+ * (FunctorDisparity2Depth, Depth.cpp:1044-1073: y = 1/(a x + b) + d, weight 1) fitted on
+ * SolveDepthToDepth's samples by the same Ceres 1.13 Levenberg-Marquardt (DENSE_SCHUR, default
+ * options, from (1,1,1)), every tile alone as in MergeDepthMaps' loop.  fp64 throughout, in a
+ * fixed summation order, so the result is reproducible bit for bit.
+ *   coeffs   (optional) [batch][ntiles][4] floats  abcd = (a, b, 1, d), the order D2DTransform reads
+ *   coeffs64 (optional) [batch][ntiles][4] doubles the unrounded solution
+ *   summary  (optional) [batch][ntiles][4] doubles {initial cost, final cost, iterations,
+ *            termination: 0 no convergence, 1 function, 2 parameter, 3 gradient tolerance,
+ *            4 minimum radius, 5 failure}
+ * apply != 0 then runs D2DTransform (Depth.cpp:214-243) on the tiles. */
+int pf_register_disparity(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, float* tiles,
+                          int batch, float zr0, float zr1, int apply, float* coeffs,
+                          double* coeffs64, double* summary);
+
+/* PerspectiveMap::D2DTransform (Depth.cpp:214-243) on device data, in place: channel 0 of npix
+ * pixels becomes clamp01(c / (a * clampX + b) + d) in fp32, NaN kept; abcd: 4 HOST floats. */
+int pf_disparity_transform(pf_ctx* ctx, float* data, long long npix, int channels,
+                           const float* abcd);
+
+/* MergeDepthMaps' compute core for disparity tiles (an extension: the reference has no such
+ * driver): pf_register_disparity, D2DTransform into a context-owned copy of the tiles, then
+ * pf_fuse on that copy without coefficients.  The caller's tiles are left untouched; coeffs
+ * (optional) receives the per-tile abcd. */
+int pf_merge_disparity(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, const float* tiles,
+                       int batch, int out_w, float zr0, float zr1, float* coeffs, uint16_t* out);
+
 /* E->P depth warp: tile pixel (X,Y) -> ToSphericalCoord(X/(W-1), Y/(H-1)) (Depth.cpp:157-166)
  * -> bilinear sample of pano [batch][ph][pw] at (az/2pi*(pw-1), zen/pi*(ph-1)).  resp
  * ([batch][ntiles], optional) applies the synthetic depth-net response. */

@@ -8,10 +8,12 @@
  *   EquirectangularMap::{Load, LoadPfm, ValueAtCoord, ValueAtXY, Avg,
  *                        DispDepthConversion, Save8bit}                Depth.h:9-59
  *   PerspectiveMap::{Load, SetWindow, Value, ValueAtXY, ToSphericalCoord, SphericalTo2D,
- *                    Contain, Azimuth/ZenithMin/Max, Depth2DepthTransform} and the cached
- *                    window members middle/hedge/vedge/corner0-3    Depth.h:61-158
+ *                    Contain, Azimuth/ZenithMin/Max, D2DTransform, Depth2DepthTransform}
+ *                    and the cached window members middle/hedge/vedge/corner0-3
+ *                                                                      Depth.h:61-158
  *   Metrics::{Save, Print}                                             Depth.h:161-250
  *   MergeDepthMaps                                                     Depth.h:286-289
+ *   SolveDisparityToDepth (declared there, defined here)               Depth.h:293-294
  *   SolveDepthToDepth                                                  Depth.h:297-298
  *   SolveDepthAll                                                      Depth.h:306-307
  *   SolveDepthBySmoothing                                              Depth.h:309
@@ -31,8 +33,10 @@
  * SphericalToWorld, WorldToSpherical) are host fp32 code with the reference's Imath semantics
  * and glibc calls (csrc/pf_geom.hpp), bit-identical to it; the per-pixel path runs on the GPU.
  *
- * Not provided: SolveDisparityToDepth (declared, never defined: Depth.h:293) and
- * SolveDepthToDepth2 (never called), MedianScaling and EquirectangularMap::CopyInvalidPixels
+ * Extension (not in the reference): MergeDisparityMaps, MergeDepthMaps for disparity tiles.
+ *
+ * Not provided: SolveDepthToDepth2 (never called), a SolveDisparityToDepth over several active
+ * maps (a joint nonlinear solve), MedianScaling and EquirectangularMap::CopyInvalidPixels
  * (nothing in the reference calls them), the triangulation/subdivision members (vertices, faces,
  * subd_*: never used on the path).
  */
@@ -220,6 +224,9 @@ public:
     float ZenithMin() { return zenith_top < zenith_down ? zenith_top : zenith_down; }
     float ZenithMax() { return zenith_top > zenith_down ? zenith_top : zenith_down; }
     float ValueAtXY(int x, int y);                    /* Depth.cpp:209-212 */
+    /* Y = c / (a X + b) + d on channel 0 (Depth.h:155, Depth.cpp:214-243: X a disparity in 0-1,
+     * clamped to [1e-4, 1 - 1e-4]; Y clamped to 0-1); runs on the GPU (pf_disparity_transform) */
+    void D2DTransform(Vec4f abcd);
     void Depth2DepthTransform(Vec4f& abcd); /* runs on the GPU (pf_depth_transform) */
 };
 
@@ -240,6 +247,26 @@ bool MergeDepthMaps(std::string& equirectangular_map_filename,
                     Vec2f& zenith_range, std::string* equirectangular_map_groundtruth = nullptr,
                     Metrics* metrics = nullptr, int* time_Reg = nullptr,
                     int* time_Laplacian = nullptr);
+
+/* EXTENSION (not in the reference): MergeDepthMaps for tiles that hold relative inverse depth
+ * in 0-1 (MiDaS / DPT).  Every tile is registered alone with SolveDisparityToDepth's model and
+ * mapped to depth by D2DTransform; everything else (fusion, files written, metrics, timers) is
+ * MergeDepthMaps'. */
+bool MergeDisparityMaps(std::string& equirectangular_map_filename,
+                        std::vector<std::string>& perspective_map_filenames,
+                        std::string& out_filename, std::vector<Vec4f>& perspective_map_FOVs,
+                        std::vector<Vec4f>& perspective_map_ranges, int out_width,
+                        Vec2f& zenith_range,
+                        std::string* equirectangular_map_groundtruth = nullptr,
+                        Metrics* metrics = nullptr, int* time_Reg = nullptr,
+                        int* time_Laplacian = nullptr);
+
+/* Depth.h:291-294: the disparity-to-depth transform y = c / (a x + b) + d (x a tile's disparity,
+ * y the baseline's depth) with c fixed at 1, as the reference's FunctorDisparity2Depth
+ * (Depth.cpp:1044-1073) has it; abcd = (a, b, 1, d) for D2DTransform.  Exactly one map may be
+ * active: more (or none) returns false with a message. */
+bool SolveDisparityToDepth(EquirectangularMap& emap, std::vector<PerspectiveMap>& pmaps,
+                           std::vector<bool>& pmaps_actives, Vec2f& zenith_range, Vec4f& abcd);
 
 bool SolveDepthToDepth(EquirectangularMap& emap, std::vector<PerspectiveMap>& pmaps,
                        std::vector<bool>& pmaps_actives, Vec2f& zenith_range, Vec4f& abcd);
@@ -318,7 +345,8 @@ Vec2f WorldToSpherical(Vec3f& p);
 
 /* The mode-0 driver (Main.cpp:331-687 CreateDepthPanoramas) over std::filesystem; tile_ext is
  * "png" (MiDaS naming, Main.cpp:570-573), "jpg" (LeReS naming, :576-578) or "auto"; the LeReS
- * layout of Main.cpp:788-843 is used.  shard / nshards: this process takes the panoramas
+ * layout of Main.cpp:788-843 is used.  With PF_TILE_MODEL=disparity in the environment
+ * (panofuse_main --tile-model disparity) the tiles are disparities: MergeDisparityMaps.  shard / nshards: this process takes the panoramas
  * shard, shard + nshards, ... of the sorted folder (one process per GPU, no communication).
  * With PF_EDGE_METRICS=1 in the environment (panofuse_main --edge-metrics) each panorama also
  * gets <raw>.edges.txt: ErrorLaplacian of the result and of the baseline against the gt.

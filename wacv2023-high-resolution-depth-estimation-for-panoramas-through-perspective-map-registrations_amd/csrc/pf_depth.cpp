@@ -456,6 +456,21 @@ void PerspectiveMap::Depth2DepthTransform(Vec4f& abcd)
     hip_ok(hipMemcpy(data, d.p, n * sizeof(float), hipMemcpyDeviceToHost), "download");
 }
 
+void PerspectiveMap::D2DTransform(Vec4f abcd)  // Depth.cpp:214-243, on the GPU
+{
+    pf_ctx* c = facade_ctx();
+    if (!c || !data) return;
+    const size_t n = (size_t)width * height * channels;
+    DevMem d(n * sizeof(float));
+    if (!upload(d, data, n)) return;
+    const float k[4] = {abcd[0], abcd[1], abcd[2], abcd[3]};
+    if (!pf_ok(c, pf_disparity_transform(c, d.as<float>(), (long long)width * height, channels, k),
+               "pf_disparity_transform") ||
+        !pf_ok(c, pf_synchronize(c), "pf_synchronize"))
+        return;
+    hip_ok(hipMemcpy(data, d.p, n * sizeof(float), hipMemcpyDeviceToHost), "download");
+}
+
 // ---- free projection functions (Depth.cpp:2955-2971) ----
 Vec3f SphericalToWorld(float azimuth, float zenith) { return vec(pfgeom::sph_to_world(azimuth, zenith)); }
 
@@ -533,6 +548,38 @@ bool SolveDepthToDepth(EquirectangularMap& emap, std::vector<PerspectiveMap>& pm
                                     dt.as<float>(), 1, zr[0], zr[1], 3, all.data(),
                                     dc.as<float>(), nullptr),
                "pf_register_joint"))
+        return false;
+    float k[4];
+    if (!hip_ok(hipMemcpy(k, dc.p, sizeof(k), hipMemcpyDeviceToHost), "download")) return false;
+    abcd = Vec4f(k[0], k[1], k[2], k[3]);
+    return true;
+}
+
+// Depth.h:293-294 (declared there, never defined): y = 1/(a x + b) + d fitted to the one active
+// map's samples (pf_register_disparity); abcd = (a, b, 1, d).
+bool SolveDisparityToDepth(EquirectangularMap& emap, std::vector<PerspectiveMap>& pmaps,
+                           std::vector<bool>& actives, Vec2f& zr, Vec4f& abcd)
+{
+    std::vector<PerspectiveMap*> pm;
+    for (size_t i = 0; i < actives.size() && i < pmaps.size(); ++i)
+        if (actives[i]) pm.push_back(&pmaps[i]);
+    if (pm.size() != 1) {
+        std::cout << "[SolveDisparityToDepth] needs exactly one active map (" << pm.size()
+                  << " given): a joint disparity solve is not provided" << std::endl;
+        return false;
+    }
+    pf_ctx* c = facade_ctx();
+    if (!c || !emap.data) return false;
+    std::vector<float> packed;
+    if (!set_layout(c, pm, packed)) return false;
+    const size_t ne = (size_t)emap.width * emap.height * emap.channels;
+    DevMem de(ne * 4), dt(packed.size() * 4), dc(4 * sizeof(float));
+    if (!upload(de, emap.data, ne) || !upload(dt, packed.data(), packed.size()) || !dc.ok)
+        return false;
+    if (!pf_ok(c, pf_register_disparity(c, de.as<float>(), emap.width, emap.height, emap.channels,
+                                        dt.as<float>(), 1, zr[0], zr[1], 0, dc.as<float>(),
+                                        nullptr, nullptr),
+               "pf_register_disparity"))
         return false;
     float k[4];
     if (!hip_ok(hipMemcpy(k, dc.p, sizeof(k), hipMemcpyDeviceToHost), "download")) return false;
@@ -748,10 +795,12 @@ bool ErrorLaplacian(std::string& gt_filename, std::string& baseline_filename,
                           SobelY_mae, Laplacian5x5_mae);
 }
 
-bool MergeDepthMaps(std::string& emap_fn, std::vector<std::string>& pmap_fns,
-                    std::string& out_fn, std::vector<Vec4f>& fovs, std::vector<Vec4f>& ranges,
-                    int out_width, Vec2f& zr, std::string* gt_fn, Metrics* metrics,
-                    int* time_Reg, int* time_Laplacian)
+// The body of MergeDepthMaps for depth tiles, or with disparity_tiles for tiles that hold
+// relative inverse depth (MergeDisparityMaps): only the registration differs.
+static bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns,
+                       std::string& out_fn, std::vector<Vec4f>& fovs, std::vector<Vec4f>& ranges,
+                       int out_width, Vec2f& zr, std::string* gt_fn, Metrics* metrics,
+                       int* time_Reg, int* time_Laplacian, bool disparity_tiles)
 {
     const auto t_begin = std::chrono::steady_clock::now();
     EquirectangularMap emap;
@@ -804,19 +853,27 @@ bool MergeDepthMaps(std::string& emap_fn, std::vector<std::string>& pmap_fns,
     if (!upload(de, emap.data, ne) || !upload(dt, packed.data(), packed.size()) || !dc.ok ||
         !dout.ok)
         return false;
-    // registration (Depth.cpp:789-808): every tile alone, cubic, transform fused into fusion
+    // registration (Depth.cpp:789-808): every tile alone; depth tiles: cubic, transform fused
+    // into the fusion; disparity tiles: y = 1/(a x + b) + d, D2DTransform on the uploaded copy
     auto t = std::chrono::steady_clock::now();
-    if (!pf_ok(c, pf_register(c, de.as<float>(), emap.width, emap.height, emap.channels,
-                              dt.as<float>(), 1, zr[0], zr[1], 3, 0, dc.as<float>(), nullptr),
-               "pf_register") ||
-        !pf_ok(c, pf_synchronize(c), "pf_synchronize"))
+    if (disparity_tiles) {
+        if (!pf_ok(c, pf_register_disparity(c, de.as<float>(), emap.width, emap.height,
+                                            emap.channels, dt.as<float>(), 1, zr[0], zr[1], 1,
+                                            dc.as<float>(), nullptr, nullptr),
+                   "pf_register_disparity"))
+            return false;
+    } else if (!pf_ok(c, pf_register(c, de.as<float>(), emap.width, emap.height, emap.channels,
+                                     dt.as<float>(), 1, zr[0], zr[1], 3, 0, dc.as<float>(),
+                                     nullptr),
+                      "pf_register"))
         return false;
+    if (!pf_ok(c, pf_synchronize(c), "pf_synchronize")) return false;
     if (time_Reg) *time_Reg = elapsed_ms(t);
     // fusion (Depth.cpp:904-913)
     t = std::chrono::steady_clock::now();
     if (!pf_ok(c, pf_fuse(c, de.as<float>(), emap.width, emap.height, emap.channels,
-                          dt.as<float>(), dc.as<float>(), 1, out_width, out_height, zr[0],
-                          zr[1], dout.as<uint16_t>()),
+                          dt.as<float>(), disparity_tiles ? nullptr : dc.as<float>(), 1,
+                          out_width, out_height, zr[0], zr[1], dout.as<uint16_t>()),
                "pf_fuse") ||
         !pf_ok(c, pf_synchronize(c), "pf_synchronize"))
         return false;
@@ -872,6 +929,25 @@ bool MergeDepthMaps(std::string& emap_fn, std::vector<std::string>& pmap_fns,
         }
     }
     return true;
+}
+
+bool MergeDepthMaps(std::string& emap_fn, std::vector<std::string>& pmap_fns,
+                    std::string& out_fn, std::vector<Vec4f>& fovs, std::vector<Vec4f>& ranges,
+                    int out_width, Vec2f& zr, std::string* gt_fn, Metrics* metrics,
+                    int* time_Reg, int* time_Laplacian)
+{
+    return merge_maps(emap_fn, pmap_fns, out_fn, fovs, ranges, out_width, zr, gt_fn, metrics,
+                      time_Reg, time_Laplacian, false);
+}
+
+bool MergeDisparityMaps(std::string& emap_fn, std::vector<std::string>& pmap_fns,
+                        std::string& out_fn, std::vector<Vec4f>& fovs,
+                        std::vector<Vec4f>& ranges, int out_width, Vec2f& zr,
+                        std::string* gt_fn, Metrics* metrics, int* time_Reg,
+                        int* time_Laplacian)
+{
+    return merge_maps(emap_fn, pmap_fns, out_fn, fovs, ranges, out_width, zr, gt_fn, metrics,
+                      time_Reg, time_Laplacian, true);
 }
 
 }  // namespace DepthNamespace
@@ -941,6 +1017,9 @@ int pf_create_depth_panoramas(const std::string& rgb_folder, const std::string& 
     // PF_EDGE_METRICS=1 (panofuse_main --edge-metrics): <raw>.edges.txt beside .aligned.txt
     const char* em = std::getenv("PF_EDGE_METRICS");
     const bool edge_metrics = em && em[0] == '1';
+    // PF_TILE_MODEL=disparity (panofuse_main --tile-model disparity): MiDaS-style tiles
+    const char* tm = std::getenv("PF_TILE_MODEL");
+    const bool disparity_tiles = tm && std::string(tm) == "disparity";
     std::vector<Vec4f> fovs, ranges;
     pf_leres_layout(fovs, ranges);
     std::vector<std::string> rgb;  // AllFilesInFolder (Main.cpp:50-83): files only
@@ -997,8 +1076,14 @@ int pf_create_depth_panoramas(const std::string& rgb_folder, const std::string& 
         }
         DepthNamespace::Metrics m;
         int tr = 0, tl = 0;
-        if (!DepthNamespace::MergeDepthMaps(base, tiles, out, fovs, ranges, out_width,
-                                            g_zenith_range, &gt, &m, &tr, &tl)) {
+        const bool merged =
+            disparity_tiles ? DepthNamespace::MergeDisparityMaps(base, tiles, out, fovs, ranges,
+                                                                 out_width, g_zenith_range, &gt,
+                                                                 &m, &tr, &tl)
+                            : DepthNamespace::MergeDepthMaps(base, tiles, out, fovs, ranges,
+                                                             out_width, g_zenith_range, &gt, &m,
+                                                             &tr, &tl);
+        if (!merged) {
             std::cout << "[CreateDepthPanorma] MergeDepthMaps #" << i << " failed!" << std::endl;
             return 1;
         }

@@ -1,0 +1,391 @@
+// pf_disp.hip -- disparity-tile registration: the per-tile fit of y = 1/(a x + b) + d
+// (FunctorDisparity2Depth, Depth.cpp:1044-1073) by the reference's Ceres 1.13 trust-region
+// Levenberg-Marquardt, and PerspectiveMap::D2DTransform (Depth.cpp:214-243).
+//
+// The cubic of k_register is linear in its coefficients, so its LM runs on 15 moment sums.  This
+// model is not: every LM evaluation is a pass over the tile's samples.  One 256-lane workgroup
+// owns one (panorama, tile) pair, gathers the samples once, keeps them in registers (up to a capacity), and runs the
+// whole LM on them: a Jacobian evaluation reduces 10 fp64 sums, a trial evaluation 1.  Every lane
+// runs the (scalar) LM algebra on the same reduced sums, so every branch is block-uniform; blocks
+// never talk to each other.
+//
+// Summation order (part of the contract; tests/disp_ref.py restates it): lane l adds its samples
+// l, l + 256, ... in order from 0.0, then the halving tree of k_register (stride 128, 64, ..., 1:
+// p[l] = p[l] + p[l + stride]).  Only fp64 + - * / sqrt, no contraction.
+#include "pf_internal.hpp"
+
+#include <cfloat>
+
+namespace pf {
+
+namespace {
+constexpr int kDispLanes = 256;
+// Resident capacity: samples of one tile kept in registers across the LM iterations
+// (kDispPerLane (X, Y) pairs per lane, as the floats they were read as: the clamp to fp64 is
+// repeated per use).  Samples past it are gathered again from the cached indices in every
+// evaluation, in the same per-lane order.
+constexpr int kDispPerLane = 32;
+constexpr int kDispResident = kDispLanes * kDispPerLane;
+constexpr int kDispSums = 10;  // cost, J'r (3), upper J'J (6)
+
+constexpr int kLmMaxIter = 50;
+constexpr double kLmInitRadius = 1e4, kLmMaxRadius = 1e16, kLmMinRadius = 1e-32;
+constexpr double kLmMinRelDecrease = 1e-3, kLmMinDiag = 1e-6, kLmMaxDiag = 1e32;
+constexpr int kLmMaxInvalid = 5;
+constexpr double kLmFuncTol = 1e-6, kLmGradTol = 1e-10, kLmParamTol = 1e-8;
+// termination codes of the summary (the order of pfo_lm_summary's)
+enum { kTermNoConvergence = 0, kTermFunctionTol, kTermParameterTol, kTermGradientTol,
+       kTermMinRadius, kTermFailure };
+
+__device__ __forceinline__ double clamp_sample(double v)
+{  // Depth.cpp:1352-1362, as k_register
+    if (v < 1e-4) v = 1e-4;
+    else if (v > (1 - 1e-4)) v = 1 - 1e-4;
+    return v;
+}
+
+// One sample's terms at p = (a, b, d): r = (q + d) - Y with q = 1 / (a X + b), Jacobian row
+// (-(X q q), -(q q), 1).
+__device__ __forceinline__ void disp_terms(double X, double Y, const double p[3],
+                                           double acc[kDispSums])
+{
+    const double q = 1.0 / (p[0] * X + p[1]);
+    const double r = (q + p[2]) - Y;
+    const double qq = q * q;
+    const double j0 = -(X * qq), j1 = -qq;
+    acc[0] = acc[0] + 0.5 * (r * r);
+    acc[1] = acc[1] + j0 * r;
+    acc[2] = acc[2] + j1 * r;
+    acc[3] = acc[3] + r;
+    acc[4] = acc[4] + j0 * j0;
+    acc[5] = acc[5] + j0 * j1;
+    acc[6] = acc[6] + j0;
+    acc[7] = acc[7] + j1 * j1;
+    acc[8] = acc[8] + j1;
+    acc[9] = acc[9] + 1.0;
+}
+
+__device__ __forceinline__ void disp_cost_term(double X, double Y, const double p[3], double& acc)
+{
+    const double q = 1.0 / (p[0] * X + p[1]);
+    const double r = (q + p[2]) - Y;
+    acc = acc + 0.5 * (r * r);
+}
+
+// The halving tree over the 256 lanes' partial sums, every lane receiving the totals.  Strides
+// 128 and 64 are wave 0 reading the four waves' values from LDS, strides 32..1 its lane shifts:
+// the same additions in the same association as p[l] = p[l] + p[l + stride].
+template <int N>
+__device__ __forceinline__ void disp_reduce(double* acc, double (*part)[kDispLanes], double* tot,
+                                            int l)
+{
+#pragma unroll
+    for (int k = 0; k < N; k++) part[k][l] = acc[k];
+    __syncthreads();
+    if (l < 64) {
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            double v = (part[k][l] + part[k][l + 128]) + (part[k][l + 64] + part[k][l + 192]);
+#pragma unroll
+            for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_down(v, s, 64);
+            if (l == 0) tot[k] = v;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; k++) acc[k] = tot[k];
+}
+
+__device__ __forceinline__ double inv_psd1(double v)
+{  // Eigen LLT of a 1x1 block solved against 1 (InvertPSDMatrix, full rank)
+    const double l = sqrt(v);
+    return (1.0 / l) / l;
+}
+
+__device__ __forceinline__ bool llt2_solve(const double S[2][2], const double rhs[2], double z[2])
+{  // Eigen LLT<Upper> of the 2x2 reduced Schur system, llt3_solve's loops for n = 2
+    if (!(S[0][0] > 0.0)) return false;
+    const double l00 = sqrt(S[0][0]);
+    const double l10 = S[0][1] / l00;
+    const double x = S[1][1] - l10 * l10;
+    if (!(x > 0.0)) return false;
+    const double l11 = sqrt(x);
+    double y0 = rhs[0] / l00;
+    double y1 = rhs[1] - l10 * y0;
+    y1 = y1 / l11;
+    y1 = y1 / l11;
+    y0 = y0 - l10 * y1;
+    y0 = y0 / l00;
+    z[0] = y0;
+    z[1] = y1;
+    return true;
+}
+
+__device__ __forceinline__ double norm3(const double v[3])
+{
+    return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+}
+}  // namespace
+
+__global__ void __launch_bounds__(kDispLanes) k_register_disp(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, const int2* __restrict__ sidx, float* __restrict__ coeffs,
+    double* __restrict__ coeffs64, double* __restrict__ summary)
+{
+    __shared__ double part[kDispSums][kDispLanes];
+    __shared__ double tot[kDispSums];
+    // k_register's block order: the tiles of one panorama on one XCD
+    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
+    const int p = (int)(lb % (unsigned)ntiles), b = (int)(lb / (unsigned)ntiles), l = threadIdx.x;
+    const RegGrid rg = grids[p];
+    const float* tile = tiles + b * tstride + geom[p].off;
+    const float* em = emap + b * estride;
+    const int2* ix = sidx + rg.soff;
+    const int ns = (rg.cols + 1) * (rg.rows + 1);
+
+    // the lane's resident samples l, l + 256, ...: gathered once (independent loads)
+    float xs[kDispPerLane], ys[kDispPerLane];
+#pragma unroll
+    for (int u = 0; u < kDispPerLane; u++) {
+        const int s = l + u * kDispLanes;
+        xs[u] = 0.5f;
+        ys[u] = 0.5f;
+        if (s < ns) {
+            const int2 i2 = ix[s];
+            xs[u] = tile[i2.x];
+            ys[u] = em[i2.y];
+        }
+    }
+
+    auto eval_full = [&](const double* q, double* S) {
+#pragma unroll
+        for (int k = 0; k < kDispSums; k++) S[k] = 0.0;
+#pragma unroll
+        for (int u = 0; u < kDispPerLane; u++)
+            if (l + u * kDispLanes < ns)
+                disp_terms(clamp_sample((double)xs[u]), clamp_sample((double)ys[u]), q, S);
+        for (int s = l + kDispResident; s < ns; s += kDispLanes) {  // past the capacity
+            const int2 i2 = ix[s];
+            disp_terms(clamp_sample((double)tile[i2.x]), clamp_sample((double)em[i2.y]), q, S);
+        }
+        disp_reduce<kDispSums>(S, part, tot, l);
+    };
+    auto eval_cost = [&](const double* q) {
+        double c = 0.0;
+#pragma unroll
+        for (int u = 0; u < kDispPerLane; u++)
+            if (l + u * kDispLanes < ns)
+                disp_cost_term(clamp_sample((double)xs[u]), clamp_sample((double)ys[u]), q, c);
+        for (int s = l + kDispResident; s < ns; s += kDispLanes) {
+            const int2 i2 = ix[s];
+            disp_cost_term(clamp_sample((double)tile[i2.x]), clamp_sample((double)em[i2.y]), q, c);
+        }
+        disp_reduce<1>(&c, part, tot, l);
+        return c;
+    };
+
+    // Ceres 1.13 trust-region LM, the control flow of lm_moments (pf_kernels.hip) for three
+    // parameter blocks: DENSE_SCHUR eliminates a, the reduced system is 2x2 in (b, d).  Every lane
+    // holds the same sums, hence the same state: all exits below are block-uniform.
+    double x[3] = {1.0, 1.0, 1.0}, best[3] = {1.0, 1.0, 1.0};  // Depth.cpp:1270-1274
+    double S[kDispSums], sc[3], Ms[3][3], g[3], gs[3], diag[3] = {0, 0, 0}, D[3], step[3], cand[3];
+    auto take = [&]() {  // g and the scaled J'J from the sums of a Jacobian evaluation
+        const double M[3][3] = {{S[4], S[5], S[6]}, {S[5], S[7], S[8]}, {S[6], S[8], S[9]}};
+        for (int i = 0; i < 3; i++) {
+            g[i] = S[1 + i];
+            for (int j = 0; j < 3; j++) Ms[i][j] = (M[i][j] * sc[i]) * sc[j];
+        }
+    };
+    eval_full(x, S);
+    sc[0] = 1.0 / (1.0 + sqrt(S[4]));  // Jacobi scaling, fixed at iteration 0
+    sc[1] = 1.0 / (1.0 + sqrt(S[7]));
+    sc[2] = 1.0 / (1.0 + sqrt(S[9]));
+    take();
+    double x_cost = S[0];
+    const double initial_cost = x_cost;
+    double radius = kLmInitRadius, decrease = 2.0, x_norm = -1.0, min_cost = DBL_MAX;
+    bool reuse_diag = false, successful = true;
+    int invalid_run = 0, iteration = 0, term = kTermNoConvergence;
+    for (;;) {
+        if (successful && x_cost < min_cost) {
+            min_cost = x_cost;
+            for (int k = 0; k < 3; k++) best[k] = x[k];
+        }
+        if (iteration >= kLmMaxIter) { term = kTermNoConvergence; break; }
+        if (successful) {
+            double gmax = 0.0;
+            for (int k = 0; k < 3; k++) {
+                const double d = fabs(x[k] - (x[k] + -g[k]));
+                if (d > gmax) gmax = d;
+            }
+            if (gmax <= kLmGradTol) { term = kTermGradientTol; break; }
+        }
+        if (radius <= kLmMinRadius) { term = kTermMinRadius; break; }
+        iteration++;
+        if (!reuse_diag)
+            for (int k = 0; k < 3; k++) {
+                const double d = Ms[k][k] > kLmMinDiag ? Ms[k][k] : kLmMinDiag;
+                diag[k] = d < kLmMaxDiag ? d : kLmMaxDiag;
+            }
+        for (int k = 0; k < 3; k++) D[k] = sqrt(diag[k] / radius);
+        for (int k = 0; k < 3; k++) gs[k] = sc[k] * g[k];
+        const double ete = D[0] * D[0] + Ms[0][0];
+        double R[2][2], rhs[2], z[2];
+        for (int a = 0; a < 2; a++)
+            for (int c = a; c < 2; c++)
+                R[a][c] = Ms[1 + a][1 + c] + (a == c ? D[1 + a] * D[1 + a] : 0.0);
+        const double inv = inv_psd1(ete);
+        const double inv_g = inv * gs[0];
+        for (int a = 0; a < 2; a++) rhs[a] = gs[1 + a] - Ms[0][1 + a] * inv_g;
+        for (int a = 0; a < 2; a++) {
+            const double bt = Ms[0][1 + a] * inv;
+            for (int c = a; c < 2; c++) R[a][c] = R[a][c] - bt * Ms[0][1 + c];
+        }
+        bool ok = llt2_solve(R, rhs, z);
+        if (ok) {
+            double ya = gs[0];
+            for (int a = 0; a < 2; a++) ya = ya - Ms[0][1 + a] * z[a];
+            step[0] = inv * ya;
+            step[1] = z[0];
+            step[2] = z[1];
+            for (int k = 0; ok && k < 3; k++) ok = isfinite(step[k]);
+        }
+        reuse_diag = true;
+        double mcc = 0.0, cand_cost = 0.0;
+        bool valid = false;
+        if (ok) {
+            for (int k = 0; k < 3; k++) step[k] = step[k] * -1.0;
+            double sJr = 0.0, sMs = 0.0;
+            for (int i = 0; i < 3; i++) {
+                double q = 0.0;
+                for (int j = 0; j < 3; j++) q = q + Ms[i][j] * step[j];
+                sMs = sMs + step[i] * q;
+                sJr = sJr + step[i] * gs[i];
+            }
+            mcc = -(sJr + sMs / 2.0);
+            valid = mcc > 0.0;
+        }
+        if (valid) {
+            for (int k = 0; k < 3; k++) cand[k] = x[k] + step[k] * sc[k];
+            cand_cost = eval_cost(cand);
+            // a trial whose cost is not finite is a failed evaluation: an invalid step
+            valid = isfinite(cand_cost);
+        }
+        if (!valid) {
+            if (++invalid_run >= kLmMaxInvalid) { term = kTermFailure; break; }
+            radius = radius / decrease;
+            decrease *= 2.0;
+            successful = false;
+            continue;
+        }
+        invalid_run = 0;
+        double dx[3];
+        for (int k = 0; k < 3; k++) dx[k] = x[k] - cand[k];
+        if (norm3(dx) <= kLmParamTol * (x_norm + kLmParamTol)) { term = kTermParameterTol; break; }
+        if (fabs(x_cost - cand_cost) <= kLmFuncTol * x_cost) { term = kTermFunctionTol; break; }
+        const double rel = (x_cost - cand_cost) / mcc;
+        if (rel > kLmMinRelDecrease) {
+            for (int k = 0; k < 3; k++) x[k] = cand[k];
+            x_norm = norm3(x);
+            eval_full(x, S);
+            take();
+            x_cost = S[0];
+            const double q = 2.0 * rel - 1.0;
+            const double f = 1.0 - q * q * q;
+            radius = radius / (f > 1.0 / 3.0 ? f : 1.0 / 3.0);
+            radius = radius < kLmMaxRadius ? radius : kLmMaxRadius;
+            decrease = 2.0;
+            reuse_diag = false;
+            successful = true;
+        } else {
+            radius = radius / decrease;
+            decrease *= 2.0;
+            successful = false;
+        }
+    }
+    if (l == 0) {
+        // abcd = (a, b, 1, d): the order D2DTransform reads (Depth.cpp:216-219, 233)
+        const double full[4] = {best[0], best[1], 1.0, best[2]};
+        const long long o = (long long)b * ntiles + p;
+        for (int i = 0; i < 4; i++) {
+            if (coeffs) coeffs[o * 4 + i] = (float)full[i];
+            if (coeffs64) coeffs64[o * 4 + i] = full[i];
+        }
+        if (summary) {
+            summary[o * 4 + 0] = initial_cost;
+            summary[o * 4 + 1] = min_cost;
+            summary[o * 4 + 2] = (double)iteration;
+            summary[o * 4 + 3] = (double)term;
+        }
+    }
+}
+
+// D2DTransform's per-pixel map (Depth.cpp:225-240).  The X clamps compare the float against the
+// double constants 1e-4 and 1 - 1e-4 as Depth2DepthTransform's do: cubic_map's float thresholds
+// decide identically (pf_internal.hpp).  A NaN passes every comparison and stays NaN.
+__device__ __forceinline__ float disp_map(float X, float a, float b, float c, float d)
+{
+    if (X <= 9.99999974737875e-05f) X = (float)1e-4;
+    else if (X > 0.99989998340606689f) X = (float)(1 - 1e-4);
+    float Y = c / (a * X + b) + d;
+    if (Y < 0) Y = 0;
+    else if (Y > 1) Y = 1;
+    return Y;
+}
+
+// D2DTransform on all tiles (channel 0), in place.
+__global__ void __launch_bounds__(256) k_apply_disp(const TileGeom* __restrict__ geom, int ntiles,
+                                                    float* __restrict__ tiles, long long tstride,
+                                                    const float* __restrict__ coeffs)
+{
+    const int p = blockIdx.y, b = blockIdx.z;
+    const TileGeom g = geom[p];
+    const long long npx = (long long)g.w * g.h;
+    const float4 abcd = *reinterpret_cast<const float4*>(coeffs + ((long long)b * ntiles + p) * 4);
+    float* t = tiles + b * tstride + g.off;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < npx;
+         i += (long long)gridDim.x * 256)
+        t[i * g.c] = disp_map(t[i * g.c], abcd.x, abcd.y, abcd.z, abcd.w);
+}
+
+// D2DTransform of one map, channel 0 of every pixel, in place.
+__global__ void __launch_bounds__(256) k_disp_map(float* __restrict__ data, long long npx, int c,
+                                                  float a, float b, float cc, float d)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < npx;
+         i += (long long)gridDim.x * 256)
+        data[i * c] = disp_map(data[i * c], a, b, cc, d);
+}
+
+void launch_register_disp(hipStream_t s, const TileGeom* geom, const RegGrid* grids, int ntiles,
+                          const float* emap, long long estride, const float* tiles,
+                          long long tstride, const int2* sidx, float* coeffs, double* coeffs64,
+                          double* summary, int batch)
+{
+    hipLaunchKernelGGL(k_register_disp, dim3((unsigned)(ntiles * batch)), dim3(kDispLanes), 0, s,
+                       geom, grids, ntiles, emap, estride, tiles, tstride, sidx, coeffs, coeffs64,
+                       summary);
+}
+
+void launch_apply_disp(hipStream_t s, const TileGeom* geom, int ntiles, long long tile_pixels,
+                       float* tiles, long long tstride, const float* coeffs, int batch)
+{
+    const long long per = tile_pixels / (ntiles > 0 ? ntiles : 1);
+    long long gx = (per + 255) / 256;
+    if (gx > 1024) gx = 1024;
+    if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(k_apply_disp, dim3((unsigned)gx, ntiles, batch), dim3(256), 0, s, geom, ntiles, tiles,
+                       tstride, coeffs);
+}
+
+void launch_disp_map(hipStream_t s, float* data, long long npx, int c, const float* abcd)
+{
+    long long gx = (npx + 255) / 256;
+    if (gx > 4096) gx = 4096;
+    if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(k_disp_map, dim3((unsigned)gx), dim3(256), 0, s, data, npx, c, abcd[0], abcd[1],
+                       abcd[2], abcd[3]);
+}
+
+}  // namespace pf

@@ -356,6 +356,17 @@ void launch_register_joint(hipStream_t s, const double* sums, const int* active,
                            int batch, int degree, int solver, float* coeffs, double* coeffs64);
 void launch_apply_cubic(hipStream_t s, const TileGeom* geom, int ntiles, long long tile_elems,
                         float* tiles, long long tstride, const float* coeffs, int batch);
+// Disparity-tile registration (pf_disp.hip): the LM fit of y = 1/(a x + b) + d per (panorama,
+// tile) on the samples of sidx (launch_regidx), abcd = (a, b, 1, d); summary (optional):
+// [batch][ntiles] x {initial cost, final cost, iterations, termination code}.
+void launch_register_disp(hipStream_t s, const TileGeom* geom, const RegGrid* grids, int ntiles,
+                          const float* emap, long long estride, const float* tiles,
+                          long long tstride, const int2* sidx, float* coeffs, double* coeffs64,
+                          double* summary, int batch);
+// D2DTransform (Depth.cpp:214-243) on all tiles / on one map, channel 0, in place
+void launch_apply_disp(hipStream_t s, const TileGeom* geom, int ntiles, long long tile_pixels,
+                       float* tiles, long long tstride, const float* coeffs, int batch);
+void launch_disp_map(hipStream_t s, float* data, long long npx, int c, const float* abcd);
 int warp_patch_edge();
 int warp_patch_height();
 // host tables (pf_warp.hip): wxy/wfxy of one tile's pixels; the RGB taps of one tile

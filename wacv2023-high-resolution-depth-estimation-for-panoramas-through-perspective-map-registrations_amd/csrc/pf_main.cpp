@@ -2,6 +2,7 @@
 //   panofuse_main 0 <rgb_dir> <gt_dir> <baseline_dir> <result_dir> [--tiles DIR]
 //                 [--ext auto|jpg|png] [--width W] [--device D] [--shard R/N]
 //                 [--metrics-order tree|sequential] [--edge-metrics]
+//                 [--tile-model depth|disparity]
 //   panofuse_main export <rgb_dir> <tile_dir> [--device D]
 //   panofuse_main lap <gt_file> <given_file> [--device D]
 //   panofuse_main cmp <gt_file> <given_file> [--disp] [--align 0|1|2] [--no-cap] [--save FILE]
@@ -21,6 +22,10 @@
 // --metrics-order: the .aligned.txt means in the reference's row-major float order (sequential,
 // the default: the digits Main.cpp prints) or in the fp64-tree order (tree: deterministic, within
 // ~1e-3 relative of the reference's float sums).
+// --tile-model: what the tiles hold.  depth (the default: LeReS-style tiles, the cubic
+// registration) or disparity (MiDaS / DPT tiles, relative inverse depth in 0-1: each is fitted
+// with y = 1/(a x + b) + d and mapped to depth by D2DTransform).  The reference's MiDaS folder
+// convention (Main.cpp:577-579) is `--tiles output --ext png`.
 // --edge-metrics (opt-in, takes no value): also write <raw>.edges.txt per panorama, the
 // ErrorLaplacian values of the result and of the baseline against the gt.
 #include "../../include/pf_depth.h"
@@ -39,7 +44,10 @@ int main(int argc, char* argv[])
         std::cout << "usage: " << argv[0]
                   << " 0 <rgb_dir> <gt_dir> <baseline_dir> <result_dir> [--tiles DIR]"
                      " [--ext auto|jpg|png] [--width W] [--device D] [--shard R/N]"
-                     " [--metrics-order tree|sequential] [--edge-metrics]\n       "
+                     " [--metrics-order tree|sequential] [--edge-metrics]"
+                     " [--tile-model depth|disparity]\n"
+                     "         (MiDaS disparity tiles, the reference's folder convention:"
+                     " --tile-model disparity --tiles output --ext png)\n       "
                   << argv[0] << " export <rgb_dir> <tile_dir> [--device D]\n       "
                   << argv[0] << " lap <gt_file> <given_file> [--device D]\n       "
                   << argv[0]
@@ -193,6 +201,13 @@ int main(int argc, char* argv[])
                 return 2;
             }
             setenv("PF_METRICS_ORDER", v.c_str(), 1);  // read when the facade's context is made
+        }
+        else if (k == "--tile-model") {
+            if (v != "depth" && v != "disparity") {
+                std::cout << "bad --tile-model " << v << " (want depth or disparity)" << std::endl;
+                return 2;
+            }
+            setenv("PF_TILE_MODEL", v.c_str(), 1);  // read by pf_create_depth_panoramas
         }
         else if (k == "--shard") {  // R/N: one process per GPU over the sorted folder
             if (std::sscanf(v.c_str(), "%d/%d", &shard, &nshards) != 2 || nshards < 1 ||

@@ -33,7 +33,8 @@ EXPORTS = [
     "pf_fuse_partial_rows", "pf_fuse_coverage_rows", "pf_fuse_normalize_rows",
     "pf_fuse_tile_rows", "pf_rows_add", "pf_fuse_level", "pf_fuse_targets",
     "pf_rows_add_batch", "pf_set_jacobi_share", "pf_error_laplacian",
-    "pf_error_compare", "pf_disp_depth_convert",
+    "pf_error_compare", "pf_disp_depth_convert", "pf_register_disparity",
+    "pf_disparity_transform", "pf_merge_disparity",
 ]
 NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
           "pf_debug_smooth_fault", "pf_fuse_partial_rows", "pf_fuse_coverage_rows",
@@ -104,6 +105,9 @@ def load():
     L.pf_error_compare.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, ip, ip, fp, fp, ip, ip, ip, vp,
                                    vp, vp]
     L.pf_disp_depth_convert.argtypes = [vp, vp, C.c_longlong, ip]
+    L.pf_register_disparity.argtypes = [vp, vp, ip, ip, ip, vp, ip, fp, fp, ip, vp, vp, vp]
+    L.pf_disparity_transform.argtypes = [vp, vp, C.c_longlong, ip, C.POINTER(C.c_float)]
+    L.pf_merge_disparity.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, fp, fp, vp, vp]
     L.pf_set_solver.argtypes = [vp, ip]
     L.pf_fuse_normalize.argtypes = [vp, vp, vp, ip, ip, fp, fp, ip, vp]
     L.pf_fuse_multicover.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, ip, vp,
@@ -259,6 +263,35 @@ class Fuser:
             raise ValueError("MergeDepthMaps output height is out_w/2")
         self._check(self.L.pf_merge(self.h, _ptr(emap), ew, eh, ec, _ptr(tiles), B, ow,
                                     float(zr[0]), float(zr[1]), _ptr(coeffs), _ptr(out)))
+
+    def register_disparity(self, emap, tiles, zr, apply=True, coeffs=None, coeffs64=None,
+                           summary=None):
+        """The disparity-tile registration (pf_register_disparity): y = 1/(a x + b) + d fitted per
+        tile by the reference's LM, abcd = (a, b, 1, d).  coeffs: float32 [B, ntiles, 4], coeffs64 /
+        summary: float64 [B, ntiles, 4] device tensors (summary = initial cost, final cost,
+        iterations, termination code); apply runs D2DTransform on the tiles.  No sync."""
+        ew, eh, ec = _emap_dims(emap)
+        B = emap.shape[0]
+        self._check(self.L.pf_register_disparity(self.h, _ptr(emap), ew, eh, ec, _ptr(tiles), B,
+                                                 float(zr[0]), float(zr[1]), 1 if apply else 0,
+                                                 _ptr(coeffs), _ptr(coeffs64), _ptr(summary)))
+
+    def disparity_transform(self, t, abcd, channels=1):
+        """D2DTransform (Depth.cpp:214-243) in place on a float32 device tensor: channel 0 of its
+        pixels, `channels` interleaved values each, becomes clamp01(c / (a X + b) + d).  No sync."""
+        k = (C.c_float * 4)(*[float(v) for v in abcd])
+        self._check(self.L.pf_disparity_transform(self.h, _ptr(t), t.numel() // channels,
+                                                  int(channels), k))
+
+    def merge_disparity(self, emap, tiles, out, zr, coeffs=None):
+        """MergeDepthMaps' core for disparity tiles (pf_merge_disparity); tiles stay untouched."""
+        ew, eh, ec = _emap_dims(emap)
+        B, oh, ow = out.shape
+        if oh != ow // 2:
+            raise ValueError("MergeDepthMaps output height is out_w/2")
+        self._check(self.L.pf_merge_disparity(self.h, _ptr(emap), ew, eh, ec, _ptr(tiles), B, ow,
+                                              float(zr[0]), float(zr[1]), _ptr(coeffs),
+                                              _ptr(out)))
 
     def set_metrics_order(self, order):
         """"tree" (the context's default): fp64 partial sums (fast, means within 1e-5 of exact
