@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/build_variant.sh NAME "EXTRA HIPCC FLAGS" [OBJ ...]: an A/B variant of libpanofuse.so built
-# with extra compile-time flags (e.g. -DPF_JLAG_PF=3) into variants/NAME/lib/libpanofuse.so.  With
+# with extra compile-time flags (e.g. -DPF_JLAG_PF=1) into variants/NAME/lib/libpanofuse.so.  With
 # OBJ names (e.g. pf_warp) only those objects are compiled with the flags; the others are the
 # default build's.  A run picks the variant with PANOFUSE_LIB=variants/NAME/lib/libpanofuse.so
 # (tools/gpu_round.sh: VARIANTS="NAME:PANOFUSE_LIB=...").

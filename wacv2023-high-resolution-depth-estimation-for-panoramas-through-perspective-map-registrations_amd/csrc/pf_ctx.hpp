@@ -293,27 +293,26 @@ struct JresPlan {
     bool half = false;  // half-height regions (jres_region_rows)
 };
 
-// The halo columns of a strip on each side: T, rounded up to C for the even forms so each lane's
-// C-vector (and the one vector store per lane) stays aligned; the C == 3 form stores per column.
-inline int strip_halo(int T, int C) { return C == 3 ? T : (T + C - 1) / C * C; }
+// The halo columns of a strip on each side: T, rounded up to the columns per lane so each lane's
+// column vector (and the one vector store per lane) stays aligned.
+inline int strip_halo(int T) { return (T + kJacobiCols - 1) / kJacobiCols * kJacobiCols; }
 
-// Strips of a depth-T pass with C columns per lane over a level w wide: 64 lanes of C columns,
-// of which Tp on each side are halo and V are stored.
+// Strips of a depth-T pass over a level w wide: 64 lanes of kJacobiCols columns, of which Tp on
+// each side are halo and V are stored.
 struct StripGeom {
     int Tp, V, nstrips;
 };
-inline StripGeom strip_geometry(int T, int C, int w)
+inline StripGeom strip_geometry(int T, int w)
 {
-    const int Tp = strip_halo(T, C), V = 64 * C - 2 * Tp;
+    const int Tp = strip_halo(T), V = 64 * kJacobiCols - 2 * Tp;
     return {Tp, V, (w + V - 1) / V};
 }
 
 int jacobi_tcap(const LevelDims& L);
-std::vector<PassPlan> plan_level(pf_ctx* c, const LevelDims& L, int C, int tcap, int batch,
-                                 bool fast, int band_rows = 0);
-// The streaming passes of a whole level, with the columns per lane (*C) they were planned for.
-std::vector<PassPlan> plan_stream(pf_ctx* c, const LevelDims& L, int batch, bool fast, int* C);
-// The row chunking of one depth-T band pass (C = 2, one panorama) over band_rows rows.
+// The streaming passes of a level (of band_rows of its rows; 0: the whole band).
+std::vector<PassPlan> plan_level(pf_ctx* c, const LevelDims& L, int tcap, int batch, bool fast,
+                                 int band_rows = 0);
+// The row chunking of one depth-T band pass (one panorama) over band_rows rows.
 PassPlan plan_band_pass(pf_ctx* c, const LevelDims& L, int T, int band_rows, bool fast);
 JresPlan jres_plan(pf_ctx* c, const LevelDims& L, int batch, bool fast);
 
@@ -348,11 +347,10 @@ JacobiPass jacobi_pass(const pf_ctx* c, const LevelDims& L, const JacobiRun& r);
 int seed_tables(pf_ctx* c, const LevelDims& L, int ew, int eh, int ec);
 int jres_prepare(pf_ctx* c, const LevelDims& L, int batch, const JresPlan& jp);
 
-// The strips and row chunks of one pass: depth T, C columns per lane, band_rows rows in (at
-// most) nchunks chunks.
-inline void set_pass_shape(JacobiPass& P, int T, int C, int band_rows, int nchunks)
+// The strips and row chunks of one pass: depth T, band_rows rows in (at most) nchunks chunks.
+inline void set_pass_shape(JacobiPass& P, int T, int band_rows, int nchunks)
 {
-    const StripGeom g = strip_geometry(T, C, P.w);
+    const StripGeom g = strip_geometry(T, P.w);
     P.Tp = g.Tp;
     P.V = g.V;
     P.nstrips = g.nstrips;

@@ -33,10 +33,11 @@ int pf::seed_tables(pf_ctx* c, const LevelDims& L, int ew, int eh, int ec)
 int pf::jres_prepare(pf_ctx* c, const LevelDims& L, int batch, const JresPlan& jp)
 {
     int rc;
-    const size_t xb = sizeof(float) * jres_words_per_value() * (size_t)batch * jp.nb * 4 *
-                      (size_t)jp.K * L.w;
+    // hand-off rows [batch][nb][2 parity][2 edge][K][w] (JresArgs::xbuf)
+    const size_t xb = sizeof(float) * (size_t)batch * jp.nb * 4 * (size_t)jp.K * L.w;
     if ((rc = ensure(c, c->jres_x, xb))) return rc;
-    const size_t sb = sizeof(uint32_t) * (2 + (size_t)batch * jp.nb * jres_flags_per_block(jp.K));
+    // ticket, error count, one flag word per row block
+    const size_t sb = sizeof(uint32_t) * (2 + (size_t)batch * jp.nb);
     if ((rc = ensure_err_host(c))) return rc;
     if (c->jres_sync.bytes < sb) {
         if ((rc = ensure(c, c->jres_sync, sb))) return rc;
@@ -130,8 +131,7 @@ float* pf::run_jacobi(pf_ctx* c, const LevelDims& L, const JacobiRun& r, int* np
     static const bool slow = getenv("PF_JSLOW") != nullptr;  // force the general (scalar) form
     // packed form: the level's separable-coverage certificate (pf_jacobi.hip)
     const bool fast = r.hcol && !slow;
-    int C = 2;
-    const std::vector<PassPlan> plan = plan_stream(c, L, r.batch, fast, &C);
+    const std::vector<PassPlan> plan = plan_level(c, L, jacobi_tcap(L), r.batch, fast);
     if (r.first == 2 && r.emap && !seed_tables_match(c, L, r.ew, r.eh, r.ec)) return nullptr;
     JacobiPass P = jacobi_pass(c, L, r);
     const int band_rows = L.h1 - L.h0 + 1;
@@ -139,7 +139,7 @@ float* pf::run_jacobi(pf_ctx* c, const LevelDims& L, const JacobiRun& r, int* np
     float* dst = (r.first == 0) ? r.b : r.a;
     if (show_plans()) {
         fprintf(stderr, "jacobi plan %dx%d band %d iters %d batch %d %s C%d:", L.w, L.h,
-                band_rows, L.iters, r.batch, fast ? "packed" : "general", C);
+                band_rows, L.iters, r.batch, fast ? "packed" : "general", kJacobiCols);
         for (const PassPlan& pp : plan)
             fprintf(stderr, " T%d/n%d%s", pp.T, pp.nchunks, pp.stages > 1 ? "p" : "");
         fprintf(stderr, "\n");
@@ -147,13 +147,13 @@ float* pf::run_jacobi(pf_ctx* c, const LevelDims& L, const JacobiRun& r, int* np
     int pass = 0;
     for (const PassPlan& pp : plan) {
         const int T = pp.T;
-        set_pass_shape(P, T, C, band_rows, pp.nchunks);
+        set_pass_shape(P, T, band_rows, pp.nchunks);
         P.src_mode = pass == 0 ? r.first : 0;
         P.src = src;
         P.dst = dst;
         P.out_mode = (pass + 1 == (int)plan.size() && r.out) ? 1 : 0;
         if (pp.stages > 1) launch_jpipe(c->stream, P, pp.stages, T / pp.stages, r.batch);
-        else launch_jstream(c->stream, P, C, T, r.batch, fast);
+        else launch_jstream(c->stream, P, T, r.batch, fast);
         src = dst;
         dst = (dst == r.a) ? r.b : r.a;
         pass++;

@@ -205,6 +205,10 @@ __host__ __device__ inline long long emap_index(float az, float zen, int w, int 
     return ((long long)y * w + x) * c;
 }
 
+// Columns per lane of the streamed Jacobi passes: a wave's strip is 64 * kJacobiCols virtual
+// columns wide (3 and 4 were built and measured slower on MI355X).
+static constexpr int kJacobiCols = 2;
+
 // One temporally blocked Jacobi pass (pf_jacobi.hip).
 struct JacobiPass {
     const float* src; long long sstride;    // SRC_BUF input
@@ -251,8 +255,6 @@ struct JresArgs {
 };
 int jres_region_rows(int w, bool half = false);  // 0: not supported
 int jres_threads();
-int jres_words_per_value();
-int jres_flags_per_block(int K);  // 2: the hand-off rows travel as {value, tag} granules
 int jres_blocks_per_cu(int w, bool half);
 void launch_jres(hipStream_t s, const JresArgs& A);
 
@@ -293,9 +295,8 @@ void launch_targets_multi(hipStream_t s, const TileGeom* geom, int ntiles, const
                           long long tstride, const float* coeffs, const TgtMulti& M,
                           const int2* order, int batch);
 bool jstream_supported_T(int T);
-int jstream_waves_per_cu(int C, int T, bool fast);
-bool jstream_supported_C(int C, bool fast);
-void launch_jstream(hipStream_t s, const JacobiPass& P, int C, int T, int batch, bool fast);
+int jstream_waves_per_cu(int T, bool fast);
+void launch_jstream(hipStream_t s, const JacobiPass& P, int T, int batch, bool fast);
 bool jpipe_supported(int S, int TS);
 int jpipe_waves_per_cu(int S, int TS);
 void launch_jpipe(hipStream_t s, const JacobiPass& P, int S, int TS, int batch);

@@ -34,6 +34,12 @@
 // un-windowed ones (the host's separable-coverage certificate; column 0 is never windowed, so the
 // west tap of column 0 is never needed).  The east tap of column w-1 is pixel (0, Y+1): the
 // reference's linear buffer[yy*width + xx] addressing.
+//
+// Built, measured no faster on MI355X and removed (the code is in this file's
+// history): barrier-free sweeps with LDS flags and per-row hand-off flags (same time as the
+// barriers); hand-off by data-tagged {value, round} granules (2x slower); a wave's last row
+// stored to LDS before its row 0 is computed (no change); a 1024-wide form of 8 waves (slower
+// than the streaming passes in both places it was tried).
 #include "pf_internal.hpp"
 
 namespace pf {
@@ -80,19 +86,6 @@ __device__ __forceinline__ float fma_scalar(float a, float b, float c)
     asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
-
-#ifndef PF_JRES_LDSFLAG
-#define PF_JRES_LDSFLAG 0  // barrier-free sweeps + per-row hand-off flags (measured: same time as barriers)
-#endif
-#ifndef PF_JRES_EARLY_EDGE
-// 1: a wave's new last row goes to LDS before its row 0 is computed (the store overlaps row 0's
-// arithmetic).  Round 6, three alternating serial rounds on one MI355X: 506-528 us against
-// 508-523 us per C3 launch: no change.  Off.
-#define PF_JRES_EARLY_EDGE 0
-#endif
-#ifndef PF_JRES_GRANULE
-#define PF_JRES_GRANULE 0  // hand-off by data-tagged granules (measured 2x slower: 32-KB edges)
-#endif
 
 // sc1 (write-through / L2-bypassing) buffer accesses for the inter-workgroup row hand-off
 constexpr int kSC1 = 16;
@@ -180,12 +173,8 @@ struct JRes {
             rows_mid<R + 1, HAS_EDGE>(n, dn, em);
         }
     }
-    // bot_out (JRES_EARLY_EDGE): the LDS slot of this wave's new last row, stored as soon as
-    // that row is done, so the store overlaps row 0's arithmetic instead of joining the stores
-    // every wave issues just before the sweep's barrier
     template <bool HAS_EDGE>
-    __device__ __forceinline__ void sweep(const f2* up_lds, const f2* dn_lds, uint32_t em,
-                                          f2* bot_out = nullptr)
+    __device__ __forceinline__ void sweep(const f2* up_lds, const f2* dn_lds, uint32_t em)
     {
         f2 up[NP], dn[NP], s1[NP], n[NP];
 #pragma unroll
@@ -196,9 +185,6 @@ struct JRes {
             n[k] = b[0][k];
         }
         if constexpr (RS > 1) rows_mid<1, HAS_EDGE>(n, dn, em);
-        if (RS > 1 && bot_out)
-#pragma unroll
-            for (int k = 0; k < NP; k++) bot_out[64 * k] = b[RS - 1][k];
         if (HAS_EDGE && (em & 1u)) row<0, true>(up, RS > 1 ? s1 : dn);
         else row<0, false>(up, RS > 1 ? s1 : dn);
     }
@@ -289,155 +275,6 @@ __global__ void __launch_bounds__(64 * NWV) k_jres(JresArgs A)
 
     const long long xplane = (long long)K * w;  // floats of one published edge
     float* const xb = A.xbuf;
-#if PF_JRES_LDSFLAG
-    // Barrier-free sweeps: wave w starts sweep s+1 once its neighbour waves have published their
-    // edge rows of state s (an LDS flag per wave), so a wave runs at most one sweep ahead of its
-    // neighbours and, while the halo waves wait for a hand-off, the waves further in keep
-    // sweeping (a wave d waves from the halo can run d sweeps ahead).  Edge rows of state s sit in
-    // buffer s & 1: wave w overwrites buffer s & 1 only after its neighbours published state s+1,
-    // i.e. after they read state s-1 from it.  The hand-off is per row: each published row
-    // carries its own flag (one sc1 store after the storing wave's vmcnt(0)); a halo wave polls
-    // the flags of its own rows only.  No workgroup barrier after the start.
-    __shared__ int eflag[NW];
-    auto publish_edges = [&](int st) {
-        put_edges(st & 1);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (lane == 0) *reinterpret_cast<volatile int*>(&eflag[wv]) = st;
-    };
-    auto wait_edges = [&](int nbw, int st) {
-        int spins = 0;
-        while (*reinterpret_cast<volatile int*>(&eflag[nbw]) < st) {
-            __builtin_amdgcn_s_sleep(0);
-            if (++spins > (1 << 26)) {
-                if (lane == 0) jres_timeout(A);
-                break;
-            }
-        }
-        asm volatile("" ::: "memory");  // the edge reads below stay after the flag read
-    };
-    // halo rows of this wave (refreshed from the neighbour blocks after every round), as bits
-    uint32_t halo = 0;
-#pragma unroll
-    for (int r = 0; r < RS; r++) {
-        const int Y = rs + wv * RS + r;
-        if ((j > 0 && Y >= c0 - K && Y < c0) || (j < A.nb - 1 && Y >= c1 && Y < re)) halo |= 1u << r;
-    }
-    halo = __builtin_amdgcn_readfirstlane(halo);
-    uint32_t* const gflag = A.flags;  // [batch][nb][2 edge][K] per published row
-    publish_edges(0);
-    __syncthreads();  // every wave's state-0 edges and flag in place
-    int s = 0, round = 0;
-    while (true) {
-        const int n = min(K, A.iters - s);
-        for (int i = 0; i < n; i++) {
-            if (wv > 0) wait_edges(wv - 1, s);
-            if (wv < NW - 1) wait_edges(wv + 1, s);
-            const int cb = s & 1;
-            const f2* up = wv > 0 ? &lds_edge[cb][1][wv > 0 ? wv - 1 : 0][0][lane] : nullptr;
-            const f2* dn = wv < NW - 1 ? &lds_edge[cb][0][wv < NW - 1 ? wv + 1 : 0][0][lane] : nullptr;
-            const int reach = n - 1 - i;
-            const bool skip = (j > 0 && wv * RS + RS - 1 < qc0 - reach) ||
-                              (j < A.nb - 1 && wv * RS >= qc1 + reach);
-            if (!(A.dbg & 4) && !skip) {
-                if (em) S.template sweep<true>(up, dn, em);
-                else S.template sweep<false>(up, dn, em);
-            }
-            s++;
-            // a halo wave publishes its end-of-round edges after the hand-off refreshed its rows
-            if (!(i == n - 1 && halo && s < A.iters)) publish_edges(s);
-        }
-        round++;
-        if (s >= A.iters) break;
-        if (A.dbg & 1) {
-            if (halo) publish_edges(s);
-            continue;
-        }
-        int xl = x0;
-        asm volatile("" : "+v"(xl));
-        const int par = round & 1;
-        const uint32_t want = A.fbase + (uint32_t)round;
-        // publish: this wave's core rows that a neighbour block needs (sc1 stores, drained, then
-        // one sc1 flag per row)
-        {
-            float* mine = xb + ((long long)(p * A.nb + j) * 2 + par) * 2 * xplane;
-            const auto mr = rsrc(mine, (uint32_t)(sizeof(float) * xplane * 2));
-            uint32_t pubm = 0;  // bit 2r+e: row r published in edge set e
-#pragma unroll
-            for (int r = 0; r < RS; r++) {
-                const int Y = rs + wv * RS + r;
-#pragma unroll
-                for (int e = 0; e < 2; e++) {
-                    const bool pub = e == 0 ? (j > 0 && Y >= c0 && Y < c0 + K)
-                                            : (j < A.nb - 1 && Y >= c1 - K && Y < c1);
-                    if (!pub) continue;  // wave-uniform
-                    pubm |= 1u << (2 * r + e);
-                    const int yo = e == 0 ? Y - c0 : Y - (c1 - K);
-                    const int off = (int)(sizeof(float) * (e * xplane + (long long)yo * w + xl));
-#pragma unroll
-                    for (int k = 0; k < NP; k += 2) {
-                        u4v v;
-                        v[0] = __float_as_uint(S.b[r][k].x);
-                        v[1] = __float_as_uint(S.b[r][k].y);
-                        v[2] = __float_as_uint(S.b[r][k + 1].x);
-                        v[3] = __float_as_uint(S.b[r][k + 1].y);
-                        __builtin_amdgcn_raw_buffer_store_b128(v, mr, off + 8 * k, 0, kSC1);
-                    }
-                }
-            }
-            if (pubm) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                // lane 2r+e flags row r of edge set e
-                if (lane < 2 * RS && ((pubm >> lane) & 1u)) {
-                    const int r = lane >> 1, e = lane & 1;
-                    const int Y = rs + wv * RS + r;
-                    const int yo = e == 0 ? Y - c0 : Y - (c1 - K);
-                    __hip_atomic_store(&gflag[((long long)(p * A.nb + j) * 2 + e) * K + yo], want,
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
-        if (halo) {
-            // poll the flags of this wave's halo rows (lane r: row r), then load them
-            int spins = 0;
-            while (true) {
-                bool ok = true;
-                if (lane < RS && ((halo >> lane) & 1u)) {
-                    const int Y = rs + wv * RS + lane;
-                    const bool top = j > 0 && Y < c0;
-                    const int sj = top ? j - 1 : j + 1, e = top ? 1 : 0;
-                    const int yo = top ? Y - (c0 - K) : Y - c1;
-                    const uint32_t f = __hip_atomic_load(&gflag[((long long)(p * A.nb + sj) * 2 + e) * K + yo],
-                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ok = (int)(f - want) >= 0;
-                }
-                if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1 << A.spin_log2)) {
-                    if (lane == 0) jres_timeout(A);
-                    break;
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < RS; r++) {
-                if (!((halo >> r) & 1u)) continue;  // wave-uniform
-                const int Y = rs + wv * RS + r;
-                const bool top = j > 0 && Y < c0;
-                const int sj = top ? j - 1 : j + 1, e = top ? 1 : 0;
-                const int yo = top ? Y - (c0 - K) : Y - c1;
-                const float* theirs = xb + ((long long)(p * A.nb + sj) * 2 + par) * 2 * xplane;
-                const auto tr = rsrc(theirs, (uint32_t)(sizeof(float) * xplane * 2));
-                const int off = (int)(sizeof(float) * (e * xplane + (long long)yo * w + xl));
-#pragma unroll
-                for (int k = 0; k < NP; k += 2) {
-                    const u4v v = __builtin_amdgcn_raw_buffer_load_b128(tr, off + 8 * k, 0, kSC1);
-                    S.b[r][k] = f2{__uint_as_float(v[0]), __uint_as_float(v[1])};
-                    S.b[r][k + 1] = f2{__uint_as_float(v[2]), __uint_as_float(v[3])};
-                }
-            }
-            publish_edges(s);
-        }
-    }
-#else
     int s = 0, round = 0;
     while (true) {
         const int n = min(K, A.iters - s);
@@ -454,20 +291,10 @@ __global__ void __launch_bounds__(64 * NWV) k_jres(JresArgs A)
             const bool skip = (j > 0 && wv * RS + RS - 1 < qc0 - reach) ||
                               (j < A.nb - 1 && wv * RS >= qc1 + reach);
             if (!(A.dbg & 4) && !skip) {
-#if PF_JRES_EARLY_EDGE
-                f2* bot = RS > 1 && !(A.dbg & 8) ? &lds_edge[cb ^ 1][1][wv][0][lane] : nullptr;
-#else
-                f2* bot = nullptr;
-#endif
-                if (em) S.template sweep<true>(up, dn, em, bot);
-                else S.template sweep<false>(up, dn, em, bot);
+                if (em) S.template sweep<true>(up, dn, em);
+                else S.template sweep<false>(up, dn, em);
                 if (!(A.dbg & 8)) {
-                    if (bot) {  // the last row went out inside the sweep
-#pragma unroll
-                        for (int k = 0; k < NP; k++) lds_edge[cb ^ 1][0][wv][k][lane] = S.b[0][k];
-                    } else {
-                        put_edges(cb ^ 1);
-                    }
+                    put_edges(cb ^ 1);
                     __syncthreads();
                 }
             } else if (!(A.dbg & 8)) {
@@ -487,61 +314,6 @@ __global__ void __launch_bounds__(64 * NWV) k_jres(JresArgs A)
         asm volatile("" : "+v"(xl));
         const int par = round & 1;
         const uint32_t want = A.fbase + (uint32_t)round;
-#if PF_JRES_GRANULE
-        // Data-tagged granules (MI355X_MICROARCH.md, handoff-1to1): every float travels as one
-        // 8-B {value, round tag} granule, stored write-through (sc1) with no wait and no flag;
-        // the consumer waves re-read their rows (sc1) until every tag is this round's.  Parity
-        // slots: a block overwrites slot (round & 1) only after taking its neighbours' rows of
-        // the round in between, which they publish after reading this slot.
-        uint32_t* const gb = reinterpret_cast<uint32_t*>(xb);
-        const long long gplane = 2 * xplane;  // uint32 words of one published edge
-        const uint32_t gbytes = (uint32_t)(sizeof(uint32_t) * gplane * 2);
-        const auto mr = rsrc(gb + ((long long)(p * A.nb + j) * 2 + par) * 2 * gplane, gbytes);
-#pragma unroll
-        for (int r = 0; r < RS; r++) {
-            const int Y = rs + wv * RS + r;
-#pragma unroll
-            for (int e = 0; e < 2; e++) {  // a row can be in both published sets when core < 2K
-                const bool pub = e == 0 ? (j > 0 && Y >= c0 && Y < c0 + K)
-                                        : (j < A.nb - 1 && Y >= c1 - K && Y < c1);
-                if (!pub) continue;  // wave-uniform
-                const int yo = e == 0 ? Y - c0 : Y - (c1 - K);
-                const int off = (int)(sizeof(uint32_t) * (e * gplane + 2 * ((long long)yo * w + xl)));
-#pragma unroll
-                for (int k = 0; k < NP; k++) {
-                    const u4v v = {__float_as_uint(S.b[r][k].x), want, __float_as_uint(S.b[r][k].y), want};
-                    __builtin_amdgcn_raw_buffer_store_b128(v, mr, off + 16 * k, 0, kSC1);
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < RS; r++) {
-            const int Y = rs + wv * RS + r;
-            int src_j = -1, e = 0, yo = 0;
-            if (j > 0 && Y >= c0 - K && Y < c0) { src_j = j - 1; e = 1; yo = Y - (c0 - K); }
-            else if (j < A.nb - 1 && Y >= c1 && Y < re) { src_j = j + 1; e = 0; yo = Y - c1; }
-            if (src_j >= 0) {  // wave-uniform
-                const auto tr = rsrc(gb + ((long long)(p * A.nb + src_j) * 2 + par) * 2 * gplane, gbytes);
-                const int off = (int)(sizeof(uint32_t) * (e * gplane + 2 * ((long long)yo * w + xl)));
-                int spins = 0;
-                while (true) {
-                    bool ok = true;
-#pragma unroll
-                    for (int k = 0; k < NP; k++) {
-                        const u4v v = __builtin_amdgcn_raw_buffer_load_b128(tr, off + 16 * k, 0, kSC1);
-                        S.b[r][k] = f2{__uint_as_float(v[0]), __uint_as_float(v[2])};
-                        ok = ok && v[1] == want && v[3] == want;
-                    }
-                    if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;  // every lane's granules current
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > (1 << (A.spin_log2 - 2))) {  // bounded: counted, never hangs
-                        if (lane == 0) jres_timeout(A);
-                        break;
-                    }
-                }
-            }
-        }
-#else
         float* mine = xb + ((long long)(p * A.nb + j) * 2 + par) * 2 * xplane;
         const auto mr = rsrc(mine, (uint32_t)(sizeof(float) * xplane * 2));
 #pragma unroll
@@ -605,10 +377,7 @@ __global__ void __launch_bounds__(64 * NWV) k_jres(JresArgs A)
                 }
             }
         }
-#endif
     }
-
-#endif
 
     // ---- the core rows of the finished level
 #pragma unroll
@@ -665,20 +434,7 @@ static void launch_cr(hipStream_t s, const JresArgs& A, int grid, int src_mode, 
 #define PF_JRES_WAVES 16
 #endif
 static constexpr int kJW = PF_JRES_WAVES;
-int jres_words_per_value() { return PF_JRES_GRANULE ? 2 : 1; }
-// hand-off flag words per row block: one per published row (LDS-flag form) or one per block
-int jres_flags_per_block(int K) { return PF_JRES_LDSFLAG ? 2 * K : 1; }
 static constexpr int kRS512 = 64 / kJW, kRS256 = 128 / kJW;
-
-// 1024-wide levels (round 5, off): 16 columns per lane, 8 waves of 4 rows (a 32-row region; the
-// LDS edge rows of 16 waves would need 256 KB, 8 waves need 128 KB: one workgroup per CU, two
-// waves per SIMD at 236 VGPRs, no spills).  Measured slower than the streaming passes: C5's one
-// call 2.42 ms against 2.16 (its 1024-wide level 0 at batch 1), and C3's batch-64 level 1
-// (PF_JRES1024_ANY=1) 14.2k against 16.7k panoramas/s (profiles/r05/jres1024.txt).
-#ifndef PF_JRES_1024
-#define PF_JRES_1024 0
-#endif
-static constexpr int kJW1024 = 8, kRS1024 = 4;
 
 // Half-height regions (round 5): the same workgroup with half the rows per wave (512 wide: 2
 // rows, a 32-row region).  A sweep then costs each wave half the updates, which is what a
@@ -695,7 +451,6 @@ int jres_region_rows(int w, bool half)
     if (half) return (PF_JRES_HALF && w == 512) ? 32 : 0;
     if (w == 512) return 64;
     if (w == 256) return 128;
-    if (w == 1024 && PF_JRES_1024) return kJW1024 * kRS1024;
     return 0;
 }
 int jres_threads() { return 64 * kJW; }
@@ -709,10 +464,6 @@ void launch_jres(hipStream_t s, const JresArgs& A)
 #endif
     if (A.w == 512) launch_cr<8, kRS512, kJW>(s, A, grid, A.src_mode, A.out != nullptr);
     else if (A.w == 256) launch_cr<4, kRS256, kJW>(s, A, grid, A.src_mode, A.out != nullptr);
-#if PF_JRES_1024
-    else if (A.w == 1024)
-        launch_cr<16, kRS1024, kJW1024>(s, A, grid, A.src_mode, A.out != nullptr);
-#endif
 }
 
 // resident blocks per CU of the instantiation that launches at this width (half: the half-height
@@ -721,20 +472,13 @@ int jres_blocks_per_cu(int w, bool half)
 {
     int nb = 0;
     const void* f = reinterpret_cast<const void*>(k_jres<8, kRS512, kJW, 0, false>);
-    int threads = 64 * kJW;
 #if PF_JRES_HALF
     if (w == 512 && half) f = reinterpret_cast<const void*>(k_jres<8, kRS512 / 2, kJW, 0, false>);
 #else
     (void)half;
 #endif
     if (w == 256) f = reinterpret_cast<const void*>(k_jres<4, kRS256, kJW, 0, false>);
-#if PF_JRES_1024
-    if (w == 1024) {
-        f = reinterpret_cast<const void*>(k_jres<16, kRS1024, kJW1024, 0, false>);
-        threads = 64 * kJW1024;
-    }
-#endif
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, threads, 0) != hipSuccess) nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, 64 * kJW, 0) != hipSuccess) nb = 0;
     return nb;
 }
 

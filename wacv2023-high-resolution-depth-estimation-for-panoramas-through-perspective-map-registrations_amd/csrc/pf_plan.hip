@@ -13,19 +13,13 @@ static int plan_simds(const pf_ctx* c)
     return n < 4 ? 4 : n;
 }
 
-// Jacobi pass geometry: lanes own C columns, strips carry a Tp-column halo (Tp >= T, rounded to
-// C so vector rows stay aligned); the sweep depth and row chunking of every pass come from the
-// cost model of plan_level().  Env overrides for tuning runs: PF_JT (largest T), PF_JOVH (per-step
-// overhead in update units), PF_JC=4 (4 columns per lane, builds with PF_JACOBI_C4 only).
+// Jacobi pass geometry: lanes own kJacobiCols columns, strips carry a Tp-column halo (Tp >= T,
+// rounded to the column count so vector rows stay aligned); the sweep depth and row chunking of
+// every pass come from the cost model of plan_level().  Env overrides for tuning runs: PF_JT
+// (largest T), PF_JOVH (per-step overhead in update units).
 struct JacobiTuning {
-    // columns per lane: 2 (default); PF_JC=3 / 4 force those forms, PF_JC=0 lets the cost model
-    // pick per level.  Round 6 measured C = 3 (192-column strips, 10 % less halo at level 1, 5 %
-    // at level 2, but its L ring in LDS and 224 VGPRs: two waves per SIMD) slower on MI355X: T10
-    // passes 100-103 / 343-355 us at levels 1 / 2 against 92 / 296 us for C = 2 (serial C3 trace),
-    // and the cost model, which does not see that, would pick it (with T8 / T5 passes: 4.2 ms)
-    int C = 2, Tmax = 10;
+    int Tmax = 10;
     double step_overhead = 3.0, lone_cycles = 4.0;  // swept on MI355X (profiles/r02/jacobi; recipe: tools/gpu_round.sh ab)
-    double c4_eff = 23.0 / 26.0;  // packed C=4 issue per pixel-update relative to C=2
     double pipe_overhead = 1.0;   // pipelined engine: barrier + exchange per step, update units
     // per pass, in the cost units of best_chunks (~10 ns each at C3): a launch's fixed cost
     // (dispatch, ramp, drain; a few us).  Without it the planner cut the batch-1 levels into
@@ -39,8 +33,6 @@ static const JacobiTuning& jacobi_tuning()
 {
     static const JacobiTuning tune = [] {
         JacobiTuning t;
-        if (const char* e = getenv("PF_JC")) t.C = atoi(e) == 4 ? 4 : (atoi(e) == 3 ? 3 : (atoi(e) == 0 ? 0 : 2));
-        if (const char* e = getenv("PF_JC4EFF")) t.c4_eff = atof(e);
         if (const char* e = getenv("PF_JT")) t.Tmax = atoi(e);
         if (const char* e = getenv("PF_JOVH")) t.step_overhead = atof(e);
         if (const char* e = getenv("PF_JC1")) t.lone_cycles = atof(e);
@@ -53,25 +45,23 @@ static const JacobiTuning& jacobi_tuning()
 }
 
 // One pass: depth T, nchunks row chunks.  Its nstrips*batch*nchunks waves each run
-// rows_per_chunk + 3T + ~4 steps of T*C updates (lagged levels, halo, 6-step alignment), and
+// rows_per_chunk + 3T + ~4 steps of T updates per column (lagged levels, halo, 6-step alignment), and
 // they run in ceil(waves / resident) rounds, so the pass costs ~ rounds * steps * (T + o) with o
 // the per-step overhead (loads, LDS ring, store) in update units.  Whole rounds matter: at the
 // small levels a "one wave per slot" grid left the last round 20-80% empty.
-static PassPlan best_chunks(int T, int C, int band_rows, int w, int batch, int per_simd,
-                            int nsimd, int stages = 1)
+static PassPlan best_chunks(int T, int band_rows, int w, int batch, int per_simd, int nsimd,
+                            int stages = 1)
 {
     const JacobiTuning& tune = jacobi_tuning();
     const double c1 = tune.lone_cycles;
     const double ovh = tune.step_overhead + (stages > 1 ? tune.pipe_overhead : 0.0);
-    // VALU work of one step of one wave in update units: T/stages levels of C updates, per-update
-    // issue of the C form
-    const double lv = (double)T / stages;
-    const double work = C == 4 ? lv * 2.0 * tune.c4_eff : (C == 3 ? lv * 1.5 : lv);
+    // VALU work of one step of one wave in update units: T/stages levels
+    const double work = (double)T / stages;
     PassPlan best;
     best.T = T;
     best.stages = stages;
     best.cost = 1e300;
-    const long long per = (long long)strip_geometry(T, C, w).nstrips * batch;
+    const long long per = (long long)strip_geometry(T, w).nstrips * batch;
     const long long slots = (long long)per_simd * nsimd;
     for (int n = 1; n <= band_rows; n++) {
         const int rows = (band_rows + n - 1) / n;
@@ -96,7 +86,7 @@ static PassPlan best_chunks(int T, int C, int band_rows, int w, int batch, int p
 
 // Sweep depths for a level: a shortest-path split of `iters` into passes from the supported
 // menu (<= tcap), each with its best chunking.
-std::vector<PassPlan> pf::plan_level(pf_ctx* c, const LevelDims& L, int C, int tcap, int batch,
+std::vector<PassPlan> pf::plan_level(pf_ctx* c, const LevelDims& L, int tcap, int batch,
                                      bool fast, int band_rows)
 {
     const JacobiTuning& tune = jacobi_tuning();
@@ -105,20 +95,20 @@ std::vector<PassPlan> pf::plan_level(pf_ctx* c, const LevelDims& L, int C, int t
     PassPlan opt[11];
     for (int T : menu)
         if (T <= tcap && jstream_supported_T(T))
-            opt[T] = best_chunks(T, C, band_rows, L.w, batch,
-                                 jstream_waves_per_cu(C, T, fast) / 4, 4 * c->num_cu);
+            opt[T] = best_chunks(T, band_rows, L.w, batch, jstream_waves_per_cu(T, fast) / 4,
+                                 4 * c->num_cu);
     // the pipelined engine (2 waves per strip-chunk), packed form only; PF_JPIPE=0 disables it,
     // PF_JPIPE=1 takes it wherever it exists, otherwise the cost model decides
     static const char* pe = getenv("PF_JPIPE");
     const int pmode = pe ? atoi(pe) : 2;
-    if (fast && C == 2 && pmode != 0)
+    if (fast && pmode != 0)
         for (int T : menu) {
             if (T > tcap || T % 2 || !jpipe_supported(2, T / 2)) continue;
-            PassPlan pp = best_chunks(T, C, band_rows, L.w, batch,
-                                      jpipe_waves_per_cu(2, T / 2) / 4, 4 * c->num_cu, 2);
+            PassPlan pp = best_chunks(T, band_rows, L.w, batch, jpipe_waves_per_cu(2, T / 2) / 4,
+                                      4 * c->num_cu, 2);
             if (pmode == 1 || pp.cost < opt[T].cost || !jstream_supported_T(T)) opt[T] = pp;
         }
-    if (fast && C == 2 && pmode == 1)  // forced: the single-wave engine only where no pipe fits
+    if (fast && pmode == 1)  // forced: the single-wave engine only where no pipe fits
         for (int T : menu)
             if (opt[T].stages == 1) opt[T].cost *= 1e6;
     // tuning runs: PF_JTONLY<w>=T restricts the level of width w to depth-T passes (and depths 1
@@ -147,8 +137,8 @@ std::vector<PassPlan> pf::plan_level(pf_ctx* c, const LevelDims& L, int C, int t
     if (c->jacobi_share < 1.0)
         for (PassPlan& pp : plan)
             if (pp.stages == 1)
-                pp.nchunks = best_chunks(pp.T, C, band_rows, L.w, batch,
-                                         jstream_waves_per_cu(C, pp.T, fast) / 4, plan_simds(c))
+                pp.nchunks = best_chunks(pp.T, band_rows, L.w, batch,
+                                         jstream_waves_per_cu(pp.T, fast) / 4, plan_simds(c))
                                  .nchunks;
     // tuning runs: PF_JN<w> forces the row chunking of the level of width w
     char key[32];
@@ -176,39 +166,9 @@ int pf::jacobi_tcap(const LevelDims& L)
     return cap;
 }
 
-// The streaming passes of a whole level.  2 columns per lane unless the tunables force another
-// form or (PF_JC=0) the cost model prefers one:
-// 4 columns per lane (packed form only): fewer DPP moves and pair assemblies per pixel and a
-// wider strip per halo; 2 keeps more waves resident.
-// 3 columns per lane (packed form): a 192-column strip, so the 2T-column halo is a smaller
-// share than in the 128-column strips of C = 2 (L.w >= 192 + 2T: jacobi_tcap's bound)
-std::vector<PassPlan> pf::plan_stream(pf_ctx* c, const LevelDims& L, int batch, bool fast, int* C)
-{
-    const JacobiTuning& tune = jacobi_tuning();
-    const bool c4ok = jstream_supported_C(4, fast) && L.w % 4 == 0 && L.w >= 512;
-    const bool c3ok = jstream_supported_C(3, fast) && L.w >= 256;
-    *C = 2;
-    std::vector<PassPlan> plan = plan_level(c, L, 2, jacobi_tcap(L), batch, fast);
-    double cbest = 0;
-    for (const PassPlan& pp : plan) cbest += pp.cost;
-    for (int cc : {3, 4}) {
-        if (!(cc == 3 ? c3ok : c4ok) || (tune.C != 0 && tune.C != cc)) continue;
-        std::vector<PassPlan> pc = plan_level(c, L, cc, jacobi_tcap(L), batch, fast);
-        double cost = 0;
-        for (const PassPlan& pp : pc) cost += pp.cost;
-        if (tune.C == cc || cost < cbest) {
-            *C = cc;
-            cbest = cost;
-            plan.swap(pc);
-        }
-    }
-    return plan;
-}
-
 PassPlan pf::plan_band_pass(pf_ctx* c, const LevelDims& L, int T, int band_rows, bool fast)
 {
-    return best_chunks(T, 2, band_rows, L.w, 1, jstream_waves_per_cu(2, T, fast) / 4,
-                       plan_simds(c));
+    return best_chunks(T, band_rows, L.w, 1, jstream_waves_per_cu(T, fast) / 4, plan_simds(c));
 }
 
 JresPlan pf::jres_plan(pf_ctx* c, const LevelDims& L, int batch, bool fast)
@@ -219,9 +179,10 @@ JresPlan pf::jres_plan(pf_ctx* c, const LevelDims& L, int batch, bool fast)
     if (mode == 0 || !fast || batch < 1) return jp;
     const int rows = jres_region_rows(L.w);  // region rows of one workgroup
     if (rows <= 0 || L.iters < 1) return jp;
-    // resident blocks per CU at widths 256, 512, 1024, for the full and the half-height region
-    static int bpc_w[3][2] = {{-1, -1}, {-1, -1}, {-1, -1}};
-    const int wi = L.w == 256 ? 0 : (L.w == 512 ? 1 : 2);
+    // resident blocks per CU at widths 256 and 512 (jres_region_rows supports no other), for the
+    // full and the half-height region
+    static int bpc_w[2][2] = {{-1, -1}, {-1, -1}};
+    const int wi = L.w == 256 ? 0 : 1;
     const int band = L.h1 - L.h0 + 1;
     // cost in sweep units: the blocks run in ceil(blocks / resident) rounds of residency, each
     // sweep costs one unit (fixed region size), each K-sweep hand-off ~2.5 units (measured
@@ -257,12 +218,6 @@ JresPlan pf::jres_plan(pf_ctx* c, const LevelDims& L, int batch, bool fast)
             const int rounds = (L.iters + K - 1) / K;
             const long long resident = (long long)c->num_cu * bpc;
             const long long waves = ((long long)batch * nb + resident - 1) / resident;
-            // 1024 wide (one workgroup per CU, two waves per SIMD): only where every block of
-            // the launch is resident at once -- the latency-bound one-panorama levels (C5); at
-            // C3's batch its passes are not measured against the streaming engine's
-            // (PF_JRES1024_ANY=1: allow)
-            static const bool any1024 = getenv("PF_JRES1024_ANY") && atoi(getenv("PF_JRES1024_ANY"));
-            if (L.w == 1024 && waves > 1 && !any1024) continue;
             const double cost = (double)waves * (L.iters * sweep + (rounds - 1) * xcost);
             if (cost < best) {
                 best = cost;

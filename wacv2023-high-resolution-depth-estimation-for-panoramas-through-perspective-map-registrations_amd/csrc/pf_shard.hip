@@ -395,7 +395,7 @@ int pf_fuse_band_plan(pf_ctx* c, int out_w, int out_h, float zr0, float zr1, int
         return fail(c, PF_EINVAL, "level %d: the zenith band leaves no room for band passes", level);
     const int band = L->h1 - L->h0 + 1;
     // the sweep depths depend only on (level, nbands): every rank derives the same plan
-    std::vector<PassPlan> plan = plan_level(c, *L, 2, jacobi_tcap(*L), 1, c->lc.full[level],
+    std::vector<PassPlan> plan = plan_level(c, *L, jacobi_tcap(*L), 1, c->lc.full[level],
                                             (band + nbands - 1) / nbands);
     if ((int)plan.size() > cap) return fail(c, PF_EINVAL, "plan of %zu passes > cap %d", plan.size(), cap);
     for (size_t i = 0; i < plan.size(); i++) T[i] = plan[i].T;
@@ -436,12 +436,12 @@ int pf_fuse_band_pass(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
     JacobiPass P = jacobi_pass(c, L, r);
     P.row_lo = row0;
     P.row_hi = row1;
-    set_pass_shape(P, T, 2, row1 - row0, plan_band_pass(c, L, T, row1 - row0, fast).nchunks);
+    set_pass_shape(P, T, row1 - row0, plan_band_pass(c, L, T, row1 - row0, fast).nchunks);
     P.src_mode = src_mode;
     P.src = src;
     P.dst = dst;
     P.out_mode = out ? 1 : 0;
-    launch_jstream(c->stream, P, 2, T, 1, fast);
+    launch_jstream(c->stream, P, T, 1, fast);
     HIPCHK(c, hipGetLastError());
     return PF_OK;
 }
