@@ -137,6 +137,47 @@ int pf_disparity_transform(pf_ctx* ctx, float* data, long long npix, int channel
 int pf_merge_disparity(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, const float* tiles,
                        int batch, int out_w, float zr0, float zr1, float* coeffs, uint16_t* out);
 
+/* ---- post-fusion calibration (no tile layout needed; all pointers are device pointers) ----
+ *
+ * SolveDepthToDepth2 (Depth.cpp:1158-1259): one cubic per panorama from the fused u16 result
+ * data [batch][out_h][out_w] to the baseline emap [batch][eh][ew][ec] (channel 0), on every pixel
+ * of rows h0..h1 (the band of pf_level_info's last level): x = (float)data / 65535.0f,
+ * y = ValueAtCoord of the pixel's spherical coordinate, both clamped to [1e-4, 1 - 1e-4] in fp64.
+ * The reference's Ceres 1.13 Levenberg-Marquardt (DENSE_SCHUR, default options) from (0, 0, 1, 0),
+ * evaluated from 15 fp64 moment sums taken in a fixed order (chunks of 16,384 samples),
+ * so the result is reproducible bit for bit.  The rows must exist (h1 <= out_h - 1).
+ *   coeffs   (optional) [batch][4] floats   abcd = Vec4f(vars) (Depth.cpp:1251)
+ *   coeffs64 (optional) [batch][4] doubles  the unrounded solution
+ *   summary  (optional) [batch][4] doubles  as pf_register_disparity's
+ * apply != 0 then runs pf_result_transform with the fitted coefficients. */
+int pf_register_global(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, uint16_t* data,
+                       int batch, int out_w, int out_h, float zr0, float zr1, int apply,
+                       float* coeffs, double* coeffs64, double* summary);
+
+/* The cubic on the u16 result, in place (an extension: the reference fits abcd with
+ * SolveDepthToDepth2 and leaves the use to the caller).  Rows h0..h1 only: v = (float)d / 65535.0f,
+ * Depth2DepthTransform's map (Depth.cpp:256-271) in fp32, NaN becomes 0, d = (u16)(Y * 65535.0f).
+ * coeffs: DEVICE [batch][4] floats. */
+int pf_result_transform(pf_ctx* ctx, uint16_t* data, int batch, int out_w, int out_h, float zr0,
+                        float zr1, const float* coeffs);
+
+/* MedianScaling (Depth.cpp:637-701): channel 0 of map0 [batch][h0][w0][c0] is scaled by
+ * m1 / m0 (fp32) on its valid pixels, where m0 / m1 are the order statistics at index n / 2 of
+ * the valid values of map0 / map1 (an exact selection: what nth_element leaves there), valid
+ * meaning !(v < 1e-4 || v >= 1 - 1e-4) in double; NaN counts as invalid.
+ *   medians (optional) [batch][2] floats {m0, m1}
+ *   status  (optional) [batch] ints: 0 ok; 1 a map has no valid pixel (the reference indexes an
+ *           empty vector there): medians 0, nothing written */
+int pf_median_scale(pf_ctx* ctx, float* map0, int w0, int h0, int c0, const float* map1, int w1,
+                    int h1, int c1, int batch, float* medians, int* status);
+
+/* EquirectangularMap::CopyInvalidPixels (Depth.cpp:703-725): for every pixel (x, y) of dst
+ * [batch][h][w][c], channel 0 of ref [batch][rh][rw][rc] at X = int((float)x * ((float)rw /
+ * (float)w)), Y likewise, is copied into channel 0 of dst where it is < 1e-4 or >= 1 - 1e-4
+ * (NaN is not copied).  X / Y are clamped to the last column / row. */
+int pf_copy_invalid(pf_ctx* ctx, float* dst, int w, int h, int c, const float* ref, int rw,
+                    int rh, int rc, int batch);
+
 /* E->P depth warp: tile pixel (X,Y) -> ToSphericalCoord(X/(W-1), Y/(H-1)) (Depth.cpp:157-166)
  * -> bilinear sample of pano [batch][ph][pw] at (az/2pi*(pw-1), zen/pi*(ph-1)).  resp
  * ([batch][ntiles], optional) applies the synthetic depth-net response. */

@@ -5,7 +5,7 @@
  * -lpanofuse_depth -lpanofuse; the arithmetic runs in the HIP kernels of libpanofuse.
  *
  * Entry points and the reference interface each one replaces:
- *   EquirectangularMap::{Load, LoadPfm, ValueAtCoord, ValueAtXY, Avg,
+ *   EquirectangularMap::{Load, LoadPfm, ValueAtCoord, ValueAtXY, Avg, CopyInvalidPixels,
  *                        DispDepthConversion, Save8bit}                Depth.h:9-59
  *   PerspectiveMap::{Load, SetWindow, Value, ValueAtXY, ToSphericalCoord, SphericalTo2D,
  *                    Contain, Azimuth/ZenithMin/Max, D2DTransform, Depth2DepthTransform}
@@ -15,12 +15,14 @@
  *   MergeDepthMaps                                                     Depth.h:286-289
  *   SolveDisparityToDepth (declared there, defined here)               Depth.h:293-294
  *   SolveDepthToDepth                                                  Depth.h:297-298
+ *   SolveDepthToDepth2                                                 Depth.h:300-301
  *   SolveDepthAll                                                      Depth.h:306-307
  *   SolveDepthBySmoothing                                              Depth.h:309
  *   ErrorData / ErrorEmap                                              Depth.h:313-316
  *   ErrorCompare                                                       Depth.h:318-319
  *   ErrorLaplacian                                                     Depth.h:321-323
  *   SphericalToWorld / WorldToSpherical                                Depth.h:326-329
+ *   MedianScaling                                                      Depth.h:337
  *   Save16BitPNG                                                       Depth.cpp:27-32
  *   g_zenith_range                                                     Depth.cpp:22
  *
@@ -33,12 +35,11 @@
  * SphericalToWorld, WorldToSpherical) are host fp32 code with the reference's Imath semantics
  * and glibc calls (csrc/pf_geom.hpp), bit-identical to it; the per-pixel path runs on the GPU.
  *
- * Extension (not in the reference): MergeDisparityMaps, MergeDepthMaps for disparity tiles.
+ * Extensions (not in the reference): MergeDisparityMaps, MergeDepthMaps for disparity tiles;
+ * TransformResult, the cubic of SolveDepthToDepth2 applied to the u16 result.
  *
- * Not provided: SolveDepthToDepth2 (never called), a SolveDisparityToDepth over several active
- * maps (a joint nonlinear solve), MedianScaling and EquirectangularMap::CopyInvalidPixels
- * (nothing in the reference calls them), the triangulation/subdivision members (vertices, faces,
- * subd_*: never used on the path).
+ * Not provided: a SolveDisparityToDepth over several active maps (a joint nonlinear solve), the
+ * triangulation/subdivision members (vertices, faces, subd_*: never used on the path).
  */
 #pragma once
 
@@ -184,6 +185,10 @@ public:
     float ValueAtCoord(float azimuth, float zenith);
     float ValueAtXY(int x, int y);
     double Avg();
+    /* mark invalid pixels from a reference emap (Depth.h:52, Depth.cpp:703-725), on the GPU
+     * (pf_copy_invalid): channel 0 of ref_emap at (int((float)x * ratio_x), int((float)y *
+     * ratio_y)) is copied into channel 0 of this map where it is < 1e-4 or >= 1 - 1e-4 */
+    void CopyInvalidPixels(EquirectangularMap& ref_emap);
     /* disparity <-> depth (Depth.cpp:587-610) on the GPU (pf_disp_depth_convert): channel 0 becomes
      * 1 / v where (double)fabsf(v) >= 1e-5 -- once per channel of the map, as the reference's loop
      * over the channels converts channel 0 each time */
@@ -271,6 +276,19 @@ bool SolveDisparityToDepth(EquirectangularMap& emap, std::vector<PerspectiveMap>
 bool SolveDepthToDepth(EquirectangularMap& emap, std::vector<PerspectiveMap>& pmaps,
                        std::vector<bool>& pmaps_actives, Vec2f& zenith_range, Vec4f& abcd);
 
+/* Depth.h:300-301, Depth.cpp:1158-1259: the final global registration of a fused u16 result
+ * (data [height][width]) to the baseline emap: one cubic fitted on every pixel of the band rows by
+ * the reference's LM from (0, 0, 1, 0), on the GPU (pf_register_global).  Prints the reference's
+ * "[SolveDepthToDepth2] abcd:(a b c d) cost:<initial>-><final>" line.  data is not modified. */
+bool SolveDepthToDepth2(EquirectangularMap& emap, unsigned short* data, int width, int height,
+                        Vec2f& zenith_range, Vec4f& abcd);
+/* EXTENSION (not in the reference, which leaves the use of SolveDepthToDepth2's abcd to the
+ * caller): Depth2DepthTransform's cubic on the band rows of the u16 result, in place, on the GPU
+ * (pf_result_transform): v = (float)d / 65535.0f, Y clamped to 0-1, NaN becomes 0,
+ * d = (unsigned short)(Y * 65535.0f); the other rows are left untouched. */
+bool TransformResult(unsigned short* data, int width, int height, Vec2f& zenith_range,
+                     Vec4f& abcd);
+
 bool SolveDepthAll(EquirectangularMap& emap, std::vector<PerspectiveMap>& pmaps,
                    unsigned short* data, int& out_width, int& out_height, Vec2f& zenith_range,
                    const char* Laplacian_filename = nullptr);
@@ -341,6 +359,15 @@ Vec3f SphericalToWorld(float azimuth, float zenith);
 /* 3d position to spherical coord.; p is normalized in place (Depth.cpp:2960-2971) */
 Vec2f WorldToSpherical(Vec3f& p);
 
+/* median scaling emap0 toward emap1 (Depth.h:337, Depth.cpp:637-701), on the GPU
+ * (pf_median_scale): channel 0 of emap0 is multiplied by median1 / median0 on its valid pixels
+ * (!(v < 1e-4 || v >= 1 - 1e-4)); the medians are the order statistics at index n / 2 of the
+ * valid values.  Where the reference's behaviour is undefined, this is the rule: NaN counts as
+ * invalid, and a map without any valid pixel returns false after the reference's
+ * "MedianScaling: zero val0_median ??" line, before any GPU call, with nothing written. */
+bool MedianScaling(EquirectangularMap& emap0, EquirectangularMap& emap1,
+                   float* emap0_median = nullptr, float* emap1_median = nullptr);
+
 }  // namespace DepthNamespace
 
 /* The mode-0 driver (Main.cpp:331-687 CreateDepthPanoramas) over std::filesystem; tile_ext is
@@ -348,6 +375,9 @@ Vec2f WorldToSpherical(Vec3f& p);
  * layout of Main.cpp:788-843 is used.  With PF_TILE_MODEL=disparity in the environment
  * (panofuse_main --tile-model disparity) the tiles are disparities: MergeDisparityMaps.  shard / nshards: this process takes the panoramas
  * shard, shard + nshards, ... of the sorted folder (one process per GPU, no communication).
+ * With PF_GLOBAL_ALIGN=1 in the environment (panofuse_main --global-align) MergeDepthMaps and
+ * MergeDisparityMaps run SolveDepthToDepth2 and TransformResult's cubic on the fused result before
+ * it is written and scored.
  * With PF_EDGE_METRICS=1 in the environment (panofuse_main --edge-metrics) each panorama also
  * gets <raw>.edges.txt: ErrorLaplacian of the result and of the baseline against the gt.
  * Returns the process exit code. */

@@ -64,9 +64,11 @@ def make_pair(rng, gshape, vshape):
     return g16, v16
 
 
-def build_harness(ref, d, harness=None):
+def build_harness(ref, d, harness=None, with_ceres=False):
     """Compile the reference's Depth.cpp with a harness (tools/edge_ref_harness.cpp unless another
-    path is given) into d; returns the executable."""
+    path is given) into d; returns the executable.  with_ceres: also build the configured Ceres
+    tree (ninja, at most 16 jobs; about a minute) and link its archive, for a harness that
+    reaches the solver calls."""
     harness = harness or os.path.join(ROOT, "tools", "edge_ref_harness.cpp")
     shim = os.path.join(d, "shim")
     os.makedirs(os.path.join(shim, "opencv2"))
@@ -77,7 +79,15 @@ def build_harness(ref, d, harness=None):
                     "-DCMAKE_BUILD_TYPE=Release", "-DCMAKE_POLICY_VERSION_MINIMUM=3.5",
                     "-DEIGEN_INCLUDE_DIR=" + os.path.join(ref, "eigen"), "-DCXSPARSE=OFF",
                     "-DLAPACK=OFF", "-DSUITESPARSE=OFF", "-DMINIGLOG=ON", "-DGFLAGS=OFF",
-                    "-DBUILD_TESTING=OFF"], check=True, stdout=subprocess.DEVNULL)
+                    "-DBUILD_TESTING=OFF"] +
+                   (["-DCMAKE_CXX_FLAGS=-DERROR=ERROR_ -w"] if with_ceres else []),
+                   check=True, stdout=subprocess.DEVNULL)
+    libs = []
+    if with_ceres:
+        jobs = str(min(16, os.cpu_count() or 1))
+        subprocess.run(["ninja", "-C", ceres, "-j", jobs], check=True, stdout=subprocess.DEVNULL)
+        libs = sorted(os.path.join(ceres, "lib", f) for f in os.listdir(os.path.join(ceres, "lib"))
+                      if f.endswith(".a"))
     exe = os.path.join(d, os.path.splitext(os.path.basename(harness))[0])
     inc = [shim, ref, os.path.join(ref, "ilmbase22", "include"),
            os.path.join(ref, "ceres-solver", "include"), os.path.join(ceres, "config"),
@@ -85,7 +95,8 @@ def build_harness(ref, d, harness=None):
            os.path.join(ref, "eigen")]
     subprocess.run(["g++", "-std=c++14", "-O2", "-fopenmp", "-w", "-DERROR=ERROR_",
                     "-ffunction-sections", "-fdata-sections"] + ["-I" + i for i in inc] +
-                   [harness, os.path.join(ref, "Depth.cpp"), "-Wl,--gc-sections", "-o", exe],
+                   [harness, os.path.join(ref, "Depth.cpp")] + libs +
+                   ["-Wl,--gc-sections", "-o", exe],
                    check=True)
     return exe
 

@@ -1,6 +1,6 @@
 // pf_ctx.hpp -- private to the host units of libpanofuse (pf_ctx.hip, pf_layout.hip, pf_plan.hip,
-// pf_fuse.hip, pf_shard.hip, pf_warp_api.hip, pf_smooth_api.hip, pf_eval.hip, pf_disp_api.hip):
-// the context struct
+// pf_fuse.hip, pf_shard.hip, pf_warp_api.hip, pf_smooth_api.hip, pf_eval.hip, pf_disp_api.hip,
+// pf_global_api.hip): the context struct
 // behind the C-ABI's opaque pf_ctx, the error / allocation / upload helpers, the argument-check
 // prologues the entry points share, and the few functions that cross those units.  No kernel unit
 // includes it.
@@ -93,6 +93,10 @@ struct pf_ctx {
     // workspace
     pf::DevBuf buf[3], lnorm, coeffs, lsum_ws, metrics_ws, reg_sums, reg_active;
     pf::DevBuf disp_tiles;  // pf_merge_disparity: the transformed copy of the caller's tiles
+    // pf_register_global: ValueAtCoord's column / row terms for one (result size, baseline size)
+    // key, the chunk partials with the coefficients after them; pf_median_scale: bins and states
+    pf::DevBuf glob_ecol, glob_erow, glob_ws, med_ws;
+    int glob_key[5] = {0, 0, 0, 0, 0};
     // pf_error_compare: the fit's and the final call's pf_metrics, the min / max cells, the gt
     // disparity plane and (when the caller passes none) the depth plane; apart from metrics_ws,
     // which the two inner pf_error_metrics calls size for themselves

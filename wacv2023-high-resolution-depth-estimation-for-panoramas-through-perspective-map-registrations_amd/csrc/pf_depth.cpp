@@ -293,6 +293,22 @@ double EquirectangularMap::Avg()  // Depth.cpp:563-583
     return avg;
 }
 
+void EquirectangularMap::CopyInvalidPixels(EquirectangularMap& ref)  // Depth.cpp:703-725
+{
+    pf_ctx* c = facade_ctx();
+    if (!c || !data || !ref.data) return;
+    const size_t n = (size_t)width * height * channels;
+    const size_t nr = (size_t)ref.width * ref.height * ref.channels;
+    DevMem dd(n * 4), dr(nr * 4);
+    if (!upload(dd, data, n) || !upload(dr, ref.data, nr)) return;
+    if (!pf_ok(c, pf_copy_invalid(c, dd.as<float>(), width, height, channels, dr.as<float>(),
+                                  ref.width, ref.height, ref.channels, 1),
+               "pf_copy_invalid") ||
+        !pf_ok(c, pf_synchronize(c), "pf_synchronize"))
+        return;
+    hip_ok(hipMemcpy(data, dd.p, n * 4, hipMemcpyDeviceToHost), "download");
+}
+
 void EquirectangularMap::DispDepthConversion()  // Depth.cpp:587-610
 {
     pf_ctx* c = facade_ctx();
@@ -587,6 +603,105 @@ bool SolveDisparityToDepth(EquirectangularMap& emap, std::vector<PerspectiveMap>
     return true;
 }
 
+namespace {
+// "[SolveDepthToDepth2] abcd:(a b c d) cost:i->f" (Depth.cpp:1256: Imath's operator<< of a Vec4f)
+void print_global_fit(const float k[4], const double sm[4])
+{
+    std::cout << "[SolveDepthToDepth2] abcd:(" << k[0] << " " << k[1] << " " << k[2] << " " << k[3]
+              << ") cost:" << sm[0] << "->" << sm[1] << std::endl;
+}
+
+// pf_register_global on a device result (apply: the transform as well); prints the fit's line.
+bool global_fit(pf_ctx* c, const float* d_emap, const EquirectangularMap& emap, uint16_t* d_data,
+                int w, int h, Vec2f& zr, bool apply, Vec4f& abcd)
+{
+    DevMem dc(4 * sizeof(float)), ds(4 * sizeof(double));
+    if (!dc.ok || !ds.ok) return false;
+    if (!pf_ok(c, pf_register_global(c, d_emap, emap.width, emap.height, emap.channels, d_data, 1,
+                                     w, h, zr[0], zr[1], apply ? 1 : 0, dc.as<float>(), nullptr,
+                                     ds.as<double>()),
+               "pf_register_global") ||
+        !pf_ok(c, pf_synchronize(c), "pf_synchronize"))
+        return false;
+    float k[4];
+    double sm[4];
+    if (!hip_ok(hipMemcpy(k, dc.p, sizeof(k), hipMemcpyDeviceToHost), "download") ||
+        !hip_ok(hipMemcpy(sm, ds.p, sizeof(sm), hipMemcpyDeviceToHost), "download"))
+        return false;
+    abcd = Vec4f(k[0], k[1], k[2], k[3]);
+    print_global_fit(k, sm);
+    return true;
+}
+}  // namespace
+
+bool SolveDepthToDepth2(EquirectangularMap& emap, unsigned short* data, int width, int height,
+                        Vec2f& zr, Vec4f& abcd)  // Depth.cpp:1158-1259
+{
+    pf_ctx* c = facade_ctx();
+    if (!c || !emap.data || !data || width < 1 || height < 1) return false;
+    const size_t ne = (size_t)emap.width * emap.height * emap.channels;
+    const size_t no = (size_t)width * height;
+    DevMem de(ne * 4), dd(no * 2);
+    if (!upload(de, emap.data, ne) || !upload(dd, data, no)) return false;
+    return global_fit(c, de.as<float>(), emap, dd.as<uint16_t>(), width, height, zr, false, abcd);
+}
+
+bool TransformResult(unsigned short* data, int width, int height, Vec2f& zr, Vec4f& abcd)
+{
+    pf_ctx* c = facade_ctx();
+    if (!c || !data || width < 1 || height < 1) return false;
+    const size_t no = (size_t)width * height;
+    const float k[4] = {abcd[0], abcd[1], abcd[2], abcd[3]};
+    DevMem dd(no * 2), dc(sizeof(k));
+    if (!upload(dd, data, no) || !upload(dc, k, 4)) return false;
+    if (!pf_ok(c, pf_result_transform(c, dd.as<uint16_t>(), 1, width, height, zr[0], zr[1],
+                                      dc.as<float>()),
+               "pf_result_transform") ||
+        !pf_ok(c, pf_synchronize(c), "pf_synchronize"))
+        return false;
+    return hip_ok(hipMemcpy(data, dd.p, no * 2, hipMemcpyDeviceToHost), "download");
+}
+
+bool MedianScaling(EquirectangularMap& emap0, EquirectangularMap& emap1, float* emap0_median,
+                   float* emap1_median)  // Depth.cpp:637-701
+{
+    auto any_valid = [](const EquirectangularMap& m) {
+        if (!m.data) return false;
+        const size_t n = (size_t)m.width * m.height;
+        for (size_t i = 0; i < n; ++i) {
+            const float v = m.data[i * m.channels];
+            if (!(v < 1e-4 || v >= 1 - 1e-4) && v == v) return true;
+        }
+        return false;
+    };
+    if (!any_valid(emap0) || !any_valid(emap1)) {  // the reference indexes an empty vector here
+        std::cout << "MedianScaling: zero val0_median ??" << std::endl;
+        return false;
+    }
+    pf_ctx* c = facade_ctx();
+    if (!c) return false;
+    const size_t n0 = (size_t)emap0.width * emap0.height * emap0.channels;
+    const size_t n1 = (size_t)emap1.width * emap1.height * emap1.channels;
+    DevMem d0(n0 * 4), d1(n1 * 4), dm(2 * sizeof(float)), dst(sizeof(int));
+    if (!upload(d0, emap0.data, n0) || !upload(d1, emap1.data, n1) || !dm.ok || !dst.ok)
+        return false;
+    if (!pf_ok(c, pf_median_scale(c, d0.as<float>(), emap0.width, emap0.height, emap0.channels,
+                                  d1.as<float>(), emap1.width, emap1.height, emap1.channels, 1,
+                                  dm.as<float>(), dst.as<int>()),
+               "pf_median_scale") ||
+        !pf_ok(c, pf_synchronize(c), "pf_synchronize"))
+        return false;
+    float med[2];
+    int status = 0;
+    if (!hip_ok(hipMemcpy(med, dm.p, sizeof(med), hipMemcpyDeviceToHost), "download") ||
+        !hip_ok(hipMemcpy(&status, dst.p, sizeof(status), hipMemcpyDeviceToHost), "download") ||
+        status != 0)
+        return false;
+    if (emap0_median) *emap0_median = med[0];
+    if (emap1_median) *emap1_median = med[1];
+    return hip_ok(hipMemcpy(emap0.data, d0.p, n0 * 4, hipMemcpyDeviceToHost), "download");
+}
+
 bool SolveDepthAll(EquirectangularMap& emap, std::vector<PerspectiveMap>& pmaps,
                    unsigned short* data, int& out_width, int& out_height, Vec2f& zr,
                    const char* Laplacian_filename)
@@ -878,6 +993,15 @@ static bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns,
         !pf_ok(c, pf_synchronize(c), "pf_synchronize"))
         return false;
     if (time_Laplacian) *time_Laplacian = elapsed_ms(t);
+    // PF_GLOBAL_ALIGN=1 (panofuse_main --global-align): the fused result is pulled back onto the
+    // baseline by SolveDepthToDepth2's cubic before it is written and scored
+    const char* ga = std::getenv("PF_GLOBAL_ALIGN");
+    if (ga && std::strcmp(ga, "1") == 0) {
+        Vec4f g;
+        if (!global_fit(c, de.as<float>(), emap, dout.as<uint16_t>(), out_width, out_height, zr,
+                        true, g))
+            return false;
+    }
     std::vector<unsigned short> data(no);
     if (!hip_ok(hipMemcpy(data.data(), dout.p, no * 2, hipMemcpyDeviceToHost), "download"))
         return false;

@@ -368,6 +368,26 @@ void launch_register_disp(hipStream_t s, const TileGeom* geom, const RegGrid* gr
 void launch_apply_disp(hipStream_t s, const TileGeom* geom, int ntiles, long long tile_pixels,
                        float* tiles, long long tstride, const float* coeffs, int batch);
 void launch_disp_map(hipStream_t s, float* data, long long npx, int c, const float* abcd);
+// Global result-to-baseline fit (pf_global.hip, SolveDepthToDepth2): per (panorama, chunk of
+// kGlobalChunk consecutive band samples) the 15 moment sums to partials [batch][nchunks][15];
+// ecol / erow: ValueAtCoord's column term per X and row term per Y (element offsets).  Then the
+// chunk partials added in chunk order and the LM from (0, 0, 1, 0) (k_global_solve,
+// pf_kernels.hip); summary as launch_register_disp's, [batch][4].
+static constexpr int kGlobalChunk = 16384;
+void launch_global_sums(hipStream_t s, const uint16_t* data, long long dstride, const float* emap,
+                        long long estride, const int* ecol, const int* erow, int w, int h0,
+                        int ns, int nchunks, double* partials, int batch);
+void launch_global_solve(hipStream_t s, const double* partials, int nchunks, int batch,
+                         float* coeffs, double* coeffs64, double* summary);
+// the cubic of coeffs [batch][4] (device) on u16 values [first, first + n) of every panorama
+void launch_result_transform(hipStream_t s, uint16_t* data, long long dstride, long long first,
+                             int n, const float* coeffs, int batch);
+// MedianScaling / CopyInvalidPixels (pf_global.hip)
+size_t median_workspace_bytes(int batch);
+void launch_median_scale(hipStream_t s, float* map0, int w0, int h0, int c0, const float* map1,
+                         int w1, int h1, int c1, int batch, void* ws, float* medians, int* status);
+void launch_copy_invalid(hipStream_t s, float* dst, int w, int h, int c, const float* ref, int rw,
+                         int rh, int rc, int batch);
 int warp_patch_edge();
 int warp_patch_height();
 // host tables (pf_warp.hip): wxy/wfxy of one tile's pixels; the RGB taps of one tile

@@ -337,12 +337,14 @@ __device__ int solve_normal(const double* S, int degree, double* coef)
 
 // ---------------------------------------------------------------------------------------------
 // The reference's registration solver: Ceres 1.13 trust-region Levenberg-Marquardt, DENSE_SCHUR,
-// default options, from (1,1,1,1) (Depth.cpp:1270-1274, 1399-1404), evaluated from the 15 moment
+// default options, from `start` ((1,1,1,1) for SolveDepthToDepth, Depth.cpp:1270-1274, 1399-1404;
+// (0,0,1,0) for SolveDepthToDepth2, Depth.cpp:1169-1173), evaluated from the 15 moment
 // sums -- the residuals are linear in (a,b,c,d), so cost, gradient and J'J are exact functions of
 // them.  Every rule (Jacobi column scaling, LM diagonal and radius updates, step validity and
 // quality, the parameter/function/gradient tolerances, returning the best accepted point) is
 // cited in oracle/pf_oracle_lm.c, whose pfo_lm_moments is this function operation for operation
-// (fp64 +, -, *, /, sqrt only, no contraction), so the two agree bit for bit.
+// (fp64 +, -, *, /, sqrt only, no contraction), so the two agree bit for bit.  summary (optional):
+// {initial cost, final cost, iterations, termination} in pf_register_disparity's encoding.
 namespace {
 constexpr int kLmMaxIter = 50;
 constexpr double kLmInitRadius = 1e4, kLmMaxRadius = 1e16, kLmMinRadius = 1e-32;
@@ -418,7 +420,8 @@ __device__ double norm4(const double v[4])
 }
 }  // namespace
 
-__device__ void lm_moments(const double* S, double coef[4])
+__device__ void lm_moments(const double* S, const double start[4], double coef[4],
+                           double* summary = nullptr)
 {
     Mom m;
     const int idx[4][4] = {{0, 1, 2, 3}, {1, 4, 5, 6}, {2, 5, 7, 8}, {3, 6, 8, 9}};
@@ -427,16 +430,18 @@ __device__ void lm_moments(const double* S, double coef[4])
         m.Jy[i] = S[10 + i];
     }
     m.yy = S[14];
-    double x[4] = {1.0, 1.0, 1.0, 1.0}, best[4] = {1.0, 1.0, 1.0, 1.0};
+    double x[4] = {start[0], start[1], start[2], start[3]};
+    double best[4] = {start[0], start[1], start[2], start[3]};
     double sc[4], Ms[4][4], g[4], gs[4], diag[4] = {0, 0, 0, 0}, D[4], step[4], cand[4];
     for (int k = 0; k < 4; k++) sc[k] = 1.0 / (1.0 + sqrt(m.M[k][k]));
     for (int i = 0; i < 4; i++)
         for (int j = 0; j < 4; j++) Ms[i][j] = (m.M[i][j] * sc[i]) * sc[j];
     double radius = kLmInitRadius, decrease = 2.0, x_norm = -1.0;
     bool reuse_diag = false, successful = true;
-    int invalid_run = 0, iteration = 0;
+    int invalid_run = 0, iteration = 0, term = 0;
     double x_cost = mom_cost(m, x);
     mom_gradient(m, x, g);
+    const double initial_cost = x_cost;
     double min_cost = DBL_MAX;
     for (;;) {
         if (successful && x_cost < min_cost) {
@@ -450,9 +455,9 @@ __device__ void lm_moments(const double* S, double coef[4])
                 const double d = fabs(x[k] - (x[k] + -g[k]));
                 if (d > gmax) gmax = d;
             }
-            if (gmax <= kLmGradTol) break;
+            if (gmax <= kLmGradTol) { term = 3; break; }
         }
-        if (radius <= kLmMinRadius) break;
+        if (radius <= kLmMinRadius) { term = 4; break; }
         iteration++;
         if (!reuse_diag)
             for (int k = 0; k < 4; k++) {
@@ -497,7 +502,7 @@ __device__ void lm_moments(const double* S, double coef[4])
             valid = mcc > 0.0;
         }
         if (!valid) {
-            if (++invalid_run >= kLmMaxInvalid) break;
+            if (++invalid_run >= kLmMaxInvalid) { term = 5; break; }
             radius = radius / decrease;
             decrease *= 2.0;
             successful = false;
@@ -509,8 +514,8 @@ __device__ void lm_moments(const double* S, double coef[4])
         if (!isfinite(cand_cost)) cand_cost = DBL_MAX;
         double dx[4];
         for (int k = 0; k < 4; k++) dx[k] = x[k] - cand[k];
-        if (norm4(dx) <= kLmParamTol * (x_norm + kLmParamTol)) break;
-        if (fabs(x_cost - cand_cost) <= kLmFuncTol * x_cost) break;
+        if (norm4(dx) <= kLmParamTol * (x_norm + kLmParamTol)) { term = 2; break; }
+        if (fabs(x_cost - cand_cost) <= kLmFuncTol * x_cost) { term = 1; break; }
         const double rel = (x_cost - cand_cost) / mcc;
         if (rel > kLmMinRelDecrease) {
             for (int k = 0; k < 4; k++) x[k] = cand[k];
@@ -531,6 +536,12 @@ __device__ void lm_moments(const double* S, double coef[4])
         }
     }
     for (int k = 0; k < 4; k++) coef[k] = best[k];
+    if (summary) {
+        summary[0] = initial_cost;
+        summary[1] = min_cost;
+        summary[2] = (double)iteration;
+        summary[3] = (double)term;
+    }
 }
 
 // Degree-d least squares from the normal-equation sums (falling back to lower degrees when the
@@ -539,8 +550,9 @@ __device__ void solve_store(const double* S, int degree, int solver, float* coef
                             double* coeffs64, long long o)
 {
     if (solver == PF_SOLVER_LM && degree == 3) {
+        const double ones[4] = {1.0, 1.0, 1.0, 1.0};
         double c[4];
-        lm_moments(S, c);
+        lm_moments(S, ones, c);
         for (int i = 0; i < 4; i++) {
             if (coeffs) coeffs[o + i] = (float)c[i];  // Vec4f(vars), Depth.cpp:1408
             if (coeffs64) coeffs64[o + i] = c[i];
@@ -924,6 +936,53 @@ void launch_regidx(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
 }
 
 int register_sums_per_tile() { return kRegSums; }
+
+// SolveDepthToDepth2's solve (Depth.cpp:1158-1259): per panorama, the chunk partials of
+// k_global_sums (pf_global.hip) added in chunk order from 0.0, then the LM from (0, 0, 1, 0).
+// One wave per panorama: lane k < 15 adds sum k over the chunks (eight loads in flight, added in
+// chunk order), lane 0 solves.
+__global__ void __launch_bounds__(64) k_global_solve(const double* __restrict__ partials,
+                                                     int nchunks, int batch,
+                                                     float* __restrict__ coeffs,
+                                                     double* __restrict__ coeffs64,
+                                                     double* __restrict__ summary)
+{
+    __shared__ double Ssh[kRegSums];
+    const int b = blockIdx.x, k = threadIdx.x;
+    if (k < kRegSums) {
+        const double* p = partials + (long long)b * nchunks * kRegSums + k;
+        double acc = 0.0;
+        for (int c0 = 0; c0 < nchunks; c0 += 8) {
+            double v[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++)
+                v[u] = c0 + u < nchunks ? p[(long long)(c0 + u) * kRegSums] : 0.0;
+#pragma unroll
+            for (int u = 0; u < 8; u++)
+                if (c0 + u < nchunks) acc = acc + v[u];
+        }
+        Ssh[k] = acc;
+    }
+    __syncthreads();
+    if (k != 0) return;
+    double S[kRegSums];
+    for (int i = 0; i < kRegSums; i++) S[i] = Ssh[i];
+    const double start[4] = {0.0, 0.0, 1.0, 0.0};
+    double c[4], sm[4];
+    lm_moments(S, start, c, sm);
+    for (int i = 0; i < 4; i++) {
+        if (coeffs) coeffs[(long long)b * 4 + i] = (float)c[i];  // Vec4f(vars), Depth.cpp:1251
+        if (coeffs64) coeffs64[(long long)b * 4 + i] = c[i];
+        if (summary) summary[(long long)b * 4 + i] = sm[i];
+    }
+}
+
+void launch_global_solve(hipStream_t s, const double* partials, int nchunks, int batch,
+                         float* coeffs, double* coeffs64, double* summary)
+{
+    hipLaunchKernelGGL(k_global_solve, dim3((unsigned)batch), dim3(64), 0, s, partials, nchunks,
+                       batch, coeffs, coeffs64, summary);
+}
 
 void launch_register_joint(hipStream_t s, const double* sums, const int* active, int ntiles,
                            int batch, int degree, int solver, float* coeffs, double* coeffs64)

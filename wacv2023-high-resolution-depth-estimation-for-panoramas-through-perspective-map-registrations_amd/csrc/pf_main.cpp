@@ -2,7 +2,7 @@
 //   panofuse_main 0 <rgb_dir> <gt_dir> <baseline_dir> <result_dir> [--tiles DIR]
 //                 [--ext auto|jpg|png] [--width W] [--device D] [--shard R/N]
 //                 [--metrics-order tree|sequential] [--edge-metrics]
-//                 [--tile-model depth|disparity]
+//                 [--tile-model depth|disparity] [--global-align]
 //   panofuse_main export <rgb_dir> <tile_dir> [--device D]
 //   panofuse_main lap <gt_file> <given_file> [--device D]
 //   panofuse_main cmp <gt_file> <given_file> [--disp] [--align 0|1|2] [--no-cap] [--save FILE]
@@ -26,6 +26,9 @@
 // registration) or disparity (MiDaS / DPT tiles, relative inverse depth in 0-1: each is fitted
 // with y = 1/(a x + b) + d and mapped to depth by D2DTransform).  The reference's MiDaS folder
 // convention (Main.cpp:577-579) is `--tiles output --ext png`.
+// --global-align (opt-in, takes no value): after the fusion the u16 result is registered to the
+// baseline with SolveDepthToDepth2's cubic (Depth.cpp:1158-1259) and transformed, before it is
+// written and scored; prints the "[SolveDepthToDepth2] ..." line per panorama.
 // --edge-metrics (opt-in, takes no value): also write <raw>.edges.txt per panorama, the
 // ErrorLaplacian values of the result and of the baseline against the gt.
 #include "../../include/pf_depth.h"
@@ -45,7 +48,7 @@ int main(int argc, char* argv[])
                   << " 0 <rgb_dir> <gt_dir> <baseline_dir> <result_dir> [--tiles DIR]"
                      " [--ext auto|jpg|png] [--width W] [--device D] [--shard R/N]"
                      " [--metrics-order tree|sequential] [--edge-metrics]"
-                     " [--tile-model depth|disparity]\n"
+                     " [--tile-model depth|disparity] [--global-align]\n"
                      "         (MiDaS disparity tiles, the reference's folder convention:"
                      " --tile-model disparity --tiles output --ext png)\n       "
                   << argv[0] << " export <rgb_dir> <tile_dir> [--device D]\n       "
@@ -186,6 +189,11 @@ int main(int argc, char* argv[])
         const std::string k(argv[i]);
         if (k == "--edge-metrics") {  // a flag without a value
             setenv("PF_EDGE_METRICS", "1", 1);  // read by pf_create_depth_panoramas
+            --i;
+            continue;
+        }
+        if (k == "--global-align") {  // a flag without a value
+            setenv("PF_GLOBAL_ALIGN", "1", 1);  // read by MergeDepthMaps / MergeDisparityMaps
             --i;
             continue;
         }

@@ -34,7 +34,8 @@ EXPORTS = [
     "pf_fuse_tile_rows", "pf_rows_add", "pf_fuse_level", "pf_fuse_targets",
     "pf_rows_add_batch", "pf_set_jacobi_share", "pf_error_laplacian",
     "pf_error_compare", "pf_disp_depth_convert", "pf_register_disparity",
-    "pf_disparity_transform", "pf_merge_disparity",
+    "pf_disparity_transform", "pf_merge_disparity", "pf_register_global",
+    "pf_result_transform", "pf_median_scale", "pf_copy_invalid",
 ]
 NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
           "pf_debug_smooth_fault", "pf_fuse_partial_rows", "pf_fuse_coverage_rows",
@@ -108,6 +109,10 @@ def load():
     L.pf_register_disparity.argtypes = [vp, vp, ip, ip, ip, vp, ip, fp, fp, ip, vp, vp, vp]
     L.pf_disparity_transform.argtypes = [vp, vp, C.c_longlong, ip, C.POINTER(C.c_float)]
     L.pf_merge_disparity.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, fp, fp, vp, vp]
+    L.pf_register_global.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, ip, fp, fp, ip, vp, vp, vp]
+    L.pf_result_transform.argtypes = [vp, vp, ip, ip, ip, fp, fp, vp]
+    L.pf_median_scale.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, ip, ip, vp, vp]
+    L.pf_copy_invalid.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, ip, ip]
     L.pf_set_solver.argtypes = [vp, ip]
     L.pf_fuse_normalize.argtypes = [vp, vp, vp, ip, ip, fp, fp, ip, vp]
     L.pf_fuse_multicover.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, ip, vp,
@@ -292,6 +297,43 @@ class Fuser:
         self._check(self.L.pf_merge_disparity(self.h, _ptr(emap), ew, eh, ec, _ptr(tiles), B, ow,
                                               float(zr[0]), float(zr[1]), _ptr(coeffs),
                                               _ptr(out)))
+
+    def register_global(self, emap, data, zr, apply=False, coeffs=None, coeffs64=None,
+                        summary=None):
+        """SolveDepthToDepth2 (pf_register_global): one cubic per panorama from the fused result
+        data (int16 / uint16 [B, H, W], read as u16) to the baseline emap, by the reference's LM
+        from (0, 0, 1, 0).  coeffs: float32 [B, 4], coeffs64 / summary: float64 [B, 4] device
+        tensors (summary = initial cost, final cost, iterations, termination code); apply runs
+        result_transform with the fitted coefficients.  Needs no tile layout.  No sync."""
+        ew, eh, ec = _emap_dims(emap)
+        B, oh, ow = data.shape
+        self._check(self.L.pf_register_global(self.h, _ptr(emap), ew, eh, ec, _ptr(data), B, ow,
+                                              oh, float(zr[0]), float(zr[1]), 1 if apply else 0,
+                                              _ptr(coeffs), _ptr(coeffs64), _ptr(summary)))
+
+    def result_transform(self, data, zr, coeffs):
+        """The cubic of coeffs (float32 [B, 4] device tensor) on rows h0..h1 of the u16 result
+        data [B, H, W], in place (pf_result_transform).  No sync."""
+        B, oh, ow = data.shape
+        self._check(self.L.pf_result_transform(self.h, _ptr(data), B, ow, oh, float(zr[0]),
+                                               float(zr[1]), _ptr(coeffs)))
+
+    def median_scale(self, map0, map1, medians=None, status=None):
+        """MedianScaling (pf_median_scale): channel 0 of map0 (float32 [B, h, w] or [B, h, w, c])
+        is scaled in place toward map1's median.  medians: float32 [B, 2], status: int32 [B]
+        device tensors (1: a map without any valid pixel, nothing written).  No sync."""
+        w0, h0, c0 = _emap_dims(map0)
+        w1, h1, c1 = _emap_dims(map1)
+        self._check(self.L.pf_median_scale(self.h, _ptr(map0), w0, h0, c0, _ptr(map1), w1, h1, c1,
+                                           map0.shape[0], _ptr(medians), _ptr(status)))
+
+    def copy_invalid(self, dst, ref):
+        """EquirectangularMap::CopyInvalidPixels (pf_copy_invalid): ref's invalid pixels
+        (channel 0 < 1e-4 or >= 1 - 1e-4) are copied into channel 0 of dst, in place.  No sync."""
+        w, h, c = _emap_dims(dst)
+        rw, rh, rc = _emap_dims(ref)
+        self._check(self.L.pf_copy_invalid(self.h, _ptr(dst), w, h, c, _ptr(ref), rw, rh, rc,
+                                           dst.shape[0]))
 
     def set_metrics_order(self, order):
         """"tree" (the context's default): fp64 partial sums (fast, means within 1e-5 of exact
