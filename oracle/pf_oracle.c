@@ -573,6 +573,12 @@ int pfo_solve_depth_all(const float* emap, int ew, int eh, int ec, const pfo_til
     pfo_level L;
     pfo_level_dims(out_w, out_h, zr0, zr1, 0, &L);
     int max_level = L.max_level;
+    /* The band of every level keeps a row clear of each pole (the sweeps read row Y-1 and Y+1 of
+     * every band row) and has an interior: refused before any buffer exists. */
+    for (int level = 0; level < max_level; level++) {
+        pfo_level_dims(out_w, out_h, zr0, zr1, level, &L);
+        if (L.h0 < 1 || L.h1 > L.h - 2 || L.h0 >= L.h1) return PFO_EBAND;
+    }
     float* prev = NULL;
     long long oops_all = 0;
     for (int level = 0; level < max_level; level++) {

@@ -143,7 +143,10 @@ void pfo_normalize(const float* Lsum, const int32_t* n, const pfo_level* L, floa
 /* Damped Jacobi sweeps (Depth.cpp:1649-1718); Lnorm with the marker for un-windowed pixels. */
 void pfo_jacobi(float* buf, float* tmp, const float* Lnorm, const pfo_level* L, int iters);
 void pfo_quantize(const float* buf, int n, uint16_t* out);
-/* SolveDepthAll (Depth.cpp:1416-1771).  Returns 0 or a negative error. */
+/* SolveDepthAll (Depth.cpp:1416-1771).  Returns 0 or a negative error: -1 from pfo_targets, or
+ * PFO_EBAND, before any buffer is touched, for a level with h0 < 1, h1 > h - 2 or h0 >= h1 (the
+ * reference reads and writes outside its buffers there). */
+#define PFO_EBAND (-3)
 int  pfo_solve_depth_all(const float* emap, int ew, int eh, int ec, const pfo_tile* tiles,
                          int ntiles, const float* tile_data, int out_w, int out_h, float zr0,
                          float zr1, uint16_t* out, long long* oops);

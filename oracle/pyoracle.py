@@ -200,17 +200,24 @@ def quantize(buf):
     return out.reshape(buf.shape)
 
 
-def solve_depth_all(emap, tiles, tile_data, out_w, zr):
+EBAND = -3  # PFO_EBAND: a level's band touches a pole row or has no interior
+
+
+def solve_depth_all(emap, tiles, tile_data, out_w, zr, out_h=None):
+    out_h = out_w // 2 if out_h is None else int(out_h)
     eh, ew = emap.shape[:2]
     ec = emap.shape[2] if emap.ndim == 3 else 1
-    out = np.zeros(out_w * (out_w // 2), np.uint16)
+    out = np.zeros(out_w * out_h, np.uint16)
     oops = C.c_longlong(0)
     rc = lib().pfo_solve_depth_all(_p(np.ascontiguousarray(emap, np.float32)), ew, eh, ec,
-                                   tiles, len(tiles), _p(tile_data), out_w, out_w // 2,
+                                   tiles, len(tiles), _p(tile_data), out_w, out_h,
                                    zr[0], zr[1], _p(out, C.c_uint16), C.byref(oops))
+    if rc == EBAND:
+        raise ValueError(f"pfo_solve_depth_all rc={rc}: {out_w}x{out_h} has a level whose band "
+                         "is not inside rows [1, h-2]")
     if rc != 0:
         raise ValueError(f"pfo_solve_depth_all rc={rc}")
-    return out.reshape(out_w // 2, out_w), oops.value
+    return out.reshape(out_h, out_w), oops.value
 
 
 def solve_smoothing(tiles, tile_data, out_w, out_h, zr):

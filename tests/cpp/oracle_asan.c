@@ -65,6 +65,16 @@ int main(int argc, char** argv)
     spill(dir, "out.u16", out, sizeof(uint16_t) * (size_t)out_w * out_h);
     spill(dir, "abcd.f32", abcd, sizeof(float) * 4 * ntiles);
 
+    /* A band that reaches the last row (level 0 of 440x220 at 3..177 degrees has h1 = h - 1) is
+     * refused before any buffer is touched: the output here is one pixel. */
+    {
+        const float zw[2] = {(float)(3.0 / 180.0 * 3.14159265359), (float)(177.0 / 180.0 * 3.14159265359)};
+        uint16_t px = 0;
+        rc = pfo_solve_depth_all(emap, ew, eh, 1, tiles, ntiles, warped, 440, 220, zw[0], zw[1],
+                                 &px, NULL);
+        if (rc != PFO_EBAND) { fprintf(stderr, "pole band: rc=%d, want %d\n", rc, PFO_EBAND); return 1; }
+    }
+
     /* RGB warp of the same layout (3 bytes per tile pixel, packed in tile order) */
     long long rgb_total = 0;
     for (int i = 0; i < ntiles; i++) rgb_total += (long long)tiles[i].width * tiles[i].height * 3;

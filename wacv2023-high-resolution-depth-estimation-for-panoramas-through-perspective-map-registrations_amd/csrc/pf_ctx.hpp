@@ -346,6 +346,8 @@ struct JacobiRun {
 // Runs L.iters sweeps; returns the buffer holding the result (unused when out is given), or
 // nullptr when a seeded run lacks its seed tables.
 float* run_jacobi(pf_ctx* c, const LevelDims& L, const JacobiRun& r, int* npasses = nullptr);
+// Under PF_JPLAN, the `jacobi plan ... sweeps` line of a level that takes the per-sweep form.
+void show_sweeps_plan(const LevelDims& L, int batch);
 // The JacobiPass fields that do not depend on the pass, over the whole band [h0, h1].
 JacobiPass jacobi_pass(const pf_ctx* c, const LevelDims& L, const JacobiRun& r);
 int seed_tables(pf_ctx* c, const LevelDims& L, int ew, int eh, int ec);

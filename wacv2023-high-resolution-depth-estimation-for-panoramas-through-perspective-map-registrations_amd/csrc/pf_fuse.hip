@@ -75,6 +75,14 @@ static bool show_plans()
     return show;
 }
 
+// The per-sweep form's line among the PF_JPLAN lines (run_jres and run_jacobi print the others).
+void pf::show_sweeps_plan(const LevelDims& L, int batch)
+{
+    if (show_plans())
+        fprintf(stderr, "jacobi plan %dx%d band %d iters %d batch %d sweeps\n", L.w, L.h,
+                L.h1 - L.h0 + 1, L.iters, batch);
+}
+
 // All of a level's sweeps in one launch of the resident kernel (pf_jres.hip).
 static float* run_jres(pf_ctx* c, const LevelDims& L, const JacobiRun& r, const JresPlan& jp)
 {
@@ -306,6 +314,7 @@ static int fuse_range(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
         }
         float* res = nullptr;
         if (naive || jacobi_tcap(L) < 1) {
+            show_sweeps_plan(L, batch);
             {
                 double srcb = l == 0 ? band * 4.0 : (double)st;
                 StageTimer t(c, PF_STAGE_SEED, B * (4.0 * st + srcb), 1);

@@ -282,6 +282,7 @@ int pf_fuse_level(pf_ctx* c, const float* emap, int ew, int eh, int ec, const fl
     float* other = (float*)c->lsum_ws.p;
     float* res = nullptr;
     if (jacobi_tcap(L) < 1) {  // the plain sweep form: a seeded full plane, copied, swept
+        show_sweeps_plan(L, 1);
         if ((rc = pf_fuse_seed(c, emap, ew, eh, ec, prev, out_w, out_h, zr0, zr1, level, buf)))
             return rc;
         HIPCHK(c, hipMemcpyAsync(other, buf, sizeof(float) * st, hipMemcpyDeviceToDevice,

@@ -174,6 +174,11 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _out_h(out_w, out_h):
+    # the level entry points' output height: MergeDepthMaps' out_w / 2 unless the caller gives one
+    return out_w // 2 if out_h is None else int(out_h)
+
+
 def _emap_dims(emap):
     # emap: [B, eh, ew] or [B, eh, ew, ec]
     if emap.dim() == 3:
@@ -482,18 +487,19 @@ class Fuser:
         self._check(self.L.pf_disp_depth_convert(self.h, _ptr(t), t.numel() // channels,
                                                  int(channels)))
 
-    def probe_taps(self, out_w, zr, level):
+    def probe_taps(self, out_w, zr, level, out_h=None):
         import torch
-        w, h = level_info(out_w, out_w // 2, zr, level)[:2]
+        out_h = _out_h(out_w, out_h)
+        w, h = level_info(out_w, out_h, zr, level)[:2]
         out = torch.empty((h, w, 5), dtype=torch.int32, device=f"cuda:{self.device}")
-        self._check(self.L.pf_probe_taps(self.h, out_w, out_w // 2, float(zr[0]), float(zr[1]),
+        self._check(self.L.pf_probe_taps(self.h, out_w, out_h, float(zr[0]), float(zr[1]),
                                          level, _ptr(out)))
         return out
 
-    def fuse_partial(self, tiles, coeffs, t0, t1, out_w, zr, level, lsum, cnt):
+    def fuse_partial(self, tiles, coeffs, t0, t1, out_w, zr, level, lsum, cnt, out_h=None):
         self._check(self.L.pf_fuse_partial(self.h, _ptr(tiles), _ptr(coeffs), t0, t1, out_w,
-                                           out_w // 2, float(zr[0]), float(zr[1]), level,
-                                           _ptr(lsum), _ptr(cnt)))
+                                           _out_h(out_w, out_h), float(zr[0]), float(zr[1]),
+                                           level, _ptr(lsum), _ptr(cnt)))
 
     def fuse_partial_rows(self, tiles, coeffs, t0, t1, out_w, zr, level, row0, row1, lsum, cnt):
         """pf_fuse_partial on rows [row0, row1) only (no zeroing elsewhere)."""
@@ -539,28 +545,29 @@ class Fuser:
             n[i] = d.numel()
         self._check(self.L.pf_rows_add_batch(self.h, dst, src, n, k))
 
-    def fuse_seed(self, emap, prev, out_w, zr, level, buf):
+    def fuse_seed(self, emap, prev, out_w, zr, level, buf, out_h=None):
         ew, eh, ec = _emap_dims(emap) if emap is not None else (0, 0, 0)
         self._check(self.L.pf_fuse_seed(self.h, _ptr(emap), ew, eh, ec, _ptr(prev), out_w,
-                                        out_w // 2, float(zr[0]), float(zr[1]), level,
+                                        _out_h(out_w, out_h), float(zr[0]), float(zr[1]), level,
                                         _ptr(buf)))
 
-    def fuse_finish_level(self, lsum, cnt, out_w, zr, level, buf, out=None):
+    def fuse_finish_level(self, lsum, cnt, out_w, zr, level, buf, out=None, out_h=None):
         self._check(self.L.pf_fuse_finish_level(self.h, _ptr(lsum), _ptr(cnt), out_w,
-                                                out_w // 2, float(zr[0]), float(zr[1]), level,
-                                                _ptr(buf), _ptr(out)))
+                                                _out_h(out_w, out_h), float(zr[0]), float(zr[1]),
+                                                level, _ptr(buf), _ptr(out)))
 
-    def fuse_level(self, emap, prev, lsum, cnt, out_w, zr, level, buf, out=None):
+    def fuse_level(self, emap, prev, lsum, cnt, out_w, zr, level, buf, out=None, out_h=None):
         """pf_fuse_level: fuse_seed + fuse_finish_level with the seed inside the first pass."""
         ew, eh, ec = _emap_dims(emap) if emap is not None else (0, 0, 0)
         self._check(self.L.pf_fuse_level(self.h, _ptr(emap), ew, eh, ec, _ptr(prev), _ptr(lsum),
-                                         _ptr(cnt), out_w, out_w // 2, float(zr[0]),
+                                         _ptr(cnt), out_w, _out_h(out_w, out_h), float(zr[0]),
                                          float(zr[1]), level, _ptr(buf), _ptr(out)))
 
-    def fuse_targets(self, tiles, coeffs, out_w, zr, level, lnorm):
+    def fuse_targets(self, tiles, coeffs, out_w, zr, level, lnorm, out_h=None):
         """pf_fuse_targets: one level's normalised targets of one panorama from every tile."""
-        self._check(self.L.pf_fuse_targets(self.h, _ptr(tiles), _ptr(coeffs), out_w, out_w // 2,
-                                           float(zr[0]), float(zr[1]), level, _ptr(lnorm)))
+        self._check(self.L.pf_fuse_targets(self.h, _ptr(tiles), _ptr(coeffs), out_w,
+                                           _out_h(out_w, out_h), float(zr[0]), float(zr[1]),
+                                           level, _ptr(lnorm)))
 
     def multicover_count(self, out_w, zr, level):
         n = C.c_int(0)
