@@ -369,6 +369,28 @@ int pf_probe_warp_coords(const pf_window* fov, int tile_w, int tile_h, int pw, i
 int pf_probe_rgb_taps(const pf_window* fov, int tile_w, int tile_h, int pw, int ph,
                       uint32_t* taps);
 
+/* ---- layout audit ----
+ * What the tiles set by pf_set_tiles do at one level of an out_w x out_h fusion, counted on the
+ * GPU with the fusion's own tables (the level's host sin/cos tables and boxes) and projection:
+ * the verdict is about the taps pf_fuse reads, not about a second projection.  Taps are counted
+ * per (tile, pixel of its box, tap of the five-point mask), as the reference would visit them. */
+typedef struct pf_level_audit {
+    int w, h, h0, h1;             /* as pf_level_info */
+    long long taps_outside;       /* taps whose SphericalTo2D result leaves [0,1]^2 (tested on the
+                                     unclamped floats): the reference prints "oops!" and reads
+                                     past the tile there (Depth.cpp:1595-1604) */
+    long long taps_clamped;       /* taps whose Value() index (Y*W+X)*C left the tile buffer and
+                                     was clamped to [0, W*H*C - C]; depends on the tile size */
+    long long covered;            /* pixels with at least one covering tile */
+    long long uncovered_interior; /* rows h0+1..h1-1, columns 1..w-1, covered by no tile */
+    int max_cover;                /* most tiles over one pixel */
+    int seam;                     /* 1 if column w-1 is covered (the seam read, SURVEY App. A
+                                     item 5) */
+} pf_level_audit;
+/* out: HOST struct; the call synchronizes the context's stream. */
+int pf_layout_audit(pf_ctx* ctx, int out_w, int out_h, float zr0, float zr1, int level,
+                    pf_level_audit* out);
+
 /* ---- accuracy metrics ----
  * ErrorData (Depth.cpp:1980-2213) when given16 != NULL: the u16 result [batch][h][w];
  * ErrorEmap (Depth.cpp:2215-2458) when given != NULL: a float map [batch][h][w][given_c]

@@ -371,8 +371,13 @@ bool MedianScaling(EquirectangularMap& emap0, EquirectangularMap& emap1,
 }  // namespace DepthNamespace
 
 /* The mode-0 driver (Main.cpp:331-687 CreateDepthPanoramas) over std::filesystem; tile_ext is
- * "png" (MiDaS naming, Main.cpp:570-573), "jpg" (LeReS naming, :576-578) or "auto"; the LeReS
- * layout of Main.cpp:788-843 is used.  With PF_TILE_MODEL=disparity in the environment
+ * "png" (MiDaS naming, Main.cpp:570-573), "jpg" (LeReS naming, :576-578) or "auto".  The tile
+ * layout is the one PF_LAYOUT names in the environment (panofuse_main --layout NAME|FILE: leres,
+ * midas, fold4, fold3 or a layout file, see pf_resolve_layout), by default the LeReS layout of
+ * Main.cpp:788-843; an unusable PF_LAYOUT returns 2 before any GPU call.  After the first fused
+ * panorama the layout is audited once (pf_layout_audit) and every level with taps outside their
+ * tile prints "[layout] level L (WxH): N taps outside their tile (clamped)", in place of the
+ * reference's per-tap "oops!".  With PF_TILE_MODEL=disparity in the environment
  * (panofuse_main --tile-model disparity) the tiles are disparities: MergeDisparityMaps.  shard / nshards: this process takes the panoramas
  * shard, shard + nshards, ... of the sorted folder (one process per GPU, no communication).
  * With PF_GLOBAL_ALIGN=1 in the environment (panofuse_main --global-align) MergeDepthMaps and
@@ -387,13 +392,31 @@ int pf_create_depth_panoramas(const std::string& rgb_folder, const std::string& 
                               const std::string& tile_ext, int out_width, int shard = 0,
                               int nshards = 1);
 /* The RGB tile export of mode 0 (Main.cpp:399-430 + SaveCubeMap :242-326): every panorama of
- * rgb_folder (8/16-bit PNG, PGM/PPM) warped on the GPU (pf_warp_rgb) into the 15 LeReS tiles
- * of 1024 x round(1024/aspect) px, written as <tile_dir>/<raw>.<a0>_<a1>_<z0>_<z1>.jpg (rows
+ * rgb_folder (8/16-bit PNG, PGM/PPM) warped on the GPU (pf_warp_rgb) into the tiles of the
+ * layout PF_LAYOUT names (as above; by default the 15 LeReS tiles), each
+ * 1024 x round(1024/aspect) px, written as <tile_dir>/<raw>.<a0>_<a1>_<z0>_<z1>.jpg (rows
  * top-first, like the reference's flipped write; baseline JPEG at quality 100, 4:4:4, as the
  * reference's stbi_write_jpg call ends up, Main.cpp:319-320). */
 int pf_export_rgb_tiles(const std::string& rgb_folder, const std::string& tile_dir);
 /* The active LeReS layout (Main.cpp:788-843): 15 FOVs and ranges. */
 void pf_leres_layout(std::vector<Vec4f>& fovs, std::vector<Vec4f>& ranges);
+/* The reference's four tables by name, with its float rounding: "leres" (Main.cpp:788-843),
+ * "midas" (:731-787, 15 tiles), "fold4" (:695-730, 12 tiles), "fold3" (:845-887, 9 tiles); tile
+ * order bands outer, sectors inner.  false for an unknown name. */
+bool pf_named_layout(const std::string& name, std::vector<Vec4f>& fovs,
+                     std::vector<Vec4f>& ranges);
+/* A layout file: one tile per line, eight numbers in degrees (the window's az_left az_right
+ * zen_top zen_down, then the range's az_left az_right zen_up zen_down); '#' starts a comment,
+ * blank lines are skipped.  Every value becomes (float)D2R(deg), computed in double and rounded
+ * once: a file with fold4's degrees is fold4 bit for bit, while leres / midas / fold3 come from
+ * float additions and are in general not reproduced by their rounded degrees.  false with a
+ * message in *err for a line without exactly eight numbers, a non-finite value, no tiles or more
+ * than 4096 tiles. */
+bool pf_load_layout_file(const std::string& path, std::vector<Vec4f>& fovs,
+                         std::vector<Vec4f>& ranges, std::string* err);
+/* A known name, else a layout file (what --layout and PF_LAYOUT take). */
+bool pf_resolve_layout(const std::string& spec, std::vector<Vec4f>& fovs,
+                       std::vector<Vec4f>& ranges, std::string* err);
 
 /* C-ABI helpers (ctypes bindings, tests): load a map as EquirectangularMap::Load (is_emap = 1)
  * or PerspectiveMap::Load (0) into out (float, capacity `cap`; dims always written; returns -1
@@ -413,3 +436,11 @@ extern "C" int pfd_decode_image(const char* fn, void* out, long long cap, int* w
                                 int* is16);
 extern "C" int pfd_is_16_bit(const char* fn);
 extern "C" void pfd_leres_layout(float* fovs, float* ranges);
+/* pf_resolve_layout for bindings: the tiles of a named table or a layout file as 4 floats each
+ * into fovs / ranges (capacity `cap` tiles each; either may be NULL to ask for the count only).
+ * Returns the tile count, or -1 (unknown name / rejected file, message on stdout; or cap too
+ * small). */
+extern "C" int pfd_layout(const char* name, float* fovs, float* ranges, int cap);
+/* The export's tile size for a window (SaveCubeMap's viewport): w = 1024,
+ * h = round(1024 / aspect). */
+extern "C" void pfd_rgb_tile_size(const float* fov, int* w, int* h);

@@ -92,6 +92,7 @@ struct pf_ctx {
     std::vector<pf::WarpPatch> wpatch_grid_h;  // the layout's plain 32x32 patch grid
     // workspace
     pf::DevBuf buf[3], lnorm, coeffs, lsum_ws, metrics_ws, reg_sums, reg_active;
+    pf::DevBuf audit_ws;    // pf_layout_audit: the counter words
     pf::DevBuf disp_tiles;  // pf_merge_disparity: the transformed copy of the caller's tiles
     // pf_register_global: ValueAtCoord's column / row terms for one (result size, baseline size)
     // key, the chunk partials with the coefficients after them; pf_median_scale: bins and states

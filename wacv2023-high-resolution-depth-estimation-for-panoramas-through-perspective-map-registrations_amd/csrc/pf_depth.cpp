@@ -9,6 +9,7 @@
 #include "../../include/panofuse.h"
 #include "pf_geom.hpp"
 #include "pf_image.hpp"
+#include "pf_layouts.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1077,26 +1078,80 @@ bool MergeDisparityMaps(std::string& emap_fn, std::vector<std::string>& pmap_fns
 }  // namespace DepthNamespace
 
 // ---- mode-0 driver (Main.cpp:331-687) ----
-void pf_leres_layout(std::vector<Vec4f>& fovs, std::vector<Vec4f>& ranges)
+static void to_vec4(const std::vector<pfl::Tile>& tiles, std::vector<Vec4f>& fovs,
+                    std::vector<Vec4f>& ranges)
 {
-    // Main.cpp:788-843, the active "5-fold for LeReS" block
-    const float margin = (float)PF_D2R(3);
-    float a0[5], a1[5];
-    for (int i = 0; i < 5; ++i) {
-        a0[i] = (float)(PF_D2R(72.0 * i) - margin);
-        a1[i] = (float)(PF_D2R(72.0 * (i + 1)) + margin);
-    }
-    const double fz[3][2] = {{18, 94}, {52, 128}, {86, 162}};
-    const double rz[3][2] = {{25, 60}, {60, 120}, {120, 155}};
     fovs.clear();
     ranges.clear();
-    for (int b = 0; b < 3; ++b)
-        for (int i = 0; i < 5; ++i)
-            fovs.push_back(Vec4f(a0[i], a1[i], (float)PF_D2R(fz[b][0]), (float)PF_D2R(fz[b][1])));
-    for (int b = 0; b < 3; ++b)
-        for (int i = 0; i < 5; ++i)
-            ranges.push_back(Vec4f(a1[i] - margin, a0[i] + margin, (float)PF_D2R(rz[b][0]),
-                                   (float)PF_D2R(rz[b][1])));
+    for (const pfl::Tile& t : tiles) {
+        fovs.push_back(Vec4f(t.fov[0], t.fov[1], t.fov[2], t.fov[3]));
+        ranges.push_back(Vec4f(t.range[0], t.range[1], t.range[2], t.range[3]));
+    }
+}
+
+bool pf_named_layout(const std::string& name, std::vector<Vec4f>& fovs,
+                     std::vector<Vec4f>& ranges)
+{
+    std::vector<pfl::Tile> tiles;
+    if (!pfl::named(name, tiles)) return false;
+    to_vec4(tiles, fovs, ranges);
+    return true;
+}
+
+bool pf_load_layout_file(const std::string& path, std::vector<Vec4f>& fovs,
+                         std::vector<Vec4f>& ranges, std::string* err)
+{
+    std::vector<pfl::Tile> tiles;
+    std::string e;
+    const bool ok = pfl::load_file(path, tiles, e);
+    if (err) *err = e;
+    if (ok) to_vec4(tiles, fovs, ranges);
+    return ok;
+}
+
+bool pf_resolve_layout(const std::string& spec, std::vector<Vec4f>& fovs,
+                       std::vector<Vec4f>& ranges, std::string* err)
+{
+    std::vector<pfl::Tile> tiles;
+    std::string e;
+    const bool ok = pfl::resolve(spec, tiles, e);
+    if (err) *err = e;
+    if (ok) to_vec4(tiles, fovs, ranges);
+    return ok;
+}
+
+void pf_leres_layout(std::vector<Vec4f>& fovs, std::vector<Vec4f>& ranges)
+{
+    pf_named_layout("leres", fovs, ranges);  // Main.cpp:788-843, the active "5-fold for LeReS" block
+}
+
+// The layout of mode 0 and of the export: PF_LAYOUT (panofuse_main --layout), else leres.
+static bool env_layout(std::vector<Vec4f>& fovs, std::vector<Vec4f>& ranges)
+{
+    const char* spec = std::getenv("PF_LAYOUT");
+    std::string err;
+    if (pf_resolve_layout(spec && spec[0] ? spec : "leres", fovs, ranges, &err)) return true;
+    std::cout << "[panofuse] " << err << std::endl;
+    return false;
+}
+
+// Mode 0's stand-in for the reference's per-tap "oops!" (Depth.cpp:1595-1604): one line per level
+// of the layout the context holds that has taps outside their tile.
+static void print_layout_audit(pf_ctx* c, int out_width, Vec2f& zr)
+{
+    int nlevels = 0;
+    if (pf_level_info(out_width, out_width / 2, zr[0], zr[1], 0, nullptr, nullptr, nullptr,
+                      nullptr, nullptr, &nlevels) != PF_OK)
+        return;
+    for (int l = 0; l < nlevels; ++l) {
+        pf_level_audit a;
+        if (!pf_ok(c, pf_layout_audit(c, out_width, out_width / 2, zr[0], zr[1], l, &a),
+                   "pf_layout_audit"))
+            return;
+        if (a.taps_outside > 0)
+            std::cout << "[layout] level " << l << " (" << a.w << "x" << a.h << "): "
+                      << a.taps_outside << " taps outside their tile (clamped)" << std::endl;
+    }
 }
 
 // The opt-in edge metrics of mode 0: ErrorLaplacian of the written result and of the baseline
@@ -1145,7 +1200,8 @@ int pf_create_depth_panoramas(const std::string& rgb_folder, const std::string& 
     const char* tm = std::getenv("PF_TILE_MODEL");
     const bool disparity_tiles = tm && std::string(tm) == "disparity";
     std::vector<Vec4f> fovs, ranges;
-    pf_leres_layout(fovs, ranges);
+    if (!env_layout(fovs, ranges)) return 2;
+    bool audited = false;
     std::vector<std::string> rgb;  // AllFilesInFolder (Main.cpp:50-83): files only
     std::error_code ec;
     for (const auto& e : fs::directory_iterator(rgb_folder, ec))
@@ -1211,6 +1267,10 @@ int pf_create_depth_panoramas(const std::string& rgb_folder, const std::string& 
             std::cout << "[CreateDepthPanorma] MergeDepthMaps #" << i << " failed!" << std::endl;
             return 1;
         }
+        if (!audited) {  // once: the facade context now holds this layout at this width
+            audited = true;
+            if (pf_ctx* c = facade_ctx()) print_layout_audit(c, out_width, g_zenith_range);
+        }
         m.Save((join(result_folder, rawname) + ".aligned.txt").c_str());
         if (edge_metrics && !save_edge_metrics(gt, base, out, join(result_folder, rawname) + ".edges.txt"))
             std::cout << "[CreateDepthPanorma] no edge metrics for #" << i << std::endl;
@@ -1252,7 +1312,7 @@ int pf_export_rgb_tiles(const std::string& rgb_folder, const std::string& tile_d
 {
     namespace fs = std::filesystem;
     std::vector<Vec4f> fovs, ranges;
-    pf_leres_layout(fovs, ranges);
+    if (!env_layout(fovs, ranges)) return 2;
     pf_ctx* c = facade_ctx();
     if (!c) return 1;
     const int n = (int)fovs.size();
@@ -1389,4 +1449,27 @@ extern "C" void pfd_leres_layout(float* fovs, float* ranges)
             fovs[4 * i + k] = f[i][k];
             ranges[4 * i + k] = r[i][k];
         }
+}
+
+extern "C" int pfd_layout(const char* name, float* fovs, float* ranges, int cap)
+{
+    std::vector<Vec4f> f, r;
+    std::string err;
+    if (!name || !pf_resolve_layout(name, f, r, &err)) {
+        std::cout << "[pfd_layout] " << (name ? err : std::string("NULL name")) << std::endl;
+        return -1;
+    }
+    const int n = (int)f.size();
+    if ((fovs || ranges) && cap < n) return -1;
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < 4; ++k) {
+            if (fovs) fovs[4 * i + k] = f[i][k];
+            if (ranges) ranges[4 * i + k] = r[i][k];
+        }
+    return n;
+}
+
+extern "C" void pfd_rgb_tile_size(const float* fov, int* w, int* h)
+{
+    rgb_tile_size(Vec4f(fov[0], fov[1], fov[2], fov[3]), *w, *h);
 }

@@ -262,6 +262,12 @@ void launch_jres(hipStream_t s, const JresArgs& A);
 // Kernel launchers (pf_kernels.hip, pf_jacobi.hip).  All are asynchronous on `stream`.
 void launch_tapmap(hipStream_t s, const TileGeom* geom, const TapBox* tb, int ntiles,
                    long long max_points, const GridCol* cols, const GridRow* rows, int32_t* map);
+// pf_layout_audit's counters, ctr[kAuditWords] (zeroed on the stream before the launch): taps
+// outside, taps clamped, covered pixels, uncovered interior pixels, largest cover, seam covered
+static constexpr int kAuditWords = 6;
+void launch_layout_audit(hipStream_t s, const TileGeom* geom, const TileBox* box, int ntiles,
+                         const GridCol* cols, const GridRow* rows, LevelDims L,
+                         unsigned long long* ctr);
 void launch_targets_map(hipStream_t s, const TileGeom* geom, const TileBox* box,
                         const TapBox* tb, int ntiles, const int32_t* map, const float* tiles,
                         long long tstride, const float* coeffs, LevelDims L, float* lnorm,

@@ -239,6 +239,39 @@ int pf_set_tiles(pf_ctx* c, const pf_window* fovs, const pf_window* ranges, int 
     return PF_OK;
 }
 
+int pf_layout_audit(pf_ctx* c, int out_w, int out_h, float zr0, float zr1, int level,
+                    pf_level_audit* out)
+{
+    int rc;
+    const LevelDims* Lp = nullptr;
+    if ((rc = check_common(c, 1))) return rc;
+    if (!out) return fail(c, PF_EINVAL, "NULL buffer");
+    if ((rc = level_at(c, out_w, out_h, zr0, zr1, level, &Lp))) return rc;
+    const LevelDims& L = *Lp;
+    const LevelCache& lc = c->lc;
+    const size_t bytes = sizeof(unsigned long long) * kAuditWords;
+    if ((rc = ensure(c, c->audit_ws, bytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->audit_ws.p, 0, bytes, c->stream));
+    launch_layout_audit(c->stream, (const TileGeom*)c->geom.p, (const TileBox*)lc.box[level].p,
+                        c->ntiles, (const GridCol*)lc.cols[level].p,
+                        (const GridRow*)lc.rows[level].p, L, (unsigned long long*)c->audit_ws.p);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long h[kAuditWords];
+    HIPCHK(c, hipMemcpyAsync(h, c->audit_ws.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    out->w = L.w;
+    out->h = L.h;
+    out->h0 = L.h0;
+    out->h1 = L.h1;
+    out->taps_outside = (long long)h[0];
+    out->taps_clamped = (long long)h[1];
+    out->covered = (long long)h[2];
+    out->uncovered_interior = (long long)h[3];
+    out->max_cover = (int)h[4];
+    out->seam = (int)h[5];
+    return PF_OK;
+}
+
 }  // extern "C"
 
 // Registration tables depend on the zenith range; built per call (tiny, cached by value).

@@ -2,8 +2,9 @@
 //   panofuse_main 0 <rgb_dir> <gt_dir> <baseline_dir> <result_dir> [--tiles DIR]
 //                 [--ext auto|jpg|png] [--width W] [--device D] [--shard R/N]
 //                 [--metrics-order tree|sequential] [--edge-metrics]
-//                 [--tile-model depth|disparity] [--global-align]
-//   panofuse_main export <rgb_dir> <tile_dir> [--device D]
+//                 [--tile-model depth|disparity] [--global-align] [--layout NAME|FILE]
+//   panofuse_main export <rgb_dir> <tile_dir> [--device D] [--layout NAME|FILE]
+//   panofuse_main layout NAME|FILE [--width W] [--tile-size WxH] [--device D]
 //   panofuse_main lap <gt_file> <given_file> [--device D]
 //   panofuse_main cmp <gt_file> <given_file> [--disp] [--align 0|1|2] [--no-cap] [--save FILE]
 //                 [--device D] [--metrics-order tree|sequential]
@@ -15,7 +16,22 @@
 // "lap" is the reference's ErrorLaplacian (Depth.cpp:2636-2953) on two image files: its
 // "[ErrorLap] ..." line, then one line with the three sample counts.
 // "export" is the tile render of mode 0 (Main.cpp:399-430, SaveCubeMap :242-326) on the GPU:
-// each RGB panorama becomes the 15 LeReS perspective tiles the depth network consumes.
+// each RGB panorama becomes the perspective tiles of the chosen layout (by default the 15 LeReS
+// tiles) that the depth network consumes.
+// --layout: the tile table of mode 0 and of export.  leres (the default: Main.cpp:788-843, the
+// reference's active table), midas (:731-787), fold4 (:695-730), fold3 (:845-887), or a layout
+// file: one tile per line, eight numbers in degrees (the window's az_left az_right zen_top
+// zen_down, then the range's az_left az_right zen_up zen_down), '#' comments; each value becomes
+// (float)D2R(deg), computed in double and rounded once.  The tile file names follow the table
+// (<raw>.<a0>_<a1>_<z0>_<z1>.<ext> from round(R2D(fov)), Main.cpp:577-584).  A value that is
+// neither a known name nor a usable file ends the command with status 2 before any GPU call.
+// Mode 0 audits the layout once at its output width and prints, per level that has any,
+// "[layout] level L (WxH): N taps outside their tile (clamped)": the reference prints "oops!"
+// per such tap and reads past the tile, the library clamps the index.
+// "layout" audits a layout on the GPU (pf_layout_audit) at --width (default 2048) with tiles of
+// --tile-size (default 1024x1024) and prints, per level,
+// "LEVEL l w h h0 h1 outside clamped covered uncovered max_cover seam"; exit 1 with the message
+// when pf_set_tiles or the level set-up rejects the layout.
 // Mode 0 = CreateDepthPanoramas (Main.cpp:331-687) minus the OpenGL tile export: the perspective
 // depth tiles are read from --tiles (default "test_images", the reference's LeReS folder) named
 // <raw>.<a0>_<a1>_<z0>_<z1>.<ext>; "auto" takes .jpg when present, else .png (MiDaS naming).
@@ -25,12 +41,13 @@
 // --tile-model: what the tiles hold.  depth (the default: LeReS-style tiles, the cubic
 // registration) or disparity (MiDaS / DPT tiles, relative inverse depth in 0-1: each is fitted
 // with y = 1/(a x + b) + d and mapped to depth by D2DTransform).  The reference's MiDaS folder
-// convention (Main.cpp:577-579) is `--tiles output --ext png`.
+// convention (Main.cpp:577-579) is `--layout midas --tiles output --ext png`.
 // --global-align (opt-in, takes no value): after the fusion the u16 result is registered to the
 // baseline with SolveDepthToDepth2's cubic (Depth.cpp:1158-1259) and transformed, before it is
 // written and scored; prints the "[SolveDepthToDepth2] ..." line per panorama.
 // --edge-metrics (opt-in, takes no value): also write <raw>.edges.txt per panorama, the
 // ErrorLaplacian values of the result and of the baseline against the gt.
+#include "../../include/panofuse.h"
 #include "../../include/pf_depth.h"
 
 #include <hip/hip_runtime.h>
@@ -41,6 +58,92 @@
 #include <string>
 #include <vector>
 
+// --layout's value: checked here (no GPU call yet), carried to the facade in PF_LAYOUT.
+static bool take_layout(const std::string& v)
+{
+    std::vector<Vec4f> fovs, ranges;
+    std::string err;
+    if (!pf_resolve_layout(v, fovs, ranges, &err)) {
+        std::cout << "bad --layout: " << err << std::endl;
+        return false;
+    }
+    setenv("PF_LAYOUT", v.c_str(), 1);  // read by pf_create_depth_panoramas / pf_export_rgb_tiles
+    return true;
+}
+
+static int layout_command(int argc, char* argv[])
+{
+    if (argc < 3) {
+        std::cout << "usage: " << argv[0]
+                  << " layout NAME|FILE [--width W] [--tile-size WxH] [--device D]" << std::endl;
+        return 1;
+    }
+    int width = 2048, tw = 1024, th = 1024, dev = 0;
+    for (int i = 3; i < argc; i += 2) {
+        const std::string k(argv[i]);
+        if (i + 1 >= argc) {
+            std::cout << "option " << k << " needs a value" << std::endl;
+            return 2;
+        }
+        const std::string v(argv[i + 1]);
+        if (k == "--width") width = std::atoi(v.c_str());
+        else if (k == "--device") dev = std::atoi(v.c_str());
+        else if (k == "--tile-size") {
+            if (std::sscanf(v.c_str(), "%dx%d", &tw, &th) != 2 || tw < 2 || th < 2) {
+                std::cout << "bad --tile-size " << v << " (want WxH)" << std::endl;
+                return 2;
+            }
+        }
+        else {
+            std::cout << "unknown option " << k << std::endl;
+            return 2;
+        }
+    }
+    std::vector<Vec4f> fovs, ranges;
+    std::string err;
+    if (!pf_resolve_layout(argv[2], fovs, ranges, &err)) {
+        std::cout << "bad layout: " << err << std::endl;
+        return 2;
+    }
+    if (hipSetDevice(dev) != hipSuccess) {
+        std::cout << "no HIP device " << dev << std::endl;
+        return 1;
+    }
+    pf_ctx* c = nullptr;
+    if (pf_create(dev, &c) != PF_OK) {
+        std::cout << "pf_create(" << dev << ") failed" << std::endl;
+        return 1;
+    }
+    const int n = (int)fovs.size();
+    std::vector<pf_window> fw(n), rw(n);
+    std::vector<int> tws(n, tw), ths(n, th);
+    for (int i = 0; i < n; ++i) {
+        fw[i] = pf_window{fovs[i][0], fovs[i][1], fovs[i][2], fovs[i][3]};
+        rw[i] = pf_window{ranges[i][0], ranges[i][1], ranges[i][2], ranges[i][3]};
+    }
+    int rc = pf_set_tiles(c, fw.data(), rw.data(), n, tws.data(), ths.data(), 1, 1);
+    int nlevels = 0;
+    if (rc == PF_OK)
+        rc = pf_level_info(width, width / 2, g_zenith_range[0], g_zenith_range[1], 0, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, &nlevels);
+    for (int l = 0; rc == PF_OK && l < nlevels; ++l) {
+        pf_level_audit a;
+        rc = pf_layout_audit(c, width, width / 2, g_zenith_range[0], g_zenith_range[1], l, &a);
+        if (rc == PF_OK)
+            std::printf("LEVEL %d %d %d %d %d %lld %lld %lld %lld %d %d\n", l, a.w, a.h, a.h0, a.h1,
+                        a.taps_outside, a.taps_clamped, a.covered, a.uncovered_interior,
+                        a.max_cover, a.seam);
+    }
+    if (rc != PF_OK) {
+        const char* msg = pf_last_error(c);
+        std::cout << "layout rejected (" << rc << "): "
+                  << (msg && msg[0] ? msg : "bad output width") << std::endl;
+    }
+    std::fflush(stdout);
+    pf_destroy(c);
+    return rc == PF_OK ? 0 : 1;
+}
+
 int main(int argc, char* argv[])
 {
     if (argc < 2) {
@@ -48,10 +151,13 @@ int main(int argc, char* argv[])
                   << " 0 <rgb_dir> <gt_dir> <baseline_dir> <result_dir> [--tiles DIR]"
                      " [--ext auto|jpg|png] [--width W] [--device D] [--shard R/N]"
                      " [--metrics-order tree|sequential] [--edge-metrics]"
-                     " [--tile-model depth|disparity] [--global-align]\n"
+                     " [--tile-model depth|disparity] [--global-align] [--layout NAME|FILE]\n"
                      "         (MiDaS disparity tiles, the reference's folder convention:"
-                     " --tile-model disparity --tiles output --ext png)\n       "
-                  << argv[0] << " export <rgb_dir> <tile_dir> [--device D]\n       "
+                     " --layout midas --tile-model disparity --tiles output --ext png)\n"
+                     "         (--layout: leres (default), midas, fold4, fold3, or a file of"
+                     " lines `faz0 faz1 fzen0 fzen1 raz0 raz1 rzen0 rzen1` in degrees)\n       "
+                  << argv[0] << " export <rgb_dir> <tile_dir> [--device D] [--layout NAME|FILE]\n       "
+                  << argv[0] << " layout NAME|FILE [--width W] [--tile-size WxH] [--device D]\n       "
                   << argv[0] << " lap <gt_file> <given_file> [--device D]\n       "
                   << argv[0]
                   << " cmp <gt_file> <given_file> [--disp] [--align 0|1|2] [--no-cap] [--save FILE]"
@@ -62,17 +168,35 @@ int main(int argc, char* argv[])
     const std::string cmd(argv[1]);
     if (cmd == "export") {
         if (argc < 4) {
-            std::cout << "usage: " << argv[0] << " export <rgb_dir> <tile_dir> [--device D]"
+            std::cout << "usage: " << argv[0]
+                      << " export <rgb_dir> <tile_dir> [--device D] [--layout NAME|FILE]"
                       << std::endl;
             return 1;
         }
-        const int dev = argc >= 6 && std::string(argv[4]) == "--device" ? std::atoi(argv[5]) : 0;
+        int dev = 0;
+        for (int i = 4; i < argc; i += 2) {
+            const std::string k(argv[i]);
+            if (i + 1 >= argc) {
+                std::cout << "option " << k << " needs a value" << std::endl;
+                return 2;
+            }
+            const std::string v(argv[i + 1]);
+            if (k == "--device") dev = std::atoi(v.c_str());
+            else if (k == "--layout") {
+                if (!take_layout(v)) return 2;
+            }
+            else {
+                std::cout << "unknown option " << k << std::endl;
+                return 2;
+            }
+        }
         if (hipSetDevice(dev) != hipSuccess) {
             std::cout << "no HIP device " << dev << std::endl;
             return 1;
         }
         return pf_export_rgb_tiles(argv[2], argv[3]);
     }
+    if (cmd == "layout") return layout_command(argc, argv);
     if (cmd == "lap") {
         if (argc < 4) {
             std::cout << "usage: " << argv[0] << " lap <gt_file> <given_file> [--device D]"
@@ -216,6 +340,9 @@ int main(int argc, char* argv[])
                 return 2;
             }
             setenv("PF_TILE_MODEL", v.c_str(), 1);  // read by pf_create_depth_panoramas
+        }
+        else if (k == "--layout") {
+            if (!take_layout(v)) return 2;
         }
         else if (k == "--shard") {  // R/N: one process per GPU over the sorted folder
             if (std::sscanf(v.c_str(), "%d/%d", &shard, &nshards) != 2 || nshards < 1 ||

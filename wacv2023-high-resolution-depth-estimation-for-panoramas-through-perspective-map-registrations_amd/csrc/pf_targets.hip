@@ -49,6 +49,96 @@ __device__ __forceinline__ bool in_box2(const TileBox& bx, int X, int Y)
     return bx.xs > 0 ? (X >= bx.x0 && X < bx.x1) : (X <= bx.x0 && X > bx.x1);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Layout audit (pf_layout_audit): k_tapmap's sibling.  Rows p < ntiles of the grid walk tile p's
+// box and count, per pixel and tap of the five-point mask (the reference's visit order does not
+// matter to a count), the taps whose projection leaves [0,1]^2 -- tested on the unclamped floats,
+// Depth.cpp:1595 -- and the taps whose Value() index k_tapmap clamps.  Row p == ntiles walks the
+// level's pixels and counts the covering tiles of each.  The flags are summed inside the wave
+// (ballot + popcount, so the sums are wave-uniform), across the block's four waves through LDS,
+// and leave the block as one atomic per counter; integer sums, so the result does not depend on
+// the order the blocks arrive in.
+// ctr: [0] taps outside, [1] taps clamped, [2] covered pixels, [3] uncovered interior pixels,
+// [4] largest cover, [5] seam column covered; zeroed on the stream before the launch.
+__device__ __forceinline__ unsigned long long wave_count(bool f)
+{
+    return (unsigned long long)__popcll(__ballot(f));
+}
+
+__global__ void __launch_bounds__(256) k_layout_audit(const TileGeom* __restrict__ geom,
+                                                      const TileBox* __restrict__ box, int ntiles,
+                                                      const GridCol* __restrict__ cols,
+                                                      const GridRow* __restrict__ rows,
+                                                      LevelDims L,
+                                                      unsigned long long* __restrict__ ctr)
+{
+    __shared__ unsigned long long s_cnt[4][4];
+    __shared__ int s_max[4], s_seam[4];
+    const int p = blockIdx.y;
+    unsigned long long outside = 0, clamped = 0, covered = 0, uncovered = 0;  // wave-uniform
+    int seam = 0, most = 0;                                                   // per lane
+    if (p < ntiles) {
+        const TileBox bx = box[p];
+        // X runs x0, x0+xs, ... and stops before x1 (in_box2): columns [xlo, xhi]
+        const int xlo = bx.xs > 0 ? bx.x0 : bx.x1 + 1, xhi = bx.xs > 0 ? bx.x1 - 1 : bx.x0;
+        const int nx = xhi - xlo + 1, ny = bx.y1 - bx.y0 + 1;
+        const long long n = nx > 0 && ny > 0 ? (long long)nx * ny : 0;
+        const TileGeom g = geom[p];
+        const long long lim = (long long)g.w * g.h * g.c;
+        for (long long i0 = (long long)blockIdx.x * 256; i0 < n; i0 += (long long)gridDim.x * 256) {
+            const long long i = i0 + threadIdx.x;
+            const bool live = i < n;
+            const int Y = bx.y0 + (live ? (int)(i / nx) : 0), X = xlo + (live ? (int)(i % nx) : 0);
+            const int dx[5] = {-1, 0, 0, 0, 1}, dy[5] = {0, -1, 0, 1, 0};
+#pragma unroll
+            for (int k = 0; k < 5; k++) {
+                const GridCol c = cols[X + dx[k] + 1];
+                const GridRow r = rows[Y + dy[k] + 1];
+                float x, y;
+                sph_to_2d(g, r.sz, r.cz, c.ca, c.sa, x, y);
+                const long long idx = tile_index(g, x, y);
+                outside += wave_count(live && (x < 0 || x > 1 || y < 0 || y > 1));
+                clamped += wave_count(live && (idx < 0 || idx >= lim));
+            }
+        }
+    } else {
+        const long long n = (long long)L.w * L.h;
+        for (long long i0 = (long long)blockIdx.x * 256; i0 < n; i0 += (long long)gridDim.x * 256) {
+            const long long i = i0 + threadIdx.x;
+            const bool live = i < n;
+            const int Y = live ? (int)(i / L.w) : 0, X = live ? (int)(i % L.w) : 0;
+            int cnt = 0;
+            for (int q = 0; q < ntiles; q++) cnt += in_box2(box[q], X, Y) ? 1 : 0;
+            covered += wave_count(live && cnt > 0);
+            uncovered += wave_count(live && cnt == 0 && Y > L.h0 && Y < L.h1 && X >= 1);
+            if (live && cnt > most) most = cnt;
+            if (live && cnt > 0 && X == L.w - 1) seam = 1;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) most = max(most, __shfl_xor(most, o));
+    const bool any_seam = __ballot(seam != 0) != 0;
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        s_cnt[wv][0] = outside;
+        s_cnt[wv][1] = clamped;
+        s_cnt[wv][2] = covered;
+        s_cnt[wv][3] = uncovered;
+        s_max[wv] = most;
+        s_seam[wv] = any_seam ? 1 : 0;
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < 4) {
+        const unsigned long long v = s_cnt[0][t] + s_cnt[1][t] + s_cnt[2][t] + s_cnt[3][t];
+        if (v) atomicAdd(&ctr[t], v);
+    } else if (t == 4) {
+        const int m = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
+        if (m) atomicMax(&ctr[4], (unsigned long long)m);
+    } else if (t == 5) {
+        if (s_seam[0] | s_seam[1] | s_seam[2] | s_seam[3]) atomicMax(&ctr[5], 1ull);
+    }
+}
+
 template <bool XFORM>
 __global__ void __launch_bounds__(256) k_targets_map(const TileGeom* __restrict__ geom,
                                                      const TileBox* __restrict__ box,
@@ -390,6 +480,19 @@ void launch_targets_patch(hipStream_t s, const TileGeom* geom, const TileBox* bo
         hipLaunchKernelGGL((k_targets_patch<false, kTNB>), g, dim3(256), 0, s, geom, box, tb,
                            ntiles, map, tiles, tstride, coeffs, L, npx, npatch, lnorm, lstride,
                            batch, tmask, nmw);
+}
+
+void launch_layout_audit(hipStream_t s, const TileGeom* geom, const TileBox* box, int ntiles,
+                         const GridCol* cols, const GridRow* rows, LevelDims L,
+                         unsigned long long* ctr)
+{
+    // the widest row of the grid is the coverage row: the level's w * h pixels
+    long long nb = ((long long)L.w * L.h + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    if (nb < 1) nb = 1;
+    dim3 grid((unsigned)nb, ntiles + 1);
+    hipLaunchKernelGGL(k_layout_audit, grid, dim3(256), 0, s, geom, box, ntiles, cols, rows, L,
+                       ctr);
 }
 
 void launch_tapmap(hipStream_t s, const TileGeom* geom, const TapBox* tb, int ntiles,

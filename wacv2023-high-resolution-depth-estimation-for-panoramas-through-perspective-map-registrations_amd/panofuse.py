@@ -35,7 +35,7 @@ EXPORTS = [
     "pf_rows_add_batch", "pf_set_jacobi_share", "pf_error_laplacian",
     "pf_error_compare", "pf_disp_depth_convert", "pf_register_disparity",
     "pf_disparity_transform", "pf_merge_disparity", "pf_register_global",
-    "pf_result_transform", "pf_median_scale", "pf_copy_invalid",
+    "pf_result_transform", "pf_median_scale", "pf_copy_invalid", "pf_layout_audit",
 ]
 NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
           "pf_debug_smooth_fault", "pf_fuse_partial_rows", "pf_fuse_coverage_rows",
@@ -56,6 +56,14 @@ class PanofuseError(RuntimeError):
 class Window(C.Structure):
     _fields_ = [("az_left", C.c_float), ("az_right", C.c_float),
                 ("zen_top", C.c_float), ("zen_down", C.c_float)]
+
+
+class LevelAudit(C.Structure):
+    """pf_level_audit (include/panofuse.h)."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("h0", C.c_int), ("h1", C.c_int),
+                ("taps_outside", C.c_longlong), ("taps_clamped", C.c_longlong),
+                ("covered", C.c_longlong), ("uncovered_interior", C.c_longlong),
+                ("max_cover", C.c_int), ("seam", C.c_int)]
 
 
 class Response(C.Structure):
@@ -98,6 +106,7 @@ def load():
     L.pf_fuse_seed.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, fp, fp, ip, vp]
     L.pf_fuse_finish_level.argtypes = [vp, vp, vp, ip, ip, fp, fp, ip, vp, vp]
     L.pf_probe_taps.argtypes = [vp, ip, ip, fp, fp, ip, vp]
+    L.pf_layout_audit.argtypes = [vp, ip, ip, fp, fp, ip, C.POINTER(LevelAudit)]
     L.pf_depth_transform.argtypes = [vp, vp, C.c_longlong, ip, vp]
     L.pf_register_joint.argtypes = [vp, vp, ip, ip, ip, vp, ip, fp, fp, ip, vp, vp, vp]
     L.pf_error_metrics.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, ip, ip, ip, fp, fp, ip, ip,
@@ -495,6 +504,16 @@ class Fuser:
         self._check(self.L.pf_probe_taps(self.h, out_w, out_h, float(zr[0]), float(zr[1]),
                                          level, _ptr(out)))
         return out
+
+    def layout_audit(self, out_w, zr, level, out_h=None):
+        """pf_layout_audit: what the tiles set by set_tiles do at one level of an out_w x out_h
+        fusion, as a dict of pf_level_audit's fields (w, h, h0, h1, taps_outside, taps_clamped,
+        covered, uncovered_interior, max_cover, seam).  Counted on the GPU with the fusion's own
+        tables; synchronizes the context's stream."""
+        a = LevelAudit()
+        self._check(self.L.pf_layout_audit(self.h, out_w, _out_h(out_w, out_h), float(zr[0]),
+                                           float(zr[1]), level, C.byref(a)))
+        return {name: int(getattr(a, name)) for name, _ in LevelAudit._fields_}
 
     def fuse_partial(self, tiles, coeffs, t0, t1, out_w, zr, level, lsum, cnt, out_h=None):
         self._check(self.L.pf_fuse_partial(self.h, _ptr(tiles), _ptr(coeffs), t0, t1, out_w,
