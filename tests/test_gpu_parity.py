@@ -194,14 +194,27 @@ def test_warp_depth_bit_exact(fuser, cfg):
 def test_warp_depth_ragged_batch_and_resize(fuser):
     """Batch 19 (one full 16-panorama chunk + a ragged one), distinct responses per panorama,
     then other panorama sizes on the same context (the cached warp map must follow): 300 wide
-    stages 16-B quads, 302 wide (not a multiple of 4) the 4-B staging path."""
+    stages 16-B quads, 302 wide (not a multiple of 4) the 4-B staging path.
+
+    Together the sizes run every path of k_warp_depth at C1, each with a full and a ragged
+    16-panorama chunk.  64x32 patches per path (classified on the host from
+    panofuse.warp_coords with the rules of warp_patches_host / k_patch_box; NS = staging loads
+    per thread, wide = the direct gather):
+
+        C1 at     | ragged (16-B units) NS 1 / 2 / 4 / wide | box (4-B units) NS 4 / 8 / 16 / wide
+        512x256   | 108 / 24 / 60 /  0                      | --
+        300x150   | 144 / 48 /  0 /  0                      | --
+        302x151   | --                                      | 132 / 24 / 36 /  0
+        1024x512  |   0 / 96 / 20 / 76                      | --
+        1022x511  | --                                      |   0 / 36 / 60 / 96
+    """
     lay = PL.config_layout("C1")
     fuser.set_tiles(lay)
     tiles, total = O.make_tiles(lay)
     B = 19
     seeds = pf_synth.seeds_for(B, 777)
     resp = pf_synth.responses(seeds, lay.ntiles)
-    for (pw, ph) in ((512, 256), (300, 150), (302, 151)):
+    for (pw, ph) in ((512, 256), (300, 150), (302, 151), (1024, 512), (1022, 511)):
         gt = pf_synth.scene_depth(seeds, pw, ph).numpy()
         out = torch.zeros((B, total), dtype=torch.float32, device=DEV)
         fuser.warp_depth(_dev(gt), out, panofuse.make_responses(resp, DEV))

@@ -3,7 +3,7 @@
 Usage: python tools/pmc_traffic.py gpurun_out [out.json]
 
 Groups dispatches by kernel family (k_jlag = every Jacobi pass of every level, the unit bench.py's
-roofline aggregates over; k_warp_depth; k_targets_map; ...) and prints, per launch:
+roofline aggregates over; k_warp_depth; k_targets_multi; ...) and prints, per launch:
   fetch_size_B  FETCH_SIZE (KB -> B) as rocprofv3 reports it
   rdreq_B       32*RDREQ_32B + 64*RDREQ_64B + 128*RDREQ_128B + 64*(other RDREQ)  (request sizes)
   write_B       WRITE_SIZE (KB -> B)

@@ -36,12 +36,6 @@ void pf_destroy(pf_ctx* c)
         (void)hipEventDestroy(s.b);
     }
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-    if (c->aux) {
-        (void)hipStreamSynchronize(c->aux);
-        (void)hipStreamDestroy(c->aux);
-        (void)hipEventDestroy(c->ev_fork);
-        for (hipEvent_t e : c->ev_tgt) (void)hipEventDestroy(e);
-    }
     for (hipEvent_t e : c->ev_level)
         if (e) (void)hipEventDestroy(e);
     if (c->jres_err_h) (void)hipHostFree(c->jres_err_h);

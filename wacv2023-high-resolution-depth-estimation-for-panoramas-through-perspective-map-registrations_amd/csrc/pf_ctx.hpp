@@ -89,7 +89,7 @@ struct pf_ctx {
     // first use
     int wmap_pw = 0, wmap_ph = 0, npatch = 0;
     pf::DevBuf wmap, wfxy, wpatch, wunits;  // wunits: the ragged footprints' unit table
-    std::vector<pf::WarpPatch> wpatch_grid_h;  // the layout's plain 32x32 patch grid
+    std::vector<pf::WarpPatch> wpatch_grid_h;  // the layout's plain 64x32 patch grid
     // workspace
     pf::DevBuf buf[3], lnorm, coeffs, lsum_ws, metrics_ws, reg_sums, reg_active;
     pf::DevBuf audit_ws;    // pf_layout_audit: the counter words
@@ -137,9 +137,6 @@ struct pf_ctx {
     bool prof_on = false;
     std::vector<Span> spans;
     std::vector<hipEvent_t> event_pool;
-    // side stream for the finer levels' target planes (fuse_range), created on first use
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_tgt[4] = {};
     // end of each level's sweeps in the last fusion (pf_stream_wait_level), created on first use
     hipEvent_t ev_level[4] = {};
     int nlev_recorded = 0;

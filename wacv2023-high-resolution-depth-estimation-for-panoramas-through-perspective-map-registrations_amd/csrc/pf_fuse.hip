@@ -170,20 +170,6 @@ float* pf::run_jacobi(pf_ctx* c, const LevelDims& L, const JacobiRun& r, int* np
     return src;
 }
 
-// Side stream (lowest priority) and its fork/join events, created once per context.
-static int ensure_aux(pf_ctx* c)
-{
-    if (c->aux) return PF_OK;
-    int least = 0, greatest = 0;
-    HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-    const char* pr = getenv("PF_AUXPRIO");  // A/B runs: "high" | "default" (else lowest)
-    const int prio = pr && !strcmp(pr, "high") ? greatest : (pr && !strcmp(pr, "default") ? 0 : least);
-    HIPCHK(c, hipStreamCreateWithPriority(&c->aux, hipStreamNonBlocking, prio));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    for (hipEvent_t& e : c->ev_tgt) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    return PF_OK;
-}
-
 // Floats of the per-level target planes of one panorama (fuse_range's lnorm workspace).
 static long long target_planes(const LevelCache& lc)
 {
@@ -197,10 +183,7 @@ static long long target_planes(const LevelCache& lc)
 // plane per level (level l at lnorm_ws + batch * sum_{k<l} st_k), target_planes() * batch floats.
 //
 // The target planes depend only on the tiles and the coefficients, not on any Jacobi result, so
-// the finer levels' planes are gathered on a low-priority side stream while the coarse levels
-// sweep: the level-0 and level-1 passes fill ~2 waves per SIMD (a 512- or 1024-wide band per
-// panorama), leaving room for the gathers.  With the stage timers on, everything stays on
-// c->stream so that every stage's time is its own.
+// every level's plane is gathered first, in one launch (k_targets_multi).
 static int fuse_range(pf_ctx* c, const float* emap, int ew, int eh, int ec, const float* tiles,
                       const float* coeffs, int batch, int out_w, int out_h, uint16_t* out,
                       float* const ws[3], float* lnorm_ws)
@@ -210,8 +193,8 @@ static int fuse_range(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
     float* bufs[3] = {ws[0], ws[1], ws[2]};
     float* prev = nullptr;
     LevelCache& lc = c->lc;
+    // PF_JACOBI=naive: one launch per sweep (the form a level with jacobi_tcap(L) < 1 runs)
     static const bool naive = getenv("PF_JACOBI") && strcmp(getenv("PF_JACOBI"), "naive") == 0;
-    static const bool noside = getenv("PF_NOSIDE") != nullptr;  // A/B runs
     float* lnl[4] = {};
     {
         long long off = 0;
@@ -220,34 +203,7 @@ static int fuse_range(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
             off += (long long)lc.dims[l].w * lc.dims[l].h * batch;
         }
     }
-    auto targets = [&](int l, hipStream_t s) {
-        const LevelDims& L = lc.dims[l];
-        const long long st = (long long)L.w * L.h;
-        const GridCol* cols = (const GridCol*)lc.cols[l].p;
-        const GridRow* rows = (const GridRow*)lc.rows[l].p;
-        // PF_TARGETS=direct|map selects the older per-pixel gathers (A/B tuning runs)
-        static const char* tsel = getenv("PF_TARGETS");
-        static const bool direct = tsel && strcmp(tsel, "direct") == 0;
-        static const bool permap = tsel && strcmp(tsel, "map") == 0;
-        if (direct)
-            launch_targets(s, (const TileGeom*)c->geom.p, (const TileBox*)lc.box[l].p, 0,
-                           c->ntiles, cols, rows, tiles, c->tile_elems, coeffs, c->ntiles, L,
-                           lnl[l], st, batch);
-        else if (!permap)
-            launch_targets_patch(s, (const TileGeom*)c->geom.p, (const TileBox*)lc.box[l].p,
-                                 (const TapBox*)lc.tapbox[l].p, c->ntiles,
-                                 (const int32_t*)lc.tapmap[l].p, tiles, c->tile_elems, coeffs, L,
-                                 lnl[l], st, batch);
-        else
-            launch_targets_map(s, (const TileGeom*)c->geom.p, (const TileBox*)lc.box[l].p,
-                               (const TapBox*)lc.tapbox[l].p, c->ntiles,
-                               (const int32_t*)lc.tapmap[l].p, tiles, c->tile_elems, coeffs, L,
-                               lnl[l], st, batch);
-    };
-    // PF_TGT_MULTI=0: the per-level target launches (levels 1+ on the side stream) -- A/B runs
-    static const bool multi = !(getenv("PF_TGT_MULTI") && atoi(getenv("PF_TGT_MULTI")) == 0) &&
-                              !naive && !(getenv("PF_TARGETS"));
-    if (multi) {
+    {
         TgtMulti M{};
         M.nlev = lc.nlevels;
         M.nentries = lc.tgt_nentries;
@@ -272,19 +228,6 @@ static int fuse_range(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
         launch_targets_multi(c->stream, (const TileGeom*)c->geom.p, c->ntiles, tiles,
                              c->tile_elems, coeffs, M, (const int2*)lc.tgt_order.p, batch);
     }
-    const bool side = !multi && !c->prof_on && !noside && lc.nlevels > 1;
-    if (side) {
-        int rc;
-        if ((rc = ensure_aux(c))) return rc;
-        // the side stream starts after everything queued so far on c->stream (tiles, coeffs,
-        // and the previous call's reads of these planes)
-        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_fork, 0));
-        for (int l = 1; l < lc.nlevels; l++) {
-            targets(l, c->aux);
-            HIPCHK(c, hipEventRecord(c->ev_tgt[l], c->aux));
-        }
-    }
     for (int l = 0; l < lc.nlevels; l++) {
         const LevelDims& L = lc.dims[l];
         const long long st = (long long)L.w * L.h;
@@ -302,16 +245,6 @@ static int fuse_range(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
         const GridCol* cols = (const GridCol*)lc.cols[l].p;
         const GridRow* rows = (const GridRow*)lc.rows[l].p;
         float* const lnorm_l = lnl[l];
-        if (multi) {
-            // gathered above, for every level
-        } else if (side && l > 0) {
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_tgt[l], 0));
-        } else {
-            // algorithmic bytes: one 4-B tile texel per tap-grid point (k_targets_patch gathers
-            // each once; coarse levels touch a fraction of the tiles) + the 4-B L plane write
-            StageTimer t(c, PF_STAGE_TARGETS, B * (4.0 * band + 4.0 * (double)lc.taps[l]), 1);
-            targets(l, c->stream);
-        }
         float* res = nullptr;
         if (naive || jacobi_tcap(L) < 1) {
             show_sweeps_plan(L, batch);

@@ -91,11 +91,8 @@ struct RgbPatch {
     int wide;   // even one row's footprint exceeds the LDS slot: direct corner gathers
     int pad[2];
 };
-#ifndef PF_RGB_PW
-#define PF_RGB_PW 64
-#endif
 // RGB warp patch: 256 threads x 4 consecutive pixels of one row (kRgbPW / 4 lanes per row)
-static constexpr int kRgbPW = PF_RGB_PW, kRgbPH = 1024 / kRgbPW;
+static constexpr int kRgbPW = 64, kRgbPH = 1024 / kRgbPW;
 static constexpr int kRgbUnits = 512;            // 16-B units per patch (two per thread)
 static constexpr int kRgbCap = 16 * kRgbUnits;   // LDS bytes per parity: the u8 RGB rows as is
 
@@ -105,13 +102,13 @@ struct Resp {
     uint32_t seed, pad;
 };
 
-// One square patch of a tile for the E->P depth warp (pf_warp.hip): its tile pixels and the
+// One 64x32 patch of a tile for the E->P depth warp (pf_warp.hip): its tile pixels and the
 // azimuth-unwrapped panorama box their bilinear corners fall in (filled on the device).
 struct WarpPatch {
     int tile, X0, Y0;
     int gx0, gy0, bw, bh;  // box origin (column mod pw, row) and size, +1 row/column
     int wide;              // box larger than the LDS staging capacity: direct gathers
-    // ragged footprint (round 5, the default when pw % 4 == 0): the 16-B units of the panorama
+    // ragged footprint (round 5, the form whenever pw % 4 == 0): the 16-B units of the panorama
     // rows the patch's corners read, each row only over its corners' columns, listed as byte
     // offsets at unit_tbl[uoff .. uoff + units) (warp_patches_host); 0 units = the box above
     int uoff, units;
@@ -268,10 +265,6 @@ static constexpr int kAuditWords = 6;
 void launch_layout_audit(hipStream_t s, const TileGeom* geom, const TileBox* box, int ntiles,
                          const GridCol* cols, const GridRow* rows, LevelDims L,
                          unsigned long long* ctr);
-void launch_targets_map(hipStream_t s, const TileGeom* geom, const TileBox* box,
-                        const TapBox* tb, int ntiles, const int32_t* map, const float* tiles,
-                        long long tstride, const float* coeffs, LevelDims L, float* lnorm,
-                        long long lstride, int batch);
 void launch_targets_patch(hipStream_t s, const TileGeom* geom, const TileBox* box,
                           const TapBox* tb, int ntiles, const int32_t* map, const float* tiles,
                           long long tstride, const float* coeffs, LevelDims L, float* lnorm,
@@ -313,11 +306,6 @@ void launch_seed0(hipStream_t s, const float* emap, int ew, int eh, int ec, long
                   long long bstride, int batch);
 void launch_upsample(hipStream_t s, const float* prev, long long pstride, LevelDims L,
                      float* buf, long long bstride, int batch);
-void launch_targets(hipStream_t s, const TileGeom* geom, const TileBox* box, int t0, int t1,
-                    const GridCol* cols, const GridRow* rows, const float* tiles,
-                    long long tstride, const float* coeffs, int ntiles_total, LevelDims L,
-                    float* lnorm, long long lstride, int batch);
- // rows [r0,r1), -1: band
 // the tile masks of the level's targets patches (LevelCache::tmask, targets_patch_w/h grid)
 hipError_t launch_targets_partial(hipStream_t s, const TileGeom* geom, const TileBox* box,
                                 const TapBox* tb, const uint32_t* tmask, int nmw, int t0, int t1,

@@ -92,52 +92,6 @@ __device__ __forceinline__ bool in_box(const TileBox& bx, int X, int Y)
     return bx.xs > 0 ? (X >= bx.x0 && X < bx.x1) : (X <= bx.x0 && X > bx.x1);
 }
 
-// Targets + normalisation for the band rows [h0, h1] (Depth.cpp:1487-1647).  Gather form of
-// the reference's scatter: each pixel visits the tiles in index order, which is the reference's
-// single-thread accumulation order (and bit-identical to any order for coverage <= 2).
-// Output: normalised target, or PF_NAN_MARKER for an un-windowed pixel.
-__global__ void __launch_bounds__(kBlock) k_targets(const TileGeom* __restrict__ geom,
-                                                    const TileBox* __restrict__ box, int t0,
-                                                    int t1, const GridCol* __restrict__ cols,
-                                                    const GridRow* __restrict__ rows,
-                                                    const float* __restrict__ tiles,
-                                                    long long tstride,
-                                                    const float* __restrict__ coeffs,
-                                                    int ntiles_total, LevelDims L,
-                                                    float* __restrict__ lnorm,
-                                                    long long lstride)
-{
-    long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
-    long long nband = (long long)L.w * (L.h1 - L.h0 + 1);
-    if (i >= nband) return;
-    int b = blockIdx.y;
-    int Y = (int)(i / L.w) + L.h0, X = (int)(i - (long long)(Y - L.h0) * L.w);
-    const float* tb = tiles + b * tstride;
-    float acc = 0.0f;
-    int n = 0;
-    if (Y > L.h0 && Y < L.h1) {
-        for (int p = t0; p < t1; p++) {
-            TileBox bx = box[p];
-            if (!in_box(bx, X, Y)) continue;
-            const TileGeom& g = geom[p];
-            float4 abcd = make_float4(0, 0, 0, 0);
-            bool xf = coeffs != nullptr;
-            if (xf) abcd = *reinterpret_cast<const float4*>(coeffs + ((long long)b * ntiles_total + p) * 4);
-            acc += target_one(g, tb + g.off, cols, rows, X, Y, xf, abcd);
-            n++;
-        }
-    }
-    float out;
-    if (n == 0) out = bits_f(PF_NAN_MARKER);
-    else if (n == 1) out = acc;
-    else {
-        float center = 0.0f;
-        for (int k = 0; k < n; k++) center += 1.0f;
-        out = acc * (1.0f / center);
-    }
-    lnorm[b * lstride + (long long)Y * L.w + X] = out;
-}
-
 __global__ void __launch_bounds__(kBlock) k_normalize(const float* __restrict__ lsum,
                                                       const float* __restrict__ cnt,
                                                       LevelDims L, float* __restrict__ lnorm,
@@ -794,16 +748,6 @@ void launch_upsample(hipStream_t s, const float* prev, long long pstride, LevelD
 {
     dim3 grid(nblocks((long long)L.w * L.h), batch);
     hipLaunchKernelGGL(k_upsample, grid, dim3(kBlock), 0, s, prev, pstride, L, buf, bstride);
-}
-
-void launch_targets(hipStream_t s, const TileGeom* geom, const TileBox* box, int t0, int t1,
-                    const GridCol* cols, const GridRow* rows, const float* tiles,
-                    long long tstride, const float* coeffs, int ntiles_total, LevelDims L,
-                    float* lnorm, long long lstride, int batch)
-{
-    dim3 grid(nblocks((long long)L.w * (L.h1 - L.h0 + 1)), batch);
-    hipLaunchKernelGGL(k_targets, grid, dim3(kBlock), 0, s, geom, box, t0, t1, cols, rows, tiles,
-                       tstride, coeffs, ntiles_total, L, lnorm, lstride);
 }
 
 void launch_coverage_rows(hipStream_t s, const TileBox* box, int ntiles, LevelDims L, float* cnt,

@@ -8,15 +8,14 @@
 //     grid point of its box plus a one-pixel ring, the tile element index the reference's
 //     Value() reads -- five correctly rounded divisions per point, done once instead of five
 //     times per pixel and once per panorama.
-//  2. k_targets_map (per call): for each band pixel, the covering tiles (index order, as the
-//     reference's single-thread accumulation), five index loads from the map, and for
-//     kTgtBatch panoramas at a time the five tile gathers (+ the fused Depth2DepthTransform),
-//     the weighted sum in std::map key order and the normalisation of Depth.cpp:1626-1647.
+//  2. targets_patch (per call; k_targets_multi runs it for every level in one launch): per
+//     patch of band pixels and kTNB panoramas at a time, the covering tiles in index order (the
+//     reference's single-thread accumulation); per tile the tap values of the patch plus a
+//     one-pixel ring gathered through the map (+ the fused Depth2DepthTransform) into LDS, the
+//     five-point sums in std::map key order, then the normalisation of Depth.cpp:1626-1647.
 #include "pf_internal.hpp"
 
 namespace pf {
-
-static constexpr int kTgtBatch = 8;
 
 __global__ void __launch_bounds__(256) k_tapmap(const TileGeom* __restrict__ geom,
                                                 const TapBox* __restrict__ tb, int ntiles,
@@ -139,112 +138,20 @@ __global__ void __launch_bounds__(256) k_layout_audit(const TileGeom* __restrict
     }
 }
 
-template <bool XFORM>
-__global__ void __launch_bounds__(256) k_targets_map(const TileGeom* __restrict__ geom,
-                                                     const TileBox* __restrict__ box,
-                                                     const TapBox* __restrict__ tb, int ntiles,
-                                                     const int32_t* __restrict__ map,
-                                                     const float* __restrict__ tiles,
-                                                     long long tstride,
-                                                     const float* __restrict__ coeffs,
-                                                     LevelDims L, float* __restrict__ lnorm,
-                                                     long long lstride, int batch)
-{
-    // XCD-contiguous runs of band rows: the N/C/S taps of neighbouring rows read the same tile
-    // lines, and so do horizontally adjacent blocks.
-    const unsigned lb = xcd_remap(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * gridDim.y);
-    const unsigned bx = lb % gridDim.x, by = lb / gridDim.x;
-    const long long i = (long long)bx * 256 + threadIdx.x;
-    const long long nband = (long long)L.w * (L.h1 - L.h0 + 1);
-    if (i >= nband) return;
-    const int Y = (int)(i / L.w) + L.h0, X = (int)(i - (long long)(Y - L.h0) * L.w);
-    const long long o = (long long)Y * L.w + X;
-    const int bbeg = by * kTgtBatch;
-    float acc[kTgtBatch];
-#pragma unroll
-    for (int q = 0; q < kTgtBatch; q++) acc[q] = 0.0f;
-    int n = 0;
-    if (Y > L.h0 && Y < L.h1) {
-        for (int p = 0; p < ntiles; p++) {
-            if (!in_box2(box[p], X, Y)) continue;
-            const TapBox B = tb[p];
-            const long long base = B.off + (long long)(Y - B.ymin) * B.nx + (X - B.xmin);
-            // taps in std::map key order: (X-1,Y), (X,Y-1), (X,Y), (X,Y+1), (X+1,Y)
-            const int32_t iw = map[base - 1], in = map[base - B.nx], ic = map[base],
-                          is = map[base + B.nx], ie = map[base + 1];
-            const long long toff = geom[p].off;
-            float v[kTgtBatch][5];
-#pragma unroll
-            for (int q = 0; q < kTgtBatch; q++) {
-                const int b = bbeg + q < batch ? bbeg + q : batch - 1;
-                const float* t = tiles + b * tstride + toff;
-                v[q][0] = t[iw]; v[q][1] = t[in]; v[q][2] = t[ic]; v[q][3] = t[is]; v[q][4] = t[ie];
-            }
-#pragma unroll
-            for (int q = 0; q < kTgtBatch; q++) {
-                if constexpr (XFORM) {
-                    const int b = bbeg + q < batch ? bbeg + q : batch - 1;
-                    const float4 k = *reinterpret_cast<const float4*>(coeffs + ((long long)b * ntiles + p) * 4);
-#pragma unroll
-                    for (int m = 0; m < 5; m++) v[q][m] = cubic_map(v[q][m], k.x, k.y, k.z, k.w);
-                }
-                float Lp = 0;
-                Lp += v[q][0] * -0.25f;
-                Lp += v[q][1] * -0.25f;
-                Lp += v[q][2] * 1.0f;
-                Lp += v[q][3] * -0.25f;
-                Lp += v[q][4] * -0.25f;
-                acc[q] += Lp;
-            }
-            n++;
-        }
-    }
-    float scale = 1.0f;
-    if (n > 1) {
-        float center = 0.0f;
-        for (int k = 0; k < n; k++) center += 1.0f;
-        scale = 1.0f / center;
-    }
-#pragma unroll
-    for (int q = 0; q < kTgtBatch; q++) {
-        const int b = bbeg + q;
-        if (b >= batch) break;
-        float out;
-        if (n == 0) out = __uint_as_float(PF_NAN_MARKER);
-        else if (n == 1) out = acc[q];
-        else out = acc[q] * scale;
-        lnorm[b * lstride + o] = out;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
-// Patch-staged form (the default).  Every fusion-grid point is a tap of up to five stencils, so
-// gathering per pixel reads each tile value five times.  Here a block owns a kTPW x kTPH patch of
-// band pixels and kTNB panoramas; for every tile whose box meets the patch (index order), the tap
+// Patch-staged gather.  Every fusion-grid point is a tap of up to five stencils, so gathering
+// per pixel reads each tile value five times.  Here a block owns a kTPW x kTPH patch of band
+// pixels and kTNB panoramas; for every tile whose box meets the patch (index order), the tap
 // values of the patch plus a one-pixel ring are gathered once per grid point, transformed once
-// (Depth2DepthTransform), staged in LDS, and the five-point stencils read LDS.  The per-pixel
-// arithmetic and the tile-order accumulation are exactly those of k_targets_map.
+// (Depth2DepthTransform), staged in LDS, and the five-point stencils read LDS.
 // patch height: 8 rows (2 pixels per thread) stages 1.29 grid points per pixel instead of 1.55
-// at 4 rows; measured at C3 (profiles/r02 logs; recipe: tools/gpu_round.sh ab): 4 rows 0.687 ms, 8 rows 0.635, 16 rows 0.670
-#ifndef PF_TGT_PH
-#define PF_TGT_PH 8
-#endif
-static constexpr int kTPW = 64, kTPH = PF_TGT_PH;                // patch of kTPW x kTPH pixels
+// at 4 rows; measured at C3 (profiles/r02 logs): 4 rows 0.687 ms, 8 rows 0.635, 16 rows 0.670
+static constexpr int kTPW = 64, kTPH = 8;                        // patch of kTPW x kTPH pixels
 static constexpr int kTPP = kTPW * kTPH / 256;                   // pixels per thread
 static constexpr int kTGW = kTPW + 2, kTGH = kTPH + 2, kTG = kTGW * kTGH;  // grid points + ring
-#ifndef PF_TGT_NB
-#define PF_TGT_NB 8
-#endif
-static constexpr int kTNB = PF_TGT_NB;                           // panoramas per block
-#ifndef PF_TGT_DIAG
-#define PF_TGT_DIAG 0  // probes only (wrong output, timing): bit 0 = no tile gathers, bit 1 = no stores
-#endif
-#ifndef PF_TGT_NT
-// nt stores of the target planes keep the tiles' lines in L2 for the neighbouring patches: the
-// stage went 0.629-0.633 -> 0.618-0.623 ms per C3 step (profiles/r03/tgt and profiles/r03/jnt; recipe: tools/gpu_round.sh ab, profiles/r03/tgt/);
-// 4 / 16 panoramas per block measured 0.639-0.651 / 0.730
-#define PF_TGT_NT 1
-#endif
+// panoramas per block: 4 / 16 measured 0.639-0.651 / 0.730 ms per C3 step against 0.618-0.623
+// (profiles/r03/tgt)
+static constexpr int kTNB = 8;
 
 // One block's work: patch `pid` of level L for panoramas [bgrp*NB, +NB).
 template <bool XFORM, int NB>
@@ -256,9 +163,8 @@ __device__ __forceinline__ void targets_patch(const TileGeom* __restrict__ geom,
                                               const float* __restrict__ coeffs, const LevelDims& L,
                                               int npx, int pid, int bgrp,
                                               float* __restrict__ lnorm, long long lstride,
-                                              int batch, float (*sv0)[kTG],
-                                              const uint32_t* __restrict__ tmask = nullptr,
-                                              int nmw = 0, float (*sv1)[kTG] = nullptr)
+                                              int batch, float (*sv)[kTG],
+                                              const uint32_t* __restrict__ tmask, int nmw)
 {
     const int X0 = (pid % npx) * kTPW, Y0 = L.h0 + (pid / npx) * kTPH;
     const int t = threadIdx.x;
@@ -275,12 +181,7 @@ __device__ __forceinline__ void targets_patch(const TileGeom* __restrict__ geom,
     const int X1 = min(X0 + kTPW - 1, L.w - 1), Y1 = min(Y0 + kTPH - 1, L.h1);
     // one tile's contribution to the patch (tiles come in index order: the reference's
     // accumulation order); `last`: no staging follows, so no barrier after the stencils
-    // sv1 (PF_TGT_DBUF): tiles alternate between two staging buffers, so a tile's staging never
-    // overwrites what the previous tile's stencils read and one barrier per tile suffices
-    int nt = 0;
     auto tile = [&](const int p, const bool last) {
-        float (*sv)[kTG] = (sv1 && (nt & 1)) ? sv1 : sv0;
-        nt++;
         const TileBox bx = box[p];
         const TapBox B = tb[p];
         const long long toff = geom[p].off;
@@ -301,8 +202,7 @@ __device__ __forceinline__ void targets_patch(const TileGeom* __restrict__ geom,
 #pragma unroll
             for (int q = 0; q < NB; q++) {
                 const int b = bbeg + q < batch ? bbeg + q : batch - 1;
-                if constexpr ((PF_TGT_DIAG & 1) != 0) v[q] = (float)(m & 1023) * 1e-3f + (float)b;
-                else v[q] = tiles[b * tstride + toff + m];
+                v[q] = tiles[b * tstride + toff + m];
             }
 #pragma unroll
             for (int q = 0; q < NB; q++) {
@@ -332,7 +232,7 @@ __device__ __forceinline__ void targets_patch(const TileGeom* __restrict__ geom,
                 n[j]++;
             }
         }
-        if (!last && !sv1) __syncthreads();  // the next tile's staging overwrites sv
+        if (!last) __syncthreads();  // the next tile's staging overwrites sv
     };
     if (tmask) {  // the host's list of the tiles whose box meets this patch, as mask words
         int left = 0;  // tiles still to come (block-uniform)
@@ -367,13 +267,9 @@ __device__ __forceinline__ void targets_patch(const TileGeom* __restrict__ geom,
             if (n[j] == 0) out = __uint_as_float(PF_NAN_MARKER);
             else if (n[j] == 1) out = acc[j][q];
             else out = acc[j][q] * scale;
-            if constexpr ((PF_TGT_DIAG & 2) != 0) {
-                if (out == -12345.0f) lnorm[b * lstride + o] = out;  // probe: no stores
-            } else if constexpr (PF_TGT_NT) {
-                __builtin_nontemporal_store(out, &lnorm[b * lstride + o]);
-            } else {
-                lnorm[b * lstride + o] = out;
-            }
+            // nt: the planes' stores keep the tiles' lines in L2 for the neighbouring patches
+            // (0.629-0.633 -> 0.618-0.623 ms per C3 step, profiles/r03/tgt)
+            __builtin_nontemporal_store(out, &lnorm[b * lstride + o]);
         }
     }
 }
@@ -408,9 +304,6 @@ __global__ void __launch_bounds__(256) k_targets_patch(const TileGeom* __restric
 // finest level's patches come first, then each coarser level's patches of the same band (a host
 // table of (level, patch) entries).  The XCD-contiguous mapping gives every XCD a contiguous run
 // of the table, so a band's lines are re-read from its L2 / the MALL instead of HBM.
-#ifndef PF_TGT_DBUF
-#define PF_TGT_DBUF 0  // two staging buffers, one barrier per covering tile (A/B)
-#endif
 template <bool XFORM, int NB>
 __global__ void __launch_bounds__(256) k_targets_multi(const TileGeom* __restrict__ geom,
                                                        int ntiles, const float* __restrict__ tiles,
@@ -419,14 +312,13 @@ __global__ void __launch_bounds__(256) k_targets_multi(const TileGeom* __restric
                                                        TgtMulti M, const int2* __restrict__ order,
                                                        int batch)
 {
-    __shared__ float sv[PF_TGT_DBUF ? 2 * NB : NB][kTG];
+    __shared__ float sv[NB][kTG];
     const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
     const int e = (int)(lb % (unsigned)M.nentries), bgrp = (int)(lb / (unsigned)M.nentries);
     const int2 ent = order[e];  // (level, patch)
     const TgtLevel& T = M.lv[ent.x];
     targets_patch<XFORM, NB>(geom, T.box, T.tb, ntiles, T.map, tiles, tstride, coeffs, T.L, T.npx,
-                         ent.y, bgrp, T.lnorm, T.lstride, batch, sv, T.tmask, T.nmw,
-                         PF_TGT_DBUF ? sv + NB : nullptr);
+                             ent.y, bgrp, T.lnorm, T.lstride, batch, sv, T.tmask, T.nmw);
 }
 
 int targets_patch_w() { return kTPW; }
@@ -507,7 +399,7 @@ void launch_tapmap(hipStream_t s, const TileGeom* geom, const TapBox* tb, int nt
 
 // Partial sums of tiles [t0, t1) for one panorama on rows [r0, r1) of the band (pf_fuse_partial,
 // pf_fuse_partial_rows: the sharded fusion): lsum = the tiles' Laplacians added in tile order,
-// cnt = how many, with k_targets_map's per-pixel arithmetic.  Staged like targets_patch, for one
+// cnt = how many, with targets_patch's per-pixel arithmetic.  Staged like targets_patch, for one
 // panorama: a block owns one patch of the level's targets grid (kTPW x kTPH from row h0, the
 // grid of the host's per-patch tile masks) and, for every tile of the range whose box meets the
 // patch (the mask words ANDed with the range, index order), gathers the tap values of the patch
@@ -627,21 +519,6 @@ hipError_t launch_targets_partial(hipStream_t s, const TileGeom* geom, const Til
         hipLaunchKernelGGL(k_targets_patch_partial<false>, dim3(g), dim3(256), 0, s, geom, box, tb,
                            tmask, nmw, t0, t1, map, tiles, coeffs, L, lsum, cnt, r0, r1, npx, py0);
     return hipGetLastError();
-}
-
-void launch_targets_map(hipStream_t s, const TileGeom* geom, const TileBox* box,
-                        const TapBox* tb, int ntiles, const int32_t* map, const float* tiles,
-                        long long tstride, const float* coeffs, LevelDims L, float* lnorm,
-                        long long lstride, int batch)
-{
-    long long nband = (long long)L.w * (L.h1 - L.h0 + 1);
-    dim3 grid((unsigned)((nband + 255) / 256), (batch + kTgtBatch - 1) / kTgtBatch);
-    if (coeffs)
-        hipLaunchKernelGGL(k_targets_map<true>, grid, dim3(256), 0, s, geom, box, tb, ntiles, map,
-                           tiles, tstride, coeffs, L, lnorm, lstride, batch);
-    else
-        hipLaunchKernelGGL(k_targets_map<false>, grid, dim3(256), 0, s, geom, box, tb, ntiles, map,
-                           tiles, tstride, coeffs, L, lnorm, lstride, batch);
 }
 
 }  // namespace pf

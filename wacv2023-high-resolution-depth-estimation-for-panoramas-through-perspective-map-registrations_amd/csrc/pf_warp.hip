@@ -8,16 +8,20 @@
 //
 //  1. warp_coords_host: per tile pixel the bilinear corner (x0, y0) and weights (fx, fy), on the
 //                    host with glibc atan2f as the reference calls it (bit-exact maps).
-//  2. k_patch_box:   tiles are cut into 32x32-pixel patches; per patch the panorama footprint
-//                    (an azimuth-unwrapped box, <= kCap floats, or "wide").
-//  3. k_warp_local:  per tile pixel the corner's index inside its patch's footprint box (or the
-//                    global index with edge flags for a wide patch).
+//  2. Tiles are cut into kPatch x kPatchH (64x32) pixel patches, and per patch the panorama
+//     footprint of its corners is laid out for LDS, in one of two forms:
+//     - pw % 4 == 0: warp_patches_host lists the ragged footprint as 16-B units (<= kCap floats,
+//       or "wide") and gives every pixel its two LDS indices;
+//     - else: k_patch_box finds the azimuth-unwrapped bounding box (<= kCap floats, or "wide")
+//       and k_warp_local the corner's index inside it, staged with 4-B loads.
+//     A wide patch keeps global corner indices with edge flags.
 //
 // k_warp_depth: one block per (patch, chunk of kNB panoramas).  Per panorama the block copies the
-// footprint box from HBM into LDS with plain coalesced row loads (double-buffered: the loads for
-// panorama q+1 are in flight while panorama q is interpolated), then every pixel reads its four
-// corners from LDS.  The box is ~0.4x the panorama's bytes per panorama (vs ~4 scattered corner
-// loads per tile pixel from L2 in a direct gather), so the kernel is bound by the tile writes.
+// footprint from HBM into LDS with plain coalesced loads (double-buffered: the loads for
+// panorama q+2 are in flight while panorama q is interpolated), then every pixel reads its four
+// corners from LDS.  The footprint is ~0.4x the panorama's bytes per panorama (vs ~4 scattered
+// corner loads per tile pixel from L2 in a direct gather), so the kernel is bound by the tile
+// writes.  The forms that were measured and not kept are in DESIGN.md 3 ("E->P warp").
 //
 // Edge rule: the reference clamps x1 = min(x0+1, pw-1), y1 = min(y0+1, ph-1).  x0 == pw-1 only
 // when px == pw-1 exactly (az < 2*MYPI), i.e. fx == 0, and likewise y0 == ph-1 means fy == 0; the
@@ -34,80 +38,20 @@
 
 namespace pf {
 
-#ifndef PF_WARP_WB
-#define PF_WARP_WB 256
-#endif
-#ifndef PF_WARP_PATCH
-#define PF_WARP_PATCH 64
-#endif
-#ifndef PF_WARP_WAVEBOX
-// one 32x8 patch per WAVE with its own LDS box and no workgroup barrier (waves drift and overlap
-// each other's latencies) instead of one 32x32 patch per 256-thread block with a barrier per
-// panorama (SQ counters: ~20% of the block form's wave-cycles wait at barriers).  Measured
-// slower on MI355X at C3 (profiles/r03/warp/wb*.log; recipe: tools/gpu_round.sh ab): 0.69 ms with 1024-float wave boxes, 0.83 with 512,
-// against 0.53 for the block form (bit-identical tiles) -- the small boxes re-read more and send
-// more patches to the direct-gather path.  Off.
-#define PF_WARP_WAVEBOX 0
-#endif
-static constexpr int kWB = PF_WARP_WB;                  // threads per block
-static constexpr int kPatch = PF_WARP_PATCH;            // patch width in tile pixels
-#ifndef PF_WARP_PATCHH
-// Round 6: 64 x 32 patches (2048 pixels, 8 per thread) instead of 32 x 32.  Their ragged
-// footprints touch 37.9 cache lines per 1024 tile pixels instead of 47.4 (a host model of every
-// C3 patch; the footprint rows are longer, so fewer partial lines at the row ends): serial trace
-// 0.491-0.494 -> 0.478-0.481 ms per C3 launch; 64 x 16: 0.496-0.499 (46.2 lines); 64 x 32 with
-// 512 threads 0.481-0.484; 128 x 16 with 512 threads 0.478-0.481 (tools/gpu_round.sh serials)
-#define PF_WARP_PATCHH 32
-#endif
-static constexpr int kPatchH = PF_WARP_WAVEBOX ? 8 : PF_WARP_PATCHH;  // patch height
+// Sizes, measured on MI355X at C3: 64 x 32 patches touch 37.9 cache lines per
+// 1024 tile pixels against 47.4 for 32 x 32 (0.478-0.481 ms per launch against 0.491-0.494).
+static constexpr int kWB = 256;                         // threads per block
+static constexpr int kPatch = 64, kPatchH = 32;         // patch width and height in tile pixels
 static_assert(kWB % kPatch == 0 && kPatch * kPatchH % kWB == 0, "whole patch rows per slot");
-static_assert(!PF_WARP_WAVEBOX || (kPatch == 32 && kWB == 256), "wave boxes: 32x8 patches");
-static constexpr int kPx = kPatch * kPatchH / kWB;      // pixels per thread (prep passes)
-#ifndef PF_WARP_CAP
-#define PF_WARP_CAP 4096
-#endif
-static constexpr int kCapB = PF_WARP_CAP;               // LDS floats per parity per block
-static constexpr int kCap = PF_WARP_WAVEBOX ? kCapB / 4 : kCapB;  // per staged footprint
-static constexpr int kSlots = kCap / kWB;               // staging loads per thread
-static_assert(PF_WARP_WAVEBOX || kCap % (4 * kWB) == 0, "whole 16-B staging slots fill the box");
-#ifndef PF_WARP_BATCH
-#define PF_WARP_BATCH 16
-#endif
-static constexpr int kNB = PF_WARP_BATCH;               // panoramas per block
-// Memory operation widths and cache policy, measured on MI355X at C3 (tools/warp_probe.py,
-// profiles/r03/warp; recipe: tools/gpu_round.sh ab).  Round 2: 16-B staging loads 0.596 ms, 16-B row stores 0.600, both 0.637,
-// against 0.586 for 4-B loads and stores.  Round 3, with the split LDS parities: nt tile stores
-// 0.545-0.551 ms against 0.560-0.569 (written tiles no longer evict the staged boxes' lines from
-// L2), and 16-B staging loads on top 0.527-0.531 (kept: the defaults below); 16-B stores through
-// a wave-local LDS transpose 0.573-0.578, 16-B row stores 0.576-0.586 (not kept); 64x64 patches
-// 0.75-1.4 ms (more footprints exceed the LDS box); 5 blocks per CU (3840-float box, 96 VGPRs)
-// 0.539-0.541 without the 16-B loads.
-#ifndef PF_WARP_V4
-#define PF_WARP_V4 1     // quad-aligned footprint boxes staged with 16-B loads (pw % 4 == 0)
-#endif
-#ifndef PF_WARP_SPLIT
-// the two staging parities in separate LDS halves (consecutive lanes read/write consecutive
-// dwords: conflict-free) instead of interleaved (stride-2 dwords: 2-way bank conflicts, 64% of
-// the kernel's LDS-active cycles on MI355X, profiles/r03/warp/warp_sq_summary.txt; recipe: tools/gpu_round.sh pmc-style passes)
-#define PF_WARP_SPLIT 1
-#endif
-#ifndef PF_WARP_STPOL
-#define PF_WARP_STPOL 2  // cache policy bits of the tile stores (gfx950: 2 = nt, 16 = sc1)
-#endif
-#ifndef PF_WARP_PFD
-#define PF_WARP_PFD 2    // staging prefetch depth in panoramas (register sets in flight)
-#endif
-#ifndef PF_WARP_DIAG
-#define PF_WARP_DIAG 0   // probes only: 1 = no tile stores, 2 = no panorama loads (wrong output)
-#endif
-#ifndef PF_WARP_XPOSE
-// results pass through a wave-local LDS transpose so every lane stores its 4 pixels of one tile
-// row with one 16-B store (the compute keeps the 32-lanes-per-row mapping the box reads want)
-#define PF_WARP_XPOSE 0  // measured slower on MI355X (0.573-0.578 ms vs 0.527-0.528 at C3)
-#endif
-#ifndef PF_WARP_ROWPX
-#define PF_WARP_ROWPX 0  // a thread's pixels consecutive in one row: one 16-B store per panorama
-#endif
+static constexpr int kPx = kPatch * kPatchH / kWB;      // pixels per thread
+static constexpr int kCap = 4096;                       // LDS floats per staged footprint
+static constexpr int kSlots = kCap / kWB;               // 4-B staging loads per thread
+static_assert(kCap % (4 * kWB) == 0, "whole 16-B staging slots fill the box");
+static_assert(kSlots > 8, "the 4-B staging depths are 4, 8 and kSlots");
+static constexpr int kNB = 16;                          // panoramas per block
+// nt tile stores: the written tiles do not evict the staged footprints' lines from L2
+// (0.545-0.551 ms against 0.560-0.569)
+static constexpr int kStorePolicy = 2;                  // gfx950 cache policy bits: 2 = nt
 
 __device__ __forceinline__ uint32_t mix32(uint32_t x)
 {  // lowbias32 finaliser (the oracle's pfo_hash32)
@@ -176,7 +120,7 @@ static inline int wrap_du_h(int d, int pw)
     return d;
 }
 
-// Ragged footprints of the depth warp's 32x32 patches (round 5).  The bounding box of a patch's
+// Ragged footprints of the depth warp's patches (round 5).  The bounding box of a patch's
 // corners (k_patch_box) holds the empty corners of a rotated footprint and whole rows of
 // columns no corner of that row reads; here each panorama row v of the footprint is staged only
 // over the columns [xlo(v), xhi(v)] its corners use (pixels with y0 == v read their (x0, x0+1) on
@@ -188,14 +132,6 @@ void warp_patches_host(const TileGeom& g, int tile, const uint32_t* wxy, int pw,
                        uint32_t* loc)
 {
     const int cap = kCap / 4;  // 16-B units per staged footprint
-    // PF_WARP_ALIGN=n (A/B): each footprint row's units start and end on
-    // n-unit boundaries (8 = whole 128-B lines), so the 64 16-B loads of a wave instruction touch
-    // whole lines; the LDS box grows by the rounding
-    static const int align = [] {
-        const char* e = getenv("PF_WARP_ALIGN");
-        const int a = e ? atoi(e) : 1;
-        return a == 2 || a == 4 || a == 8 ? a : 1;
-    }();
     std::vector<int> xlo, xhi, q0, off;
     for (int Y0 = 0; Y0 < g.h; Y0 += kPatchH)
         for (int X0 = 0; X0 < g.w; X0 += kPatch) {
@@ -233,11 +169,7 @@ void warp_patches_host(const TileGeom& g, int tile, const uint32_t* wxy, int pw,
                     continue;
                 }
                 fits = xhi[r] - xlo[r] + 1 <= pw / 2;
-                long long a = floor_div(rx + xlo[r], 4), b = floor_div(rx + xhi[r] + 4, 4);
-                if (align > 1 && pw % (4 * align) == 0) {  // whole aligned groups of units
-                    a = floor_div(a, align) * align;
-                    b = floor_div(b + align - 1, align) * align;
-                }
+                const long long a = floor_div(rx + xlo[r], 4), b = floor_div(rx + xhi[r] + 4, 4);
                 q0[r] = (int)a;
                 off[r] = (int)nu;
                 nu += b - a;
@@ -309,14 +241,9 @@ void rgb_taps_host(const RgbCam& cam, int W, int H, int pw, int ph, RgbTap* taps
 
 __device__ __forceinline__ int patch_pixel(const WarpPatch& P, const TileGeom& g, int t, int k,
                                            int& i)
-{  // thread t, slot k -> tile pixel index i; returns 0 outside the tile.  A thread owns kPx
-   // consecutive pixels of one patch row (one 16-B store per panorama), a wave 8 whole rows.
-#if PF_WARP_ROWPX
-    static_assert(kPx == 4 && kPatch == 32, "4 pixels per thread, 8 threads per patch row");
-    const int X = P.X0 + 4 * (t & 7) + k, Y = P.Y0 + (t >> 3);
-#else  // a block covers kWB/kPatch whole rows per slot
+{  // thread t, slot k -> tile pixel index i; returns 0 outside the tile.  A block covers
+   // kWB/kPatch whole patch rows per slot, so a wave stores whole 256-B runs of a tile row.
     const int X = P.X0 + (t & (kPatch - 1)), Y = P.Y0 + t / kPatch + k * (kWB / kPatch);
-#endif
     i = Y * g.w + X;
     return X < g.w && Y < g.h;
 }
@@ -328,7 +255,8 @@ __device__ __forceinline__ int wrap_du(int d, int pw)
     return d;
 }
 
-// Pass 2: per patch the azimuth-unwrapped footprint box of all its corners (+1 row/column).
+// Pass 2 (pw % 4 != 0; else warp_patches_host): per patch the azimuth-unwrapped footprint box
+// of all its corners (+1 row/column).
 __global__ void __launch_bounds__(kWB) k_patch_box(const TileGeom* __restrict__ geom,
                                                    WarpPatch* __restrict__ patches, int pw,
                                                    const uint32_t* __restrict__ wxy)
@@ -356,15 +284,9 @@ __global__ void __launch_bounds__(kWB) k_patch_box(const TileGeom* __restrict__ 
     if (t == 0) {
         int gx0 = ref + red[0];
         gx0 = gx0 < 0 ? gx0 + pw : (gx0 >= pw ? gx0 - pw : gx0);
-        int bw = red[1] - red[0] + 2;
-        if (PF_WARP_V4 && (pw & 3) == 0) {  // 16-B staging loads: origin and width in quads
-            const int a = gx0 & 3;
-            gx0 -= a;
-            bw = (bw + a + 3) & ~3;
-        }
         P.gx0 = gx0;
         P.gy0 = red[2];
-        P.bw = bw;
+        P.bw = red[1] - red[0] + 2;
         P.bh = red[3] - red[2] + 2;
         P.wide = (P.bw * P.bh > kCap || P.bw > pw / 2) ? 1 : 0;
         patches[blockIdx.x] = P;
@@ -463,64 +385,48 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, uint32_
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
 }
 
-static constexpr int kLPx = PF_WARP_WAVEBOX ? 4 : kPx;  // pixels per lane in the main kernel
-struct WarpLanes {  // one thread's kLPx pixels, all panorama-invariant
-    uint32_t la[kLPx];  // LDS float index of corner (x0, y0) in the parity-interleaved box (x2)
-    uint32_t oo[kLPx];  // byte offset of the pixel inside one panorama's tile block; past the
-                        // block (a dropped buffer store) for lanes outside the tile
-    uint32_t hp[kLPx];  // mix32(pixel index): the per-pixel half of the noise hash
-    f2 wx[kLPx], wy[kLPx];  // (1-fx, fx), (1-fy, fy)
-    bool ok[kLPx];
-    bool full;  // the kPx pixels are inside the tile and contiguous (one channel): 16-B store
-    // XPOSE: oo[] are the byte offsets of the lane's 4 pixels AFTER the transpose (row
-    // 2*wave + (l>>3 & 1) + 8*(l>>4), columns 4*(l&7)..+3 of the patch); full = all inside,
-    // one channel, 16-B aligned
+struct WarpLanes {  // one thread's kPx pixels, all panorama-invariant
+    uint32_t la[kPx];  // LDS float index of corner (x0, y0) in the staged box; ragged: the top
+                       // pair's index | the bottom pair's << 16; wide: the global index | flags
+    uint32_t oo[kPx];  // byte offset of the pixel inside one panorama's tile block; past the
+                       // block (a dropped buffer store) for lanes outside the tile
+    uint32_t hp[kPx];  // mix32(pixel index): the per-pixel half of the noise hash
+    f2 wx[kPx], wy[kPx];  // (1-fx, fx), (1-fy, fy)
+    bool ok[kPx];
 };
 
-// LDS-staged interpolation of kNB panoramas for a box of at most NS*256 staging units (floats,
-// or with V4 column quads: 16-B loads of a box whose origin and width are whole quads, which
-// k_patch_box guarantees when pw % 4 == 0).  The box is double-buffered with the two parities
-// interleaved (element e of parity PA at box[2e + PA]), so a pixel's c00/c01 (and c10/c11) are
-// one ds_read2_b32 with immediate offsets in both parities.  Every staging load is issued
-// unconditionally (slots past the box reload a valid unit, panoramas past the chunk reload the
-// last one), so the loads for panorama q+2 go out before panorama q is interpolated and the wait
-// for panorama q+1's loads -- an in-order vmcnt -- never covers them.  A thread's four pixels
-// are consecutive in one tile row: one 16-B store per panorama when they are all inside.
-#ifndef PF_WARP_MASKU
-// 1: staging slots past a patch's footprint issue no load (exec-masked lanes) instead of
-// reloading a valid unit.  Measured (round 5, two alternating rounds, serial C3 steps): the
-// depth warp 0.510-0.516 ms against 0.501-0.502 unmasked; the RGB warp 0.668 ms against
-// 0.594-0.610 (the masks push it to 15 spilled VGPRs).  Off.
-#define PF_WARP_MASKU 0
-#endif
-#ifndef PF_RGB_MASKU
-#define PF_RGB_MASKU 0  // the same in the RGB warp
-#endif
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-#if !PF_WARP_WAVEBOX  // the block form (default)
-template <int NS, bool RESP, bool V4, bool RAG = false>
-__device__ __forceinline__ void warp_staged(float* box, float* xbuf, const RespK* rk,
-                                            const WarpPatch& P,
+
+// LDS-staged interpolation of kNB panoramas for a footprint of at most NS*kWB staging units: the
+// 16-B units of a ragged footprint (RAG: unit_tbl lists their byte offsets, and a pixel's bottom
+// corner pair sits on its own packed row) or the floats of a bounding box (4-B loads; the bottom
+// pair is P.bw floats after the top one).  The box is double-buffered with the two parities in
+// separate LDS halves: consecutive lanes read and write consecutive dwords, conflict-free (the
+// interleaved layout spent 64% of the LDS-active cycles in 2-way bank conflicts).
+// Every staging load is issued unconditionally (slots past the footprint reload its last unit,
+// panoramas past the chunk reload the last one: masking them measured slower), so the loads for
+// panorama q+2 go out before panorama q is interpolated and the wait for panorama q+1's loads
+// -- an in-order vmcnt -- never covers them.
+template <int NS, bool RESP, bool RAG>
+__device__ __forceinline__ void warp_staged(float* box, const RespK* rk, const WarpPatch& P,
                                             int t, const WarpLanes& W,
                                             const float* __restrict__ pano, int pw, int ph,
                                             long long pstride, float* __restrict__ tiles,
                                             long long tstride, int bbeg, int nb,
-                                            const uint32_t* __restrict__ unit_tbl = nullptr)
+                                            const uint32_t* __restrict__ unit_tbl)
 {
-    static_assert(!RAG || (V4 && PF_WARP_SPLIT), "ragged footprints: 16-B units, split parities");
-    constexpr int U = V4 ? 4 : 1;  // floats per staging unit
-    const int bw2 = 2 * P.bw, bwu = RAG ? 1 : P.bw / U, units = RAG ? P.units : bwu * P.bh;
-    uint32_t goff[NS];  // unit e = t + 256*s of the box -> panorama byte offset
-    bool live[NS];      // PF_WARP_MASKU: slots past the box load nothing (exec-masked lanes)
+    constexpr int U = RAG ? 4 : 1;  // floats per staging unit
+    static_assert(NS * U <= kSlots, "slot s writes LDS floats (t + s*kWB)*U .. < kCap");
+    const int units = RAG ? P.units : P.bw * P.bh;
+    uint32_t goff[NS];  // unit e = t + kWB*s of the footprint -> panorama byte offset
 #pragma unroll
     for (int s = 0; s < NS; s++) {
         int e = t + s * kWB;
-        live[s] = e < units;
         e = e < units ? e : units - 1;
         if constexpr (RAG) {
             goff[s] = unit_tbl[P.uoff + e];
         } else {
-            const int r = e / bwu, c = (e - r * bwu) * U;
+            const int r = e / P.bw, c = e - r * P.bw;
             int row = P.gy0 + r;
             row = row < ph ? row : ph - 1;
             int col = P.gx0 + c;
@@ -528,21 +434,16 @@ __device__ __forceinline__ void warp_staged(float* box, float* xbuf, const RespK
             goff[s] = (uint32_t)(row * pw + col) * 4u;
         }
     }
-    constexpr int D = PF_WARP_PFD;  // prefetch depth: panorama j is staged in stg[j % D]
-    float stg[D][NS][U];
+    float stg[2][NS][U];  // two panoramas in flight: panorama j is staged in stg[j % 2]
     const uint32_t pbytes = (uint32_t)(pstride * 4);
     auto fetch = [&](float (*dst)[U], int q) {
         const auto pr = rsrc(pano + (long long)(bbeg + (q < nb ? q : nb - 1)) * pstride, pbytes);
 #pragma unroll
         for (int s = 0; s < NS; s++) {
-            if constexpr (PF_WARP_DIAG == 2) {
-                for (int j = 0; j < U; j++) dst[s][j] = (float)(goff[s] & 1023u) * 1e-3f;
-            } else if constexpr (V4) {
-                if (!PF_WARP_MASKU || live[s]) {
-                    const u4v v = __builtin_amdgcn_raw_buffer_load_b128(pr, (int)goff[s], 0, 0);
+            if constexpr (RAG) {
+                const u4v v = __builtin_amdgcn_raw_buffer_load_b128(pr, (int)goff[s], 0, 0);
 #pragma unroll
-                    for (int j = 0; j < 4; j++) dst[s][j] = __uint_as_float(v[j]);
-                }
+                for (int j = 0; j < 4; j++) dst[s][j] = __uint_as_float(v[j]);
             } else {
                 dst[s][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(pr, (int)goff[s], 0, 0));
             }
@@ -552,15 +453,12 @@ __device__ __forceinline__ void warp_staged(float* box, float* xbuf, const RespK
 #pragma unroll
         for (int s = 0; s < NS; s++)
 #pragma unroll
-            for (int j = 0; j < U; j++) {
-                if constexpr (PF_WARP_SPLIT) box[pa * kCap + (t + s * kWB) * U + j] = src[s][j];
-                else box[2 * ((t + s * kWB) * U + j) + pa] = src[s][j];
-            }
+            for (int j = 0; j < U; j++) box[pa * kCap + (t + s * kWB) * U + j] = src[s][j];
     };
-    auto iter = [&](auto parity, auto slot, int q) {
-        constexpr int PA = decltype(parity)::value, SL = decltype(slot)::value;  // q%2, q%D
-        fetch(stg[SL], q + D);  // panorama q was put into parity PA last iteration: reuse stg[SL]
-        const float* L = PF_WARP_SPLIT ? box + PA * kCap : box + PA;
+    auto iter = [&](auto parity, int q) {
+        constexpr int PA = decltype(parity)::value;  // q % 2
+        fetch(stg[PA], q + 2);  // panorama q was put into parity PA last iteration: reuse stg[PA]
+        const float* L = box + PA * kCap;
         const int b = bbeg + q;
         const auto orr = rsrc(tiles + b * tstride, (uint32_t)(tstride * 4));
         f2 al{}, ka{}, be{}, si{};
@@ -578,139 +476,7 @@ __device__ __forceinline__ void warp_staged(float* box, float* xbuf, const RespK
 #pragma unroll
             for (int j = 0; j < 2; j++) {
                 const float* c = L + (RAG ? (W.la[k + j] & 0xFFFFu) : W.la[k + j]);
-                if constexpr (RAG) {  // the bottom pair sits on its own packed row
-                    const float* c2 = L + (W.la[k + j] >> 16);
-                    v[j] = bilinear(f2{c[0], c[1]}, f2{c2[0], c2[1]}, W.wx[k + j], W.wy[k + j]);
-                } else if constexpr (PF_WARP_SPLIT)
-                    v[j] = bilinear(f2{c[0], c[1]}, f2{c[P.bw], c[P.bw + 1]}, W.wx[k + j],
-                                    W.wy[k + j]);
-                else
-                    v[j] = bilinear(f2{c[0], c[2]}, f2{c[bw2], c[bw2 + 2]}, W.wx[k + j],
-                                    W.wy[k + j]);
-            }
-            if (RESP) {
-                const f2 u = f2{noise_top24(W.hp[k], key), noise_top24(W.hp[k + 1], key)};
-                const f2 nz = __builtin_elementwise_fma(u, f2{0x1p-23f, 0x1p-23f},
-                                                        f2{-1.0f, -1.0f});
-                f2 tt = al * v;
-                tt = tt + (ka * v) * v;
-                tt = tt + be;
-                v = pk_add_clamp01(tt, si * nz);
-            }
-            out[k] = v[0];
-            out[k + 1] = v[1];
-        }
-        if constexpr (PF_WARP_XPOSE) {  // wave-local transpose through LDS (in order per wave)
-            float* xt = xbuf + (t >> 6) * (kPx * 64);
-#pragma unroll
-            for (int k = 0; k < kPx; k++) xt[k * 64 + (t & 63)] = out[k];
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            const float4 r = *reinterpret_cast<const float4*>(xt + 4 * (t & 63));
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            out[0] = r.x; out[1] = r.y; out[2] = r.z; out[3] = r.w;
-        }
-        if (PF_WARP_DIAG == 1 && out[0] != -12345.0f) {
-        } else if (kPx >= 4 && W.full) {
-            const u4v o = {__float_as_uint(out[0]), __float_as_uint(out[1]),
-                           __float_as_uint(out[2 % kPx]), __float_as_uint(out[3 % kPx])};
-            __builtin_amdgcn_raw_buffer_store_b128(o, orr, (int)W.oo[0], 0, PF_WARP_STPOL);
-        } else {
-#pragma unroll
-            for (int k = 0; k < kPx; k++)
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(out[k]), orr, (int)W.oo[k],
-                                                      0, PF_WARP_STPOL);
-        }
-        put(1 - PA, stg[(SL + 1) % D]);  // panorama q+1 (a duplicate past the chunk: unread)
-        __syncthreads();
-    };
-#pragma unroll
-    for (int j = 0; j < D; j++) fetch(stg[j], j);
-    put(0, stg[0]);
-    __syncthreads();
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2 % D>;
-    if constexpr (D == 2) {
-        for (int q = 0; q < nb; q += 2) {
-            iter(I0{}, I0{}, q);
-            if (q + 1 < nb) iter(I1{}, I1{}, q + 1);
-        }
-    } else {  // D == 3: parity x slot repeats every 6 panoramas
-        static_assert(D == 3, "prefetch depth 2 or 3");
-        for (int q = 0; q < nb; q += 6) {
-            iter(I0{}, I0{}, q);
-            if (q + 1 < nb) iter(I1{}, I1{}, q + 1);
-            if (q + 2 < nb) iter(I0{}, I2{}, q + 2);
-            if (q + 3 < nb) iter(I1{}, I0{}, q + 3);
-            if (q + 4 < nb) iter(I0{}, I1{}, q + 4);
-            if (q + 5 < nb) iter(I1{}, I2{}, q + 5);
-        }
-    }
-}
-
-#ifndef PF_WARP_DMA
-// 1: ragged footprints of <= 2 units per thread are staged by LDS-DMA (global_load_lds_dwordx4:
-// each 16-B unit lands in LDS with no VGPR round trip and no ds_write), in three LDS buffers with
-// two panoramas in flight, counted vmcnt waits and raw barriers
-#define PF_WARP_DMA 0
-#endif
-#if PF_WARP_DMA
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-template <int NS, bool RESP>
-__device__ __forceinline__ void warp_dma(float* box, const RespK* rk, const WarpPatch& P, int t,
-                                         const WarpLanes& W, const float* __restrict__ pano,
-                                         long long pstride, float* __restrict__ tiles,
-                                         long long tstride, int bbeg, int nb,
-                                         const uint32_t* __restrict__ unit_tbl)
-{
-    constexpr int BUF = NS * kWB * 4;  // floats per buffer: unit e at [4e, 4e + 4)
-    static_assert(3 * BUF <= 2 * kCap, "three buffers fit the box");
-    static_assert(!PF_WARP_ROWPX && !PF_WARP_XPOSE, "kPx tile stores per panorama");
-    const int units = P.units;
-    uint32_t gofl[NS];  // float offset (in one panorama) of unit t + s*kWB
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        const int e = t + s * kWB;
-        gofl[s] = unit_tbl[P.uoff + (e < units ? e : units - 1)] >> 2;
-    }
-    const int wv = t >> 6;
-    auto dma = [&](int buf, int q) {
-        const float* pp = pano + (long long)(bbeg + (q < nb ? q : nb - 1)) * pstride;
-#pragma unroll
-        for (int s = 0; s < NS; s++)  // wave-uniform destination, lane l at +16 l bytes
-            __builtin_amdgcn_global_load_lds((gptr_t)(pp + gofl[s]),
-                                             (lptr_t)(box + buf * BUF + (s * kWB + wv * 64) * 4),
-                                             16, 0, 0);
-    };
-    dma(0, 0);
-    dma(1, 1);
-    for (int q = 0; q < nb; q++) {
-        // panorama q's units are in: every VMEM op issued after them is panorama q+1's NS loads
-        // and panorama q-1's kPx tile stores (they retire in issue order)
-        if (q == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NS) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NS + kPx) : "memory");
-        __builtin_amdgcn_s_barrier();  // every wave's units of q landed; q-1's reads are done
-        dma((q + 2) % 3, q + 2);       // into the buffer panorama q-1 was read from
-        const float* L = box + (q % 3) * BUF;
-        const int b = bbeg + q;
-        const auto orr = rsrc(tiles + b * tstride, (uint32_t)(tstride * 4));
-        f2 al{}, ka{}, be{}, si{};
-        uint32_t key = 0;
-        if (RESP) {
-            const RespK r = rk[q];
-            al = f2{r.alpha, r.alpha}; ka = f2{r.kappa, r.kappa};
-            be = f2{r.beta, r.beta}; si = f2{r.sigma, r.sigma};
-            key = r.key;
-        }
-        float out[kPx];
-#pragma unroll
-        for (int k = 0; k < kPx; k += 2) {
-            f2 v;
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const float* c = L + (W.la[k + j] & 0xFFFFu);
-                const float* c2 = L + (W.la[k + j] >> 16);
+                const float* c2 = RAG ? L + (W.la[k + j] >> 16) : c + P.bw;
                 v[j] = bilinear(f2{c[0], c[1]}, f2{c2[0], c2[1]}, W.wx[k + j], W.wy[k + j]);
             }
             if (RESP) {
@@ -728,46 +494,43 @@ __device__ __forceinline__ void warp_dma(float* box, const RespK* rk, const Warp
 #pragma unroll
         for (int k = 0; k < kPx; k++)
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(out[k]), orr, (int)W.oo[k], 0,
-                                                  PF_WARP_STPOL);
+                                                  kStorePolicy);
+        put(1 - PA, stg[1 - PA]);  // panorama q+1 (a duplicate past the chunk: unread)
+        __syncthreads();
+    };
+    fetch(stg[0], 0);
+    fetch(stg[1], 1);
+    put(0, stg[0]);
+    __syncthreads();
+    for (int q = 0; q < nb; q += 2) {
+        iter(std::integral_constant<int, 0>{}, q);
+        if (q + 1 < nb) iter(std::integral_constant<int, 1>{}, q + 1);
     }
-    // no LDS-DMA may land after the workgroup ends (the duplicate loads past the chunk)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
-#endif
 
-template <int NS, bool V4, bool RAG = false>
-__device__ __forceinline__ void warp_staged_sel(bool resp, float* box, float* xbuf,
-                                                const RespK* rk,
+template <int NS, bool RAG>
+__device__ __forceinline__ void warp_staged_sel(bool resp, float* box, const RespK* rk,
                                                 const WarpPatch& P, int t, const WarpLanes& W,
                                                 const float* pano, int pw, int ph,
                                                 long long pstride, float* tiles,
                                                 long long tstride, int bbeg, int nb,
-                                                const uint32_t* unit_tbl = nullptr)
+                                                const uint32_t* unit_tbl)
 {
-    if (resp) warp_staged<NS, true, V4, RAG>(box, xbuf, rk, P, t, W, pano, pw, ph, pstride, tiles,
-                                             tstride, bbeg, nb, unit_tbl);
-    else warp_staged<NS, false, V4, RAG>(box, xbuf, rk, P, t, W, pano, pw, ph, pstride, tiles,
-                                         tstride, bbeg, nb, unit_tbl);
+    if (resp) warp_staged<NS, true, RAG>(box, rk, P, t, W, pano, pw, ph, pstride, tiles, tstride,
+                                         bbeg, nb, unit_tbl);
+    else warp_staged<NS, false, RAG>(box, rk, P, t, W, pano, pw, ph, pstride, tiles, tstride,
+                                     bbeg, nb, unit_tbl);
 }
 
-#ifndef PF_WARP_WPE
-#define PF_WARP_WPE 1   // amdgpu_waves_per_eu minimum (occupancy target for the register budget)
-#endif
-__global__ void __launch_bounds__(kWB) __attribute__((amdgpu_waves_per_eu(PF_WARP_WPE)))
-k_warp_depth(const TileGeom* __restrict__ geom,
-                                                    int ntiles,
-                                                    const WarpPatch* __restrict__ patches,
-                                                    const uint32_t* __restrict__ unit_tbl,
-                                                    int npatch, const uint32_t* __restrict__ wloc,
-                                                    const float2* __restrict__ wfxy,
-                                                    const float* __restrict__ pano, int pw,
-                                                    int ph, long long pstride,
-                                                    const Resp* __restrict__ resp,
-                                                    float* __restrict__ tiles,
-                                                    long long tstride, int batch)
+__global__ void __launch_bounds__(kWB)
+k_warp_depth(const TileGeom* __restrict__ geom, int ntiles,
+             const WarpPatch* __restrict__ patches, const uint32_t* __restrict__ unit_tbl,
+             int npatch, const uint32_t* __restrict__ wloc, const float2* __restrict__ wfxy,
+             const float* __restrict__ pano, int pw, int ph, long long pstride,
+             const Resp* __restrict__ resp, float* __restrict__ tiles, long long tstride,
+             int batch)
 {
-    // one LDS object: the staging box, then the per-panorama response keys (a second __shared__
-    // object beside an LDS-DMA target makes hipcc wait vmcnt(0) before every box read)
+    // one LDS object: the two parities of the staging box, then the per-panorama response keys
     __shared__ float box[2 * kCap + kNB * (int)(sizeof(RespK) / sizeof(float))];
     // XCD-contiguous runs of patches; the host sorts the patches by panorama footprint, so the
     // blocks resident on one XCD stage overlapping boxes and re-read each other's lines from L2
@@ -823,276 +586,27 @@ k_warp_depth(const TileGeom* __restrict__ geom,
         return;
     }
 
-    W.full = PF_WARP_ROWPX && W.ok[0] && W.ok[kPx - 1] && g.c == 1;
-#if PF_WARP_XPOSE
-    static_assert(kPx == 4 && kPatch == 32 && !PF_WARP_ROWPX, "transpose: 8 rows x 32 per wave");
-    __shared__ float xbuf[kWB * kPx];
-    {
-        const int l = t & 63, rr = l >> 3;
-        const int Y = P.Y0 + 2 * (t >> 6) + (rr & 1) + 8 * (rr >> 1), X = P.X0 + 4 * (l & 7);
-        bool all = Y < g.h && g.c == 1;
-#pragma unroll
-        for (int j = 0; j < kPx; j++) {
-            const bool in = Y < g.h && X + j < g.w;
-            all = all && in;
-            W.oo[j] = in ? (uint32_t)(g.off + ((long long)Y * g.w + X + j) * g.c) * 4u : 0xFFFFFFF0u;
-        }
-        W.full = all && (W.oo[0] & 15u) == 0;
-    }
-#else
-    float* xbuf = nullptr;
-#endif
-#pragma unroll
-    for (int k = 0; k < kPx; k++) W.la[k] *= PF_WARP_SPLIT ? 1 : 2;  // parity-interleaved box
     RespK* const rk = reinterpret_cast<RespK*>(box + 2 * kCap);  // published by the first barrier
     if (t < nb) rk[t] = resp_key(resp, bbeg + t, ntiles, P.tile);
     const bool rs = resp != nullptr;
-    if (PF_WARP_V4 && PF_WARP_SPLIT && P.units > 0) {  // ragged footprint (warp_patches_host)
-        const int nq = (P.units + kWB - 1) / kWB;  // uniform: 16-B loads per thread
-#if PF_WARP_DMA
-        if (nq <= 2) {
-            if (nq <= 1) {
-                if (rs) warp_dma<1, true>(box, rk, P, t, W, pano, pstride, tiles, tstride, bbeg, nb, unit_tbl);
-                else warp_dma<1, false>(box, rk, P, t, W, pano, pstride, tiles, tstride, bbeg, nb, unit_tbl);
-            } else {
-                if (rs) warp_dma<2, true>(box, rk, P, t, W, pano, pstride, tiles, tstride, bbeg, nb, unit_tbl);
-                else warp_dma<2, false>(box, rk, P, t, W, pano, pstride, tiles, tstride, bbeg, nb, unit_tbl);
-            }
-        } else
-#endif
-        if (nq <= 1) warp_staged_sel<1, true, true>(rs, box, xbuf, rk, P, t, W, pano, pw, ph, pstride,
+    if (P.units > 0) {  // ragged footprint (warp_patches_host): 16-B staging loads
+        const int nq = (P.units + kWB - 1) / kWB;  // uniform: loads per thread
+        if (nq <= 1) warp_staged_sel<1, true>(rs, box, rk, P, t, W, pano, pw, ph, pstride, tiles,
+                                              tstride, bbeg, nb, unit_tbl);
+        else if (nq <= 2) warp_staged_sel<2, true>(rs, box, rk, P, t, W, pano, pw, ph, pstride,
+                                                   tiles, tstride, bbeg, nb, unit_tbl);
+        else warp_staged_sel<kSlots / 4, true>(rs, box, rk, P, t, W, pano, pw, ph, pstride,
+                                               tiles, tstride, bbeg, nb, unit_tbl);
+    } else {  // bounding box (k_patch_box, pw % 4 != 0): 4-B staging loads
+        const int ns = (P.bw * P.bh + kWB - 1) / kWB;  // uniform: loads per thread
+        if (ns <= 4) warp_staged_sel<4, false>(rs, box, rk, P, t, W, pano, pw, ph, pstride, tiles,
+                                               tstride, bbeg, nb, unit_tbl);
+        else if (ns <= 8) warp_staged_sel<8, false>(rs, box, rk, P, t, W, pano, pw, ph, pstride,
                                                     tiles, tstride, bbeg, nb, unit_tbl);
-        else if (nq <= 2) warp_staged_sel<2, true, true>(rs, box, xbuf, rk, P, t, W, pano, pw, ph,
-                                                         pstride, tiles, tstride, bbeg, nb, unit_tbl);
-        else warp_staged_sel<kSlots / 4, true, true>(rs, box, xbuf, rk, P, t, W, pano, pw, ph,
-                                                     pstride, tiles, tstride, bbeg, nb, unit_tbl);
-    } else if (PF_WARP_V4 && (pw & 3) == 0) {  // quad-aligned boxes (k_patch_box): 16-B staging loads
-        const int nq = (P.bw * P.bh / 4 + kWB - 1) / kWB;  // uniform: loads per thread
-        if (nq <= 1) warp_staged_sel<1, true>(rs, box, xbuf, rk, P, t, W, pano, pw, ph, pstride, tiles,
-                                              tstride, bbeg, nb);
-        else if (nq <= 2) warp_staged_sel<2, true>(rs, box, xbuf, rk, P, t, W, pano, pw, ph, pstride,
-                                                   tiles, tstride, bbeg, nb);
-        else warp_staged_sel<kSlots / 4, true>(rs, box, xbuf, rk, P, t, W, pano, pw, ph, pstride,
-                                               tiles, tstride, bbeg, nb);
-    } else {
-        const int ns = (P.bw * P.bh + kWB - 1) / kWB;  // uniform: staging loads per thread
-        // staging slots never exceed kSlots: slot s writes LDS unit t + s*kWB < kCap
-        constexpr int N1 = kSlots < 4 ? kSlots : 4, N2 = kSlots < 8 ? kSlots : 8;
-        if (ns <= N1) warp_staged_sel<N1, false>(rs, box, xbuf, rk, P, t, W, pano, pw, ph, pstride,
-                                                 tiles, tstride, bbeg, nb);
-        else if (ns <= N2) warp_staged_sel<N2, false>(rs, box, xbuf, rk, P, t, W, pano, pw, ph, pstride,
-                                                      tiles, tstride, bbeg, nb);
-        else warp_staged_sel<kSlots, false>(rs, box, xbuf, rk, P, t, W, pano, pw, ph, pstride, tiles,
-                                            tstride, bbeg, nb);
+        else warp_staged_sel<kSlots, false>(rs, box, rk, P, t, W, pano, pw, ph, pstride, tiles,
+                                            tstride, bbeg, nb, unit_tbl);
     }
 }
-
-#endif  // !PF_WARP_WAVEBOX
-
-#if PF_WARP_WAVEBOX
-__device__ __forceinline__ void wave_sync()
-{  // a wave's LDS operations complete in order; this only keeps the compiler from moving them
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// One wave, one 32x8 patch: the warp_staged loop with the box in the wave's own LDS region
-// (kCap floats per parity) and wave_sync() where the block form has __syncthreads().
-template <int NS, bool RESP, bool V4>
-__device__ __forceinline__ void warp_wave(float* box, const RespK* rk, const WarpPatch& P, int l,
-                                          const WarpLanes& W, const float* __restrict__ pano,
-                                          int pw, int ph, long long pstride,
-                                          float* __restrict__ tiles, long long tstride, int bbeg,
-                                          int nb)
-{
-    constexpr int U = V4 ? 4 : 1;
-    static_assert(NS * 64 * U <= kCap, "staging slots stay inside the wave's box");
-    const int bwu = P.bw / U, units = bwu * P.bh;
-    uint32_t goff[NS];
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        int e = l + s * 64;
-        e = e < units ? e : units - 1;
-        const int r = e / bwu, c = (e - r * bwu) * U;
-        int row = P.gy0 + r;
-        row = row < ph ? row : ph - 1;
-        int col = P.gx0 + c;
-        col = col < pw ? col : col - pw;
-        goff[s] = (uint32_t)(row * pw + col) * 4u;
-    }
-    float stg[2][NS][U];
-    const uint32_t pbytes = (uint32_t)(pstride * 4);
-    auto fetch = [&](float (*dst)[U], int q) {
-        const auto pr = rsrc(pano + (long long)(bbeg + (q < nb ? q : nb - 1)) * pstride, pbytes);
-#pragma unroll
-        for (int s = 0; s < NS; s++) {
-            if constexpr (V4) {
-                const u4v v = __builtin_amdgcn_raw_buffer_load_b128(pr, (int)goff[s], 0, 0);
-#pragma unroll
-                for (int j = 0; j < 4; j++) dst[s][j] = __uint_as_float(v[j]);
-            } else {
-                dst[s][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(pr, (int)goff[s], 0, 0));
-            }
-        }
-    };
-    auto put = [&](int pa, const float (*src)[U]) {
-#pragma unroll
-        for (int s = 0; s < NS; s++)
-#pragma unroll
-            for (int j = 0; j < U; j++) box[pa * kCap + (l + s * 64) * U + j] = src[s][j];
-    };
-    auto iter = [&](auto parity, int q) {
-        constexpr int PA = decltype(parity)::value;
-        fetch(stg[PA], q + 2);
-        const float* L = box + PA * kCap;
-        const int b = bbeg + q;
-        const auto orr = rsrc(tiles + b * tstride, (uint32_t)(tstride * 4));
-        f2 al{}, ka{}, be{}, si{};
-        uint32_t key = 0;
-        if (RESP) {
-            const RespK r = rk[q];
-            al = f2{r.alpha, r.alpha}; ka = f2{r.kappa, r.kappa};
-            be = f2{r.beta, r.beta}; si = f2{r.sigma, r.sigma};
-            key = r.key;
-        }
-        float out[kLPx];
-#pragma unroll
-        for (int k = 0; k < kLPx; k += 2) {
-            f2 v;
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const float* c = L + W.la[k + j];
-                v[j] = bilinear(f2{c[0], c[1]}, f2{c[P.bw], c[P.bw + 1]}, W.wx[k + j], W.wy[k + j]);
-            }
-            if (RESP) {
-                const f2 u = f2{noise_top24(W.hp[k], key), noise_top24(W.hp[k + 1], key)};
-                const f2 nz = __builtin_elementwise_fma(u, f2{0x1p-23f, 0x1p-23f},
-                                                        f2{-1.0f, -1.0f});
-                f2 tt = al * v;
-                tt = tt + (ka * v) * v;
-                tt = tt + be;
-                v = pk_add_clamp01(tt, si * nz);
-            }
-            out[k] = v[0];
-            out[k + 1] = v[1];
-        }
-#pragma unroll
-        for (int k = 0; k < kLPx; k++)
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(out[k]), orr, (int)W.oo[k], 0,
-                                                  PF_WARP_STPOL);
-        put(1 - PA, stg[1 - PA]);  // panorama q+1 (a duplicate past the chunk: unread)
-        wave_sync();
-    };
-    fetch(stg[0], 0);
-    fetch(stg[1], 1);
-    put(0, stg[0]);
-    wave_sync();
-    for (int q = 0; q < nb; q += 2) {
-        iter(std::integral_constant<int, 0>{}, q);
-        if (q + 1 < nb) iter(std::integral_constant<int, 1>{}, q + 1);
-    }
-}
-
-template <int NS, bool V4>
-__device__ __forceinline__ void warp_wave_sel(bool resp, float* box, const RespK* rk,
-                                              const WarpPatch& P, int l, const WarpLanes& W,
-                                              const float* pano, int pw, int ph, long long pstride,
-                                              float* tiles, long long tstride, int bbeg, int nb)
-{
-    if (resp) warp_wave<NS, true, V4>(box, rk, P, l, W, pano, pw, ph, pstride, tiles, tstride,
-                                      bbeg, nb);
-    else warp_wave<NS, false, V4>(box, rk, P, l, W, pano, pw, ph, pstride, tiles, tstride, bbeg,
-                                  nb);
-}
-
-__global__ void __launch_bounds__(kWB) k_warp_wave(const TileGeom* __restrict__ geom, int ntiles,
-                                                   const WarpPatch* __restrict__ patches,
-                                                   int npatch, const uint32_t* __restrict__ wloc,
-                                                   const float2* __restrict__ wfxy,
-                                                   const float* __restrict__ pano, int pw, int ph,
-                                                   long long pstride, const Resp* __restrict__ resp,
-                                                   float* __restrict__ tiles, long long tstride,
-                                                   int batch)
-{
-    __shared__ float boxes[4][2 * kCap];
-    __shared__ RespK rks[4][kNB];
-    const int npb = (npatch + 3) / 4;
-    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
-    const int pb = (int)(lb % (unsigned)npb), chunk = (int)(lb / (unsigned)npb);
-    const int w = (int)(threadIdx.x >> 6), l = (int)(threadIdx.x & 63);
-    const int pid = pb * 4 + w;
-    if (pid >= npatch) return;  // whole wave; nothing below synchronises across waves
-    const WarpPatch P = patches[pid];
-    const TileGeom& g = geom[P.tile];
-    const int bbeg = chunk * kNB;
-    const int nb = min(kNB, batch - bbeg);
-    WarpLanes W;
-#pragma unroll
-    for (int k = 0; k < kLPx; k++) {  // lane l: column l & 31, rows (l >> 5) + 2k of the patch
-        const int X = P.X0 + (l & 31), Y = P.Y0 + (l >> 5) + 2 * k;
-        const int i = Y * g.w + X;
-        W.ok[k] = X < g.w && Y < g.h;
-        W.la[k] = 0; W.wx[k] = f2{1.0f, 0.0f}; W.wy[k] = f2{1.0f, 0.0f};
-        W.hp[k] = mix32((uint32_t)i);
-        W.oo[k] = W.ok[k] ? (uint32_t)(g.off + (long long)i * g.c) * 4u : 0xFFFFFFF0u;
-        if (W.ok[k]) {
-            W.la[k] = wloc[g.pix_off + i];
-            const float2 f = wfxy[g.pix_off + i];
-            W.wx[k] = f2{1.0f - f.x, f.x};
-            W.wy[k] = f2{1.0f - f.y, f.y};
-        }
-    }
-    if (P.wide) {  // footprint too large for the wave's box: direct corner gathers
-        for (int q = 0; q < nb; q++) {
-            const int b = bbeg + q;
-            const float* pp = pano + b * pstride;
-            const RespK r = resp_key(resp, b, ntiles, P.tile);
-            float* out = tiles + b * tstride;
-#pragma unroll
-            for (int k = 0; k < kLPx; k++) {
-                if (!W.ok[k]) continue;
-                const uint32_t o00 = W.la[k] & 0x3FFFFFFFu, dx = W.la[k] >> 31;
-                const uint32_t o10 = o00 + (((W.la[k] >> 30) & 1u) ? (uint32_t)pw : 0u);
-                float v = bilinear(f2{pp[o00], pp[o00 + dx]}, f2{pp[o10], pp[o10 + dx]},
-                                   W.wx[k], W.wy[k]);
-                if (resp) {
-                    const float nz = __builtin_fmaf(noise_top24(W.hp[k], r.key), 0x1p-23f, -1.0f);
-                    float tt = r.alpha * v;
-                    tt = tt + (r.kappa * v) * v;
-                    tt = tt + r.beta;
-                    tt = tt + r.sigma * nz;
-                    v = tt < 0.0f ? 0.0f : (tt > 1.0f ? 1.0f : tt);
-                }
-                out[W.oo[k] >> 2] = v;
-            }
-        }
-        return;
-    }
-    RespK* rk = rks[w];
-    if (l < nb) rk[l] = resp_key(resp, bbeg + l, ntiles, P.tile);
-    wave_sync();
-    const bool rs = resp != nullptr;
-    float* box = boxes[w];
-    if (PF_WARP_V4 && (pw & 3) == 0) {
-        const int nq = (P.bw * P.bh / 4 + 63) / 64;  // wave-uniform: 16-B loads per lane
-        if (nq <= 1) warp_wave_sel<1, true>(rs, box, rk, P, l, W, pano, pw, ph, pstride, tiles,
-                                            tstride, bbeg, nb);
-        else if (nq <= 2) warp_wave_sel<2, true>(rs, box, rk, P, l, W, pano, pw, ph, pstride,
-                                                 tiles, tstride, bbeg, nb);
-        else warp_wave_sel<kCap / 256, true>(rs, box, rk, P, l, W, pano, pw, ph, pstride, tiles,
-                                             tstride, bbeg, nb);
-    } else {
-        const int ns = (P.bw * P.bh + 63) / 64;
-        if (ns <= 4) warp_wave_sel<4, false>(rs, box, rk, P, l, W, pano, pw, ph, pstride, tiles,
-                                             tstride, bbeg, nb);
-        else if (ns <= 8) warp_wave_sel<8, false>(rs, box, rk, P, l, W, pano, pw, ph, pstride,
-                                                  tiles, tstride, bbeg, nb);
-        else warp_wave_sel<kCap / 64, false>(rs, box, rk, P, l, W, pano, pw, ph, pstride, tiles,
-                                             tstride, bbeg, nb);
-    }
-}
-#endif
 
 // ---------------------------------------------------------------------------------------------
 void launch_warp_boxes(hipStream_t s, const TileGeom* geom, WarpPatch* patches, int npatch,
@@ -1113,41 +627,31 @@ void launch_warp_depth(hipStream_t s, const TileGeom* geom, int ntiles, const Wa
                        int pw, int ph, long long pstride, const Resp* resp, float* tiles,
                        long long tstride, int batch)
 {
-#if PF_WARP_WAVEBOX
-    const long long n = (long long)((npatch + 3) / 4) * ((batch + kNB - 1) / kNB);
-    hipLaunchKernelGGL(k_warp_wave, dim3((unsigned)n), dim3(kWB), 0, s, geom, ntiles, patches,
-                       npatch, wloc, (const float2*)wfxy, pano, pw, ph, pstride, resp, tiles,
-                       tstride, batch);
-#else
     const long long n = (long long)npatch * ((batch + kNB - 1) / kNB);
     hipLaunchKernelGGL(k_warp_depth, dim3((unsigned)n), dim3(kWB), 0, s, geom, ntiles, patches,
                        unit_tbl, npatch, wloc, (const float2*)wfxy, pano, pw, ph, pstride, resp,
                        tiles, tstride, batch);
-#endif
 }
-
 
 // =============================================================================================
 // E->P RGB warp (a18: SaveCubeMap, Main.cpp:242-326, the GL camera and GL_LINEAR + GL_REPEAT
 // sampling of SphereMesh.cpp:74-77), LDS-staged like k_warp_depth.
 //
 // Per layout and panorama size the host cuts every tile into 64x16-pixel patches and, from the
-// taps (rgb_taps_host), gives each patch the byte box of its corners' footprint: rows gy0.. and
-// bytes bx0.. of the u8 RGB panorama, the origin rounded down to 16 B and the width up to 16 B,
-// so the box is staged with whole 16-B loads (both wrap: GL_REPEAT in u and v).  One block =
-// one patch x kNBR panoramas.  Per panorama each thread loads one 16-B unit of the box,
-// converts its bytes to floats and writes them to LDS (double-buffered: the loads for panorama
-// q+2 are in flight while q is blended); a thread then blends its 4 consecutive pixels of one
+// taps (rgb_taps_host), gives each patch the ragged footprint of its corners: per row of the u8
+// RGB panorama the bytes its corners read, rounded out to 16 B, so the footprint is staged with
+// whole 16-B loads (both wrap: GL_REPEAT in u and v).  One block = one patch x kNBR panoramas.
+// Per panorama each thread loads one or two 16-B units of the footprint and writes them to LDS
+// as they are (double-buffered: the loads for panorama q+2 are in flight while q is blended);
+// a thread then blends its 4 consecutive pixels of one
 // tile row (per channel top = t00*(1-ax) + t01*ax, bottom likewise, v = top*(1-ay) + bot*ay:
 // the oracle's fp32 operations in its order), rounds them to u8 and writes the 12 bytes with
 // one 12-B store, so a wave writes four 192-B runs of tile rows.  Patches whose box exceeds
 // the LDS slot (near the poles) blend from direct byte gathers of the taps.
 // =============================================================================================
-#ifndef PF_RGB_NB
-// round 6 A/B (profiles/r06/ab/rgb_panoramas_per_block.txt): 8 slower, 32 the same
-#define PF_RGB_NB 16
-#endif
-static constexpr int kNBR = PF_RGB_NB;  // panoramas per block
+// panoramas per block; round 6 A/B (profiles/r06/ab/rgb_panoramas_per_block.txt): 8 slower, 32
+// the same
+static constexpr int kNBR = 16;
 
 static inline int wrap_signed(int d, int n)
 {
@@ -1434,16 +938,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
             goff[u] = unit_tbl[(long long)pid * kRgbUnits + (e < P.units ? e : 0)];
         }
         u4v stg[2][NU];
-        bool live[NU];  // PF_RGB_MASKU: units past the footprint load nothing
-#pragma unroll
-        for (int u = 0; u < NU; u++) live[u] = t + 256 * u < P.units;
         auto fetch = [&](int sl, int q) {
             const auto pr = rsrc(pano + (long long)(bbeg + (q < nb ? q : nb - 1)) * pstride,
                                  pbytes);
 #pragma unroll
             for (int u = 0; u < NU; u++)
-                if (!PF_RGB_MASKU || live[u])
-                    stg[sl][u] = __builtin_amdgcn_raw_buffer_load_b128(pr, (int)goff[u], 0, 0);
+                stg[sl][u] = __builtin_amdgcn_raw_buffer_load_b128(pr, (int)goff[u], 0, 0);
         };
         auto put = [&](int pa, const u4v* v) {
 #pragma unroll

@@ -95,10 +95,9 @@ int pf_warp_depth(pf_ctx* c, const float* pano, int pw, int ph, int batch,
         const size_t cap = stage_capacity(c, npix);
         std::vector<uint32_t> wxy(cap), loc;
         std::vector<float> wf(2 * cap);
-        // ragged footprints (host, warp_patches_host) unless PF_WARP_RAGGED=0 or pw % 4 != 0;
-        // else the bounding boxes of k_patch_box / k_warp_local
-        const char* rg = getenv("PF_WARP_RAGGED");
-        const bool ragged = (pw % 4) == 0 && !(rg && atoi(rg) == 0);
+        // ragged footprints (host, warp_patches_host: 16-B units) when pw % 4 == 0; else the
+        // bounding boxes of k_patch_box / k_warp_local
+        const bool ragged = (pw % 4) == 0;
         std::vector<WarpPatch> patches;
         std::vector<uint32_t> units;
         if (ragged) loc.resize(cap);
