@@ -200,6 +200,40 @@ int pf_warp_rgb(pf_ctx* ctx, const uint8_t* pano, int pw, int ph, int batch, uin
 int pf_solve_smoothing(pf_ctx* ctx, const float* tiles, const float* coeffs, int batch,
                        int out_w, int out_h, float zr0, float zr1, uint16_t* out);
 
+/* The direct tile stitch (Depth.cpp:817-865, `if (false)` in the reference): the "no blending"
+ * baseline.  Every pixel of every row takes the value of the FIRST tile (ascending order) whose
+ * range box contains it -- x0 = round(r0 / (2 MYPI) * (W-1)), x1, y0, y1 likewise in double from
+ * the ranges as pf_set_tiles stored them; inside when min(x0,x1) <= x <= max(x0,x1) and
+ * y0 <= y <= y1, both ends inclusive, no zenith band -- read at SphericalTo2D of the fusion
+ * grid's (az, zen) through Value's truncated index (an index that leaves the tile is clamped;
+ * the reference reads out of bounds there).  A pixel under no tile is 0.  Quantisation as the
+ * fusion's: clamp to [0, 1], (u16)(v * 65535.0f), NaN -> 0.
+ * tiles: [batch][tile_elems] float (channel 0 read); coeffs: NULL, or [batch][ntiles][4] applied
+ * as Depth2DepthTransform on the fly; out: [batch][out_h][out_w] u16.  Bit-exact. */
+int pf_stitch(pf_ctx* ctx, const float* tiles, const float* coeffs, int batch, int out_w,
+              int out_h, uint16_t* out);
+
+/* The Laplacian self-check of SolveDepthAll (Depth.cpp:1738-1758, `if (false)` in the
+ * reference) on given planes: for y = h0+1 .. h1-1, x = 1 .. w-2 in row-major order, from
+ * err = 0.0f,  Lcur = val - (((left + right) + up) + down) / 4.0f,  d = Lcur - L  (fp32),
+ * err = (float)((double)err + (double)d * (double)d)  -- the reference's float chain, bit for
+ * bit.  L is the pixel's normalised target, 0 where lnorm carries the un-windowed marker.
+ *   buf   [batch][h][w] float   a level's plane after its sweeps
+ *   lnorm [batch][h][w] float   the targets as pf_fuse_targets writes them
+ *   err   [batch] float, device
+ * PF_EINVAL unless 0 <= h0, h0 + 2 <= h1 <= h - 1 and w >= 3.  Needs no tile layout. */
+int pf_laplacian_residual(pf_ctx* ctx, const float* buf, const float* lnorm, int w, int h, int h0,
+                          int h1, int batch, float* err);
+
+/* The fusion of one panorama (pf_fuse with batch 1) with the self-check after every level: per
+ * level pf_fuse_targets, pf_fuse_level and pf_laplacian_residual on that level's plane and
+ * targets.  err: [nlevels] float, device; err[nlevels - 1] is the number the reference prints as
+ * "[SolveDepthAll] check Laplacian err:", the coarser levels' are the same formula on their own
+ * targets (an extension).  out (optional): [out_h][out_w] u16, equal to pf_fuse's bit for bit. */
+int pf_fuse_check(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, const float* tiles,
+                  const float* coeffs, int out_w, int out_h, float zr0, float zr1, float* err,
+                  uint16_t* out);
+
 /* ---- multi-GPU fusion of one panorama (tiles sharded over ranks) ----
  * pf_fuse_partial scatters the Laplacian targets of tiles [t0, t1) for level `level` into
  * lsum/cnt ([out levels h][w] fp32 and fp32 counts); the caller sums them over ranks

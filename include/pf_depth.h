@@ -36,7 +36,14 @@
  * and glibc calls (csrc/pf_geom.hpp), bit-identical to it; the per-pixel path runs on the GPU.
  *
  * Extensions (not in the reference): MergeDisparityMaps, MergeDepthMaps for disparity tiles;
- * TransformResult, the cubic of SolveDepthToDepth2 applied to the u16 result.
+ * TransformResult, the cubic of SolveDepthToDepth2 applied to the u16 result; StitchDepthMaps and
+ * CheckLaplacian, the two `if (false)` diagnostics of MergeDepthMaps / SolveDepthAll as calls.
+ * MergeDepthMaps / MergeDisparityMaps read three environment switches (panofuse_main sets them
+ * from --fusion, --save-stitch, --check-laplacian): PF_FUSION=laplacian|smoothing|stitch chooses
+ * what fills the result (Depth.cpp:904-922, :851; laplacian, the default, is the reference's
+ * active path; smoothing and stitch run on the registered tiles), PF_SAVE_STITCH=1 also writes
+ * <out>.pmap.png (:859), PF_CHECK_LAPLACIAN=1 prints "[SolveDepthAll] check Laplacian err:<err>"
+ * (:1757) after the fusion and is refused with any other PF_FUSION.
  *
  * Not provided: a SolveDisparityToDepth over several active maps (a joint nonlinear solve), the
  * triangulation/subdivision members (vertices, faces, subd_*: never used on the path).
@@ -296,6 +303,18 @@ bool SolveDepthAll(EquirectangularMap& emap, std::vector<PerspectiveMap>& pmaps,
 // grid, 500 Gauss-Seidel smoothing iterations near the tile-box edges), on the GPU, bit-exact.
 bool SolveDepthBySmoothing(std::vector<PerspectiveMap>& pmaps, unsigned short* data,
                            int& out_width, int& out_height, Vec2f& zenith_range);
+/* EXTENSION (in the reference an `if (false)` block of MergeDepthMaps, Depth.cpp:817-865): the
+ * direct stitch of the tiles as they are into data (width * height u16) -- every pixel takes the
+ * first map whose range box contains it, no fusion -- on the GPU (pf_stitch), bit-exact. */
+bool StitchDepthMaps(std::vector<PerspectiveMap>& pmaps, unsigned short* data, int& width,
+                     int& height);
+/* EXTENSION (in the reference an `if (false)` block of SolveDepthAll, Depth.cpp:1738-1758): runs
+ * the fusion of the maps as they are and returns, per level, the squared distance between the
+ * solved plane's 5-point Laplacian and the level's targets, summed in the reference's order
+ * (pf_fuse_check).  err_per_level.back() is the number the reference prints as
+ * "[SolveDepthAll] check Laplacian err:"; the coarser levels' are the same formula. */
+bool CheckLaplacian(EquirectangularMap& emap, std::vector<PerspectiveMap>& pmaps, int width,
+                    int height, Vec2f& zenith_range, std::vector<float>& err_per_level);
 
 bool ErrorData(EquirectangularMap& emap_gt, unsigned short* data, int data_width,
                int data_height, float& mse, float& mae, float& mre, float& mse_log,

@@ -1,6 +1,6 @@
 // pf_ctx.hpp -- private to the host units of libpanofuse (pf_ctx.hip, pf_layout.hip, pf_plan.hip,
 // pf_fuse.hip, pf_shard.hip, pf_warp_api.hip, pf_smooth_api.hip, pf_eval.hip, pf_disp_api.hip,
-// pf_global_api.hip): the context struct
+// pf_global_api.hip, pf_stitch_api.hip): the context struct
 // behind the C-ABI's opaque pf_ctx, the error / allocation / upload helpers, the argument-check
 // prologues the entry points share, and the few functions that cross those units.  No kernel unit
 // includes it.
@@ -111,6 +111,10 @@ struct pf_ctx {
     // row-band smoothing (k_smooth_band): ticket, timeouts, per-block step flags
     pf::DevBuf sm_sync;
     uint32_t sm_tk = 0, sm_fb = 1;
+    // the direct stitch (pf_stitch.hip): boxes, grid tables and the per-pixel (first covering
+    // tile, Value index) map of one output size (st_key; pf_set_tiles drops it)
+    pf::DevBuf st_box, st_cols, st_rows, st_src;
+    int st_key[2] = {0, 0};
     // level-0 seed index tables of the streaming Jacobi (seed_tables), keyed by level and emap
     pf::DevBuf seed_ecol, seed_erow;
     // resident level kernel (pf_jres.hip): hand-off rows, and the sync words ([0] ticket

@@ -750,6 +750,56 @@ bool SolveDepthBySmoothing(std::vector<PerspectiveMap>& pmaps, unsigned short* d
     return hip_ok(hipMemcpy(data, dout.p, no * 2, hipMemcpyDeviceToHost), "download");
 }
 
+bool StitchDepthMaps(std::vector<PerspectiveMap>& pmaps, unsigned short* data, int& width,
+                     int& height)
+{  // EXTENSION: Depth.cpp:817-865 on the GPU (pf_stitch), the tiles as they are
+    pf_ctx* c = facade_ctx();
+    if (!c || !data) return false;
+    std::vector<PerspectiveMap*> pm;
+    for (auto& p : pmaps) pm.push_back(&p);
+    std::vector<float> packed;
+    if (!set_layout(c, pm, packed)) return false;
+    const size_t no = (size_t)width * height;
+    DevMem dt(packed.size() * 4), dout(no * 2);
+    if (!upload(dt, packed.data(), packed.size()) || !dout.ok) return false;
+    if (!pf_ok(c, pf_stitch(c, dt.as<float>(), nullptr, 1, width, height, dout.as<uint16_t>()),
+               "pf_stitch") ||
+        !pf_ok(c, pf_synchronize(c), "pf_synchronize"))
+        return false;
+    return hip_ok(hipMemcpy(data, dout.p, no * 2, hipMemcpyDeviceToHost), "download");
+}
+
+bool CheckLaplacian(EquirectangularMap& emap, std::vector<PerspectiveMap>& pmaps, int width,
+                    int height, Vec2f& zr, std::vector<float>& err_per_level)
+{  // EXTENSION: Depth.cpp:1738-1758 on the GPU, after every level (pf_fuse_check)
+    pf_ctx* c = facade_ctx();
+    if (!c || !emap.data) return false;
+    std::vector<PerspectiveMap*> pm;
+    for (auto& p : pmaps) pm.push_back(&p);
+    std::vector<float> packed;
+    if (!set_layout(c, pm, packed)) return false;
+    int lv[6] = {};
+    if (!pf_ok(c, pf_level_info(width, height, zr[0], zr[1], 0, &lv[0], &lv[1], &lv[2], &lv[3],
+                                &lv[4], &lv[5]),
+               "pf_level_info") ||
+        lv[5] < 1)
+        return false;
+    const size_t ne = (size_t)emap.width * emap.height * emap.channels;
+    DevMem de(ne * 4), dt(packed.size() * 4), derr(sizeof(float) * lv[5]);
+    if (!upload(de, emap.data, ne) || !upload(dt, packed.data(), packed.size()) || !derr.ok)
+        return false;
+    if (!pf_ok(c, pf_fuse_check(c, de.as<float>(), emap.width, emap.height, emap.channels,
+                                dt.as<float>(), nullptr, width, height, zr[0], zr[1],
+                                derr.as<float>(), nullptr),
+               "pf_fuse_check") ||
+        !pf_ok(c, pf_synchronize(c), "pf_synchronize"))  // PF_ETIMEOUT: invalid planes
+        return false;
+    err_per_level.assign(lv[5], 0.0f);
+    return hip_ok(hipMemcpy(err_per_level.data(), derr.p, sizeof(float) * lv[5],
+                            hipMemcpyDeviceToHost),
+                  "download");
+}
+
 bool ErrorData(EquirectangularMap& gt, unsigned short* data, int w, int h, float& mse,
                float& mae, float& mre, float& mselog, float& d1, float& d2, float& d3,
                int align_way, bool cap_depth, Vec2f* ls, float* shift)
@@ -919,6 +969,29 @@ static bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns,
                        int* time_Reg, int* time_Laplacian, bool disparity_tiles)
 {
     const auto t_begin = std::chrono::steady_clock::now();
+    // PF_FUSION (panofuse_main --fusion): what fills the result (Depth.cpp:904-922, :851), the
+    // choice the reference makes by editing `if (true/false)`; PF_SAVE_STITCH / PF_CHECK_LAPLACIAN
+    // (--save-stitch / --check-laplacian): its two `if (false)` diagnostics (:817-865, :1738-1758)
+    enum { FUSE_LAPLACIAN, FUSE_SMOOTHING, FUSE_STITCH } fusion = FUSE_LAPLACIAN;
+    if (const char* fu = std::getenv("PF_FUSION")) {
+        if (std::strcmp(fu, "smoothing") == 0) fusion = FUSE_SMOOTHING;
+        else if (std::strcmp(fu, "stitch") == 0) fusion = FUSE_STITCH;
+        else if (*fu && std::strcmp(fu, "laplacian") != 0) {
+            std::cout << "[MergeDepthMaps] bad PF_FUSION " << fu
+                      << " (want laplacian, smoothing or stitch)" << std::endl;
+            return false;
+        }
+    }
+    const auto env_on = [](const char* name) {
+        const char* v = std::getenv(name);
+        return v && std::strcmp(v, "1") == 0;
+    };
+    const bool save_stitch = env_on("PF_SAVE_STITCH"), check_lap = env_on("PF_CHECK_LAPLACIAN");
+    if (check_lap && fusion != FUSE_LAPLACIAN) {
+        std::cout << "[MergeDepthMaps] PF_CHECK_LAPLACIAN needs PF_FUSION=laplacian: only the "
+                     "fusion has Laplacian targets" << std::endl;
+        return false;
+    }
     EquirectangularMap emap;
     std::vector<PerspectiveMap> pmaps;
     // the ground truth decodes on a host thread while the tiles load and the GPU fuses
@@ -985,15 +1058,57 @@ static bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns,
         return false;
     if (!pf_ok(c, pf_synchronize(c), "pf_synchronize")) return false;
     if (time_Reg) *time_Reg = elapsed_ms(t);
-    // fusion (Depth.cpp:904-913)
+    // fusion (Depth.cpp:904-913), or with PF_FUSION the smoothing (:919-922) / the stitch (:851)
+    // on the registered tiles
+    const float* const cf = disparity_tiles ? nullptr : dc.as<float>();
     t = std::chrono::steady_clock::now();
-    if (!pf_ok(c, pf_fuse(c, de.as<float>(), emap.width, emap.height, emap.channels,
-                          dt.as<float>(), disparity_tiles ? nullptr : dc.as<float>(), 1,
-                          out_width, out_height, zr[0], zr[1], dout.as<uint16_t>()),
-               "pf_fuse") ||
+    const int frc =
+        fusion == FUSE_SMOOTHING
+            ? pf_solve_smoothing(c, dt.as<float>(), cf, 1, out_width, out_height, zr[0], zr[1],
+                                 dout.as<uint16_t>())
+        : fusion == FUSE_STITCH
+            ? pf_stitch(c, dt.as<float>(), cf, 1, out_width, out_height, dout.as<uint16_t>())
+            : pf_fuse(c, de.as<float>(), emap.width, emap.height, emap.channels, dt.as<float>(),
+                      cf, 1, out_width, out_height, zr[0], zr[1], dout.as<uint16_t>());
+    if (!pf_ok(c, frc,
+               fusion == FUSE_SMOOTHING ? "pf_solve_smoothing"
+               : fusion == FUSE_STITCH  ? "pf_stitch"
+                                        : "pf_fuse") ||
         !pf_ok(c, pf_synchronize(c), "pf_synchronize"))
         return false;
     if (time_Laplacian) *time_Laplacian = elapsed_ms(t);
+    if (check_lap) {  // Depth.cpp:1738-1758: the last level's number, in the reference's words
+        int lv[6] = {};
+        DevMem derr(sizeof(float) * 4);
+        float err[4] = {};
+        if (!derr.ok ||
+            !pf_ok(c, pf_level_info(out_width, out_height, zr[0], zr[1], 0, &lv[0], &lv[1], &lv[2],
+                                    &lv[3], &lv[4], &lv[5]),
+                   "pf_level_info") ||
+            lv[5] < 1 || lv[5] > 4 ||
+            !pf_ok(c, pf_fuse_check(c, de.as<float>(), emap.width, emap.height, emap.channels,
+                                    dt.as<float>(), cf, out_width, out_height, zr[0], zr[1],
+                                    derr.as<float>(), nullptr),
+                   "pf_fuse_check") ||
+            !pf_ok(c, pf_synchronize(c), "pf_synchronize") ||
+            !hip_ok(hipMemcpy(err, derr.p, sizeof(float) * lv[5], hipMemcpyDeviceToHost),
+                    "download"))
+            return false;
+        std::cout << std::endl << "[SolveDepthAll] check Laplacian err:" << err[lv[5] - 1]
+                  << std::endl;
+    }
+    if (save_stitch) {  // Depth.cpp:817-865: <out>.pmap.png
+        DevMem ds(no * 2);
+        std::vector<unsigned short> st(no);
+        if (!ds.ok ||
+            !pf_ok(c, pf_stitch(c, dt.as<float>(), cf, 1, out_width, out_height,
+                                ds.as<uint16_t>()),
+                   "pf_stitch") ||
+            !pf_ok(c, pf_synchronize(c), "pf_synchronize") ||
+            !hip_ok(hipMemcpy(st.data(), ds.p, no * 2, hipMemcpyDeviceToHost), "download") ||
+            !Save16BitPNG(st.data(), out_width, out_height, (out_fn + ".pmap.png").c_str()))
+            return false;
+    }
     // PF_GLOBAL_ALIGN=1 (panofuse_main --global-align): the fused result is pulled back onto the
     // baseline by SolveDepthToDepth2's cubic before it is written and scored
     const char* ga = std::getenv("PF_GLOBAL_ALIGN");

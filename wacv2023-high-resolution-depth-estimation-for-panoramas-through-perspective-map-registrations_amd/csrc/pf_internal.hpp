@@ -445,6 +445,17 @@ void launch_smooth(hipStream_t s, const TileGeom* geom, int ntiles, const int2* 
                    const float* coeffs, int w, int h, int h0, int h1, int iters, float* buf,
                    int batch);
 
+// The direct stitch and the Laplacian self-check (pf_stitch.hip).  The map holds per pixel the
+// first covering tile (box ends inclusive) and its Value() index, or tile -1.
+void launch_stitch_map(hipStream_t s, const TileGeom* geom, const SmoothBox* box, int ntiles,
+                       const GridCol* cols, const GridRow* rows, int w, int h, int2* src);
+void launch_stitch(hipStream_t s, const TileGeom* geom, int ntiles, const int2* src,
+                   const float* tiles, long long tstride, const float* coeffs, int w, int h,
+                   uint16_t* out, int batch);
+// err[b] = the reference-order float chain over rows h0+1..h1-1, columns 1..w-2 of plane b
+void launch_lap_residual(hipStream_t s, const float* buf, const float* lnorm, int w, int h,
+                         int h0, int h1, int batch, float* err);
+
 // (float)u / 65535.0f, correctly rounded, without the division sequence: one multiply by the
 // reciprocal and one fma refinement.  Exhaustively equal to the division for every u in
 // [0, 65535] (checked on the host with glibc fmaf: tests/test_oracle_metrics.py).

@@ -221,6 +221,7 @@ int pf_set_tiles(pf_ctx* c, const pf_window* fovs, const pf_window* ranges, int 
     c->npix_max = npmax;
     c->lc.out_w = 0;  // boxes and registration grids depend on the ranges: rebuild lazily
     c->reg_valid = false;
+    c->st_key[0] = c->st_key[1] = 0;
     c->wmap_pw = c->wmap_ph = 0;
     c->rgb_pw = c->rgb_ph = 0;
     c->cams_h = cams;

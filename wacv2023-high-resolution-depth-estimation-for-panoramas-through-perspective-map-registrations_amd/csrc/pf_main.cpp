@@ -3,6 +3,7 @@
 //                 [--ext auto|jpg|png] [--width W] [--device D] [--shard R/N]
 //                 [--metrics-order tree|sequential] [--edge-metrics]
 //                 [--tile-model depth|disparity] [--global-align] [--layout NAME|FILE]
+//                 [--fusion laplacian|smoothing|stitch] [--save-stitch] [--check-laplacian]
 //   panofuse_main export <rgb_dir> <tile_dir> [--device D] [--layout NAME|FILE]
 //   panofuse_main layout NAME|FILE [--width W] [--tile-size WxH] [--device D]
 //   panofuse_main lap <gt_file> <given_file> [--device D]
@@ -47,6 +48,14 @@
 // written and scored; prints the "[SolveDepthToDepth2] ..." line per panorama.
 // --edge-metrics (opt-in, takes no value): also write <raw>.edges.txt per panorama, the
 // ErrorLaplacian values of the result and of the baseline against the gt.
+// --fusion laplacian|smoothing|stitch: what fills the result (Depth.cpp:904-922, :851).  laplacian
+// (the default) is SolveDepthAll; smoothing is SolveDepthBySmoothing and stitch the direct tile
+// stitch (Depth.cpp:817-865), both on the registered tiles.  Everything after it (the result file,
+// the metrics, the masks, --global-align, --edge-metrics) runs on that result.
+// --save-stitch (opt-in, takes no value): also write <raw>.png.pmap.png, the direct stitch of the
+// registered tiles (the reference's debug file, Depth.cpp:859).
+// --check-laplacian (opt-in, takes no value, only with --fusion laplacian): print SolveDepthAll's
+// self-check "[SolveDepthAll] check Laplacian err:<err>" (Depth.cpp:1738-1758) per panorama.
 #include "../../include/panofuse.h"
 #include "../../include/pf_depth.h"
 
@@ -151,7 +160,9 @@ int main(int argc, char* argv[])
                   << " 0 <rgb_dir> <gt_dir> <baseline_dir> <result_dir> [--tiles DIR]"
                      " [--ext auto|jpg|png] [--width W] [--device D] [--shard R/N]"
                      " [--metrics-order tree|sequential] [--edge-metrics]"
-                     " [--tile-model depth|disparity] [--global-align] [--layout NAME|FILE]\n"
+                     " [--tile-model depth|disparity] [--global-align] [--layout NAME|FILE]"
+                     " [--fusion laplacian|smoothing|stitch] [--save-stitch]"
+                     " [--check-laplacian]\n"
                      "         (MiDaS disparity tiles, the reference's folder convention:"
                      " --layout midas --tile-model disparity --tiles output --ext png)\n"
                      "         (--layout: leres (default), midas, fold4, fold3, or a file of"
@@ -321,9 +332,27 @@ int main(int argc, char* argv[])
             --i;
             continue;
         }
+        if (k == "--save-stitch") {  // a flag without a value
+            setenv("PF_SAVE_STITCH", "1", 1);  // read by MergeDepthMaps / MergeDisparityMaps
+            --i;
+            continue;
+        }
+        if (k == "--check-laplacian") {  // a flag without a value
+            setenv("PF_CHECK_LAPLACIAN", "1", 1);  // read by MergeDepthMaps / MergeDisparityMaps
+            --i;
+            continue;
+        }
         if (i + 1 >= argc) break;
         const std::string v(argv[i + 1]);
         if (k == "--tiles") tiles = v;
+        else if (k == "--fusion") {
+            if (v != "laplacian" && v != "smoothing" && v != "stitch") {
+                std::cout << "bad --fusion " << v << " (want laplacian, smoothing or stitch)"
+                          << std::endl;
+                return 2;
+            }
+            setenv("PF_FUSION", v.c_str(), 1);  // read by MergeDepthMaps / MergeDisparityMaps
+        }
         else if (k == "--ext") ext = v;
         else if (k == "--width") width = std::atoi(v.c_str());
         else if (k == "--device") device = std::atoi(v.c_str());
@@ -353,6 +382,15 @@ int main(int argc, char* argv[])
         }
         else {
             std::cout << "unknown option " << k << std::endl;
+            return 2;
+        }
+    }
+    {  // the self-check compares the Jacobi result with its targets: only the fusion has them
+        const char* ck = std::getenv("PF_CHECK_LAPLACIAN");
+        const char* fu = std::getenv("PF_FUSION");
+        if (ck && std::string(ck) == "1" && fu && *fu && std::string(fu) != "laplacian") {
+            std::cout << "--check-laplacian needs --fusion laplacian (got " << fu << ")"
+                      << std::endl;
             return 2;
         }
     }

@@ -36,6 +36,7 @@ EXPORTS = [
     "pf_error_compare", "pf_disp_depth_convert", "pf_register_disparity",
     "pf_disparity_transform", "pf_merge_disparity", "pf_register_global",
     "pf_result_transform", "pf_median_scale", "pf_copy_invalid", "pf_layout_audit",
+    "pf_stitch", "pf_laplacian_residual", "pf_fuse_check",
 ]
 NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
           "pf_debug_smooth_fault", "pf_fuse_partial_rows", "pf_fuse_coverage_rows",
@@ -100,6 +101,9 @@ def load():
     L.pf_warp_depth.argtypes = [vp, vp, ip, ip, ip, vp, vp]
     L.pf_warp_rgb.argtypes = [vp, vp, ip, ip, ip, vp]
     L.pf_solve_smoothing.argtypes = [vp, vp, vp, ip, ip, ip, fp, fp, vp]
+    L.pf_stitch.argtypes = [vp, vp, vp, ip, ip, ip, vp]
+    L.pf_laplacian_residual.argtypes = [vp, vp, vp, ip, ip, ip, ip, ip, vp]
+    L.pf_fuse_check.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, ip, fp, fp, vp, vp]
     L.pf_set_metrics_order.argtypes = [vp, ip]
     L.pf_level_info.argtypes = [ip, ip, fp, fp, ip] + [C.POINTER(C.c_int)] * 6
     L.pf_fuse_partial.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, ip, vp, vp]
@@ -361,6 +365,49 @@ class Fuser:
         B, oh, ow = out.shape
         self._check(self.L.pf_solve_smoothing(self.h, _ptr(tiles), _ptr(coeffs), B, ow, oh,
                                               float(zr[0]), float(zr[1]), _ptr(out)))
+
+    def stitch(self, tiles, out, coeffs=None):
+        """The direct tile stitch (pf_stitch, Depth.cpp:817-865) into out [B, out_h, out_w]
+        (int16 view of u16): every pixel takes the first tile whose range box contains it, no
+        fusion; coeffs: None or [B, ntiles, 4], applied as Depth2DepthTransform on the fly."""
+        B, oh, ow = out.shape
+        self._check(self.L.pf_stitch(self.h, _ptr(tiles), _ptr(coeffs), B, ow, oh, _ptr(out)))
+
+    def laplacian_residual(self, buf, lnorm, h0, h1, err=None):
+        """SolveDepthAll's Laplacian self-check (pf_laplacian_residual, Depth.cpp:1738-1758) of
+        the level planes buf against their targets lnorm (float32 [B, h, w] device tensors) over
+        rows h0+1 .. h1-1: the reference-order float chain per plane into err (float32 [B]
+        device tensor, made when None) -- returned.  Needs no tile layout.  No sync."""
+        import torch
+        B, h, w = buf.shape
+        if tuple(lnorm.shape) != (B, h, w):
+            raise ValueError("buf and lnorm differ in shape")
+        if err is None:
+            err = torch.zeros(B, dtype=torch.float32, device=buf.device)
+        self._check(self.L.pf_laplacian_residual(self.h, _ptr(buf), _ptr(lnorm), w, h, int(h0),
+                                                 int(h1), B, _ptr(err)))
+        return err
+
+    def fuse_check(self, emap, tiles, zr, out_w, out_h=None, coeffs=None, out=None, err=None):
+        """pf_fuse_check: the fusion of ONE panorama (emap [1, eh, ew(, ec)], tiles [1, tile_elems],
+        coeffs None or [1, ntiles, 4]) with the Laplacian self-check after every level.  Returns
+        err, a float32 [nlevels] device tensor (made when None); its last entry is the number the
+        reference prints as "check Laplacian err".  out: optional [1, out_h, out_w] or
+        [out_h, out_w] (int16 view of u16), equal to fuse()'s.  No sync."""
+        import torch
+        ew, eh, ec = _emap_dims(emap)
+        out_h = _out_h(out_w, out_h)
+        if emap.shape[0] != 1:
+            raise ValueError("fuse_check takes one panorama")
+        if err is None:
+            n = level_info(out_w, out_h, zr, 0)[5]
+            err = torch.zeros(n, dtype=torch.float32, device=emap.device)
+        if out is not None and out.numel() != out_w * out_h:
+            raise ValueError("out is not out_h x out_w")
+        self._check(self.L.pf_fuse_check(self.h, _ptr(emap), ew, eh, ec, _ptr(tiles),
+                                         _ptr(coeffs), out_w, out_h, float(zr[0]), float(zr[1]),
+                                         _ptr(err), _ptr(out)))
+        return err
 
     def warp_depth(self, pano, tiles, resp=None):
         B, ph, pw = pano.shape
