@@ -1,0 +1,312 @@
+// pf_depth_merge.cpp -- MergeDepthMaps and MergeDisparityMaps of the DepthNamespace facade.
+//
+// The reference's MergeDepthMaps (Depth.cpp:754-1041) loads the baseline and the tiles, runs
+// SolveDepthToDepth + Depth2DepthTransform per tile, SolveDepthAll, writes the u16 PNG and, with
+// a ground truth, ErrorEmap/ErrorData plus the .res.png/.giv.png masks.  Here the loads and the
+// file writes stay on the host (they are file formats), every per-pixel computation of the path
+// (registration, transform, fusion, quantisation, metrics) is a libpanofuse HIP kernel.
+#include "pf_facade.hpp"
+
+#include <chrono>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <future>
+
+namespace DepthNamespace {
+namespace {
+using namespace pff;
+
+// The environment switches of a Merge* call (panofuse_main sets them from --fusion,
+// --save-stitch, --check-laplacian, --global-align), read once at the top of the call.
+// fusion: what fills the result (Depth.cpp:904-922, :851), the choice the reference makes by
+// editing `if (true/false)`; save_stitch / check_laplacian: its two `if (false)` diagnostics
+// (:817-865, :1738-1758); global_align: the fused result is pulled back onto the baseline by
+// SolveDepthToDepth2's cubic before it is written and scored.
+struct MergeSwitches {
+    enum { LAPLACIAN, SMOOTHING, STITCH } fusion = LAPLACIAN;
+    bool save_stitch = false, check_laplacian = false, global_align = false;
+};
+
+bool read_merge_switches(MergeSwitches& s)
+{
+    const auto env_on = [](const char* name) {
+        const char* v = std::getenv(name);
+        return v && std::strcmp(v, "1") == 0;
+    };
+    if (const char* fu = std::getenv("PF_FUSION")) {
+        if (std::strcmp(fu, "smoothing") == 0) s.fusion = MergeSwitches::SMOOTHING;
+        else if (std::strcmp(fu, "stitch") == 0) s.fusion = MergeSwitches::STITCH;
+        else if (*fu && std::strcmp(fu, "laplacian") != 0) {
+            std::cout << "[MergeDepthMaps] bad PF_FUSION " << fu
+                      << " (want laplacian, smoothing or stitch)" << std::endl;
+            return false;
+        }
+    }
+    s.save_stitch = env_on("PF_SAVE_STITCH");
+    s.check_laplacian = env_on("PF_CHECK_LAPLACIAN");
+    s.global_align = env_on("PF_GLOBAL_ALIGN");
+    if (s.check_laplacian && s.fusion != MergeSwitches::LAPLACIAN) {
+        std::cout << "[MergeDepthMaps] PF_CHECK_LAPLACIAN needs PF_FUSION=laplacian: only the "
+                     "fusion has Laplacian targets" << std::endl;
+        return false;
+    }
+    return true;
+}
+
+int elapsed_ms(std::chrono::steady_clock::time_point t0)
+{
+    return (int)std::chrono::duration_cast<std::chrono::milliseconds>(
+               std::chrono::steady_clock::now() - t0)
+        .count();
+}
+
+// MergeDepthMaps stores MIN2(range, D2R(359.9)) (Depth.cpp:783-784: a float against a double,
+// the double result rounded back to float).
+float cap_range(float r)
+{
+    const double cap = PF_D2R(359.9);
+    return (float)((double)r < cap ? (double)r : cap);
+}
+
+// The baseline and the tiles from their files, the tiles with their windows and ranges
+// (Depth.cpp:773-787); the tiles decode in parallel host threads (zlib inflate is the host cost).
+bool load_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::vector<Vec4f>& fovs,
+               std::vector<Vec4f>& ranges, EquirectangularMap& emap,
+               std::vector<PerspectiveMap>& pmaps)
+{
+    if (!emap.Load(emap_fn)) return false;
+    if (fovs.size() < pmap_fns.size() || ranges.size() < pmap_fns.size()) {
+        std::cout << "[MergeDepthMaps] fewer FOVs/ranges than maps" << std::endl;
+        return false;
+    }
+    pmaps.resize(pmap_fns.size());
+    std::vector<std::future<bool>> loads;
+    for (size_t i = 0; i < pmap_fns.size(); i++)
+        loads.push_back(
+            std::async(std::launch::async, [&, i] { return pmaps[i].Load(pmap_fns[i]); }));
+    bool ok = true;
+    for (auto& f : loads) ok = f.get() && ok;
+    if (!ok) return false;
+    for (size_t i = 0; i < pmap_fns.size(); i++) {
+        PerspectiveMap& p = pmaps[i];
+        p.SetWindow(fovs[i][0], fovs[i][1], fovs[i][2], fovs[i][3]);
+        p.ranges = Vec4f(cap_range(ranges[i][0]), cap_range(ranges[i][1]), ranges[i][2],
+                         ranges[i][3]);
+    }
+    return true;
+}
+
+// What the GPU steps work on: the baseline, the packed tiles, the per-tile cubics the fusion
+// applies (null for disparity tiles, which the registration has transformed already) and the
+// u16 result, all on the device.
+struct Job {
+    pf_ctx* c;
+    const EquirectangularMap& emap;
+    const float* d_emap;
+    float* d_tiles;  // the disparity registration transforms them in place
+    const float* d_coeffs;
+    uint16_t* d_out;
+    int w, h;
+    Vec2f& zr;
+};
+
+// Registration (Depth.cpp:789-808): every tile alone; depth tiles: cubic, the transform fused
+// into the fusion; disparity tiles: y = 1/(a x + b) + d, D2DTransform on the uploaded copy.
+bool register_tiles(const Job& j, float* d_coeffs, bool disparity_tiles)
+{
+    const EquirectangularMap& e = j.emap;
+    return call_sync(j.c,
+                     disparity_tiles
+                         ? pf_register_disparity(j.c, j.d_emap, e.width, e.height, e.channels,
+                                                 j.d_tiles, 1, j.zr[0], j.zr[1], 1, d_coeffs,
+                                                 nullptr, nullptr)
+                         : pf_register(j.c, j.d_emap, e.width, e.height, e.channels, j.d_tiles, 1,
+                                       j.zr[0], j.zr[1], 3, 0, d_coeffs, nullptr),
+                     disparity_tiles ? "pf_register_disparity" : "pf_register");
+}
+
+// The fusion (Depth.cpp:904-913), or the smoothing (:919-922) / the stitch (:851) on the
+// registered tiles.
+bool fuse(const Job& j, const MergeSwitches& s)
+{
+    const EquirectangularMap& e = j.emap;
+    switch (s.fusion) {
+    case MergeSwitches::SMOOTHING:
+        return call_sync(j.c, pf_solve_smoothing(j.c, j.d_tiles, j.d_coeffs, 1, j.w, j.h, j.zr[0],
+                                                 j.zr[1], j.d_out),
+                         "pf_solve_smoothing");
+    case MergeSwitches::STITCH:
+        return call_sync(j.c, pf_stitch(j.c, j.d_tiles, j.d_coeffs, 1, j.w, j.h, j.d_out),
+                         "pf_stitch");
+    default:
+        return call_sync(j.c, pf_fuse(j.c, j.d_emap, e.width, e.height, e.channels, j.d_tiles,
+                                      j.d_coeffs, 1, j.w, j.h, j.zr[0], j.zr[1], j.d_out),
+                         "pf_fuse");
+    }
+}
+
+// Depth.cpp:1738-1758: the last level's number, in the reference's words.
+bool print_laplacian_check(const Job& j)
+{
+    const EquirectangularMap& e = j.emap;
+    int nlevels = 0;
+    DevMem derr(sizeof(float) * 4);
+    float err[4] = {};
+    if (!derr.ok ||
+        !pf_ok(j.c, pf_level_info(j.w, j.h, j.zr[0], j.zr[1], 0, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr, &nlevels),
+               "pf_level_info") ||
+        nlevels < 1 || nlevels > 4 ||
+        !call_sync(j.c, pf_fuse_check(j.c, j.d_emap, e.width, e.height, e.channels, j.d_tiles,
+                                      j.d_coeffs, j.w, j.h, j.zr[0], j.zr[1], derr.as<float>(),
+                                      nullptr),
+                   "pf_fuse_check") ||
+        !download(err, derr, nlevels))
+        return false;
+    std::cout << std::endl << "[SolveDepthAll] check Laplacian err:" << err[nlevels - 1]
+              << std::endl;
+    return true;
+}
+
+// Depth.cpp:817-865: <out>.pmap.png, the direct stitch of the registered tiles.
+bool save_stitch(const Job& j, const std::string& out_fn)
+{
+    const size_t no = (size_t)j.w * j.h;
+    DevMem ds(no * 2);
+    std::vector<unsigned short> st(no);
+    return ds.ok &&
+           call_sync(j.c, pf_stitch(j.c, j.d_tiles, j.d_coeffs, 1, j.w, j.h, ds.as<uint16_t>()),
+                     "pf_stitch") &&
+           download(st.data(), ds, no) &&
+           Save16BitPNG(st.data(), j.w, j.h, (out_fn + ".pmap.png").c_str());
+}
+
+// A u16 map masked by the gt's invalid (0) / saturated pixels and the zenith band.
+template <class ValueAt>
+void save_masked(EquirectangularMap& gt, Vec2f& zr, int w, int h, ValueAt value_at,
+                 const std::string& fn)
+{
+    const int h0 = (int)std::floor(h * zr[0] / PF_MYPI_D);
+    const int h1 = (int)std::ceil(h * zr[1] / PF_MYPI_D);
+    std::vector<unsigned short> o((size_t)w * h);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            unsigned short& d = o[(size_t)y * w + x];
+            if (y < h0 || y > h1) {
+                d = 0;
+                continue;
+            }
+            const int X = (int)((float)x * (float)gt.width / (float)w);
+            const int Y = (int)((float)y * (float)gt.height / (float)h);
+            const float g = gt.ValueAtXY(X, Y);
+            d = g == 0 ? 0 : ((double)g >= 1 - 1e-4 ? 65535 : value_at(x, y));
+        }
+    Save16BitPNG(o.data(), w, h, fn.c_str());
+}
+
+// Depth.cpp:920-1037: the baseline's and the result's metrics against the gt, printed, and the
+// two masked maps <out>.res.png / <out>.giv.png (the first on a host thread beside the second).
+void score_and_mask(EquirectangularMap& gt, EquirectangularMap& emap,
+                    std::vector<unsigned short>& data, int w, int h, Vec2f& zr,
+                    const std::string& out_fn, Metrics* metrics)
+{
+    const int align_way = 1;
+    const bool cap_depth = true;
+    Metrics local;
+    Metrics& M = metrics ? *metrics : local;
+    ErrorEmap(gt, emap, M.mse_given, M.mae_given, M.mre_given, M.mselog_given, M.delta1_given,
+              M.delta2_given, M.delta3_given, align_way, cap_depth);
+    ErrorData(gt, data.data(), w, h, M.mse_result, M.mae_result, M.mre_result, M.mselog_result,
+              M.delta1_result, M.delta2_result, M.delta3_result, align_way, cap_depth);
+    M.Print();
+    auto res = std::async(std::launch::async, [&] {
+        save_masked(gt, zr, w, h, [&](int x, int y) { return data[(size_t)y * w + x]; },
+                    out_fn + ".res.png");
+    });
+    save_masked(gt, zr, emap.width, emap.height,
+                [&](int x, int y) { return (unsigned short)(emap.ValueAtXY(x, y) * 65535.0f); },
+                out_fn + ".giv.png");
+    res.get();
+}
+
+// The body of MergeDepthMaps for depth tiles, or with disparity_tiles for tiles that hold
+// relative inverse depth (MergeDisparityMaps): only the registration differs.
+bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::string& out_fn,
+                std::vector<Vec4f>& fovs, std::vector<Vec4f>& ranges, int out_width, Vec2f& zr,
+                std::string* gt_fn, Metrics* metrics, int* time_Reg, int* time_Laplacian,
+                bool disparity_tiles)
+{
+    const auto t_begin = std::chrono::steady_clock::now();
+    MergeSwitches sw;
+    if (!read_merge_switches(sw)) return false;
+    EquirectangularMap emap, gt;
+    std::vector<PerspectiveMap> pmaps;
+    // the ground truth decodes on a host thread while the tiles load and the GPU fuses
+    std::future<bool> gt_loaded;
+    if (gt_fn) gt_loaded = std::async(std::launch::async, [&] { return gt.Load(*gt_fn); });
+    struct Join {  // never leave with the loader still writing into `gt`
+        std::future<bool>& f;
+        ~Join()
+        {
+            if (f.valid()) f.wait();
+        }
+    } join{gt_loaded};
+    if (!load_maps(emap_fn, pmap_fns, fovs, ranges, emap, pmaps)) return false;
+    const int out_height = out_width / 2;
+    const size_t no = (size_t)out_width * out_height;
+
+    pf_ctx* c = facade_ctx();
+    if (!c) return false;
+    DevMem dt = tiles_on_device(c, pmaps);
+    if (!dt.ok) return false;
+    DevMem de = on_device(emap), dc(sizeof(float) * 4 * pmaps.size()), dout(no * 2);
+    if (!de.ok || !dc.ok || !dout.ok) return false;
+    const Job j{c, emap, de.as<float>(), dt.as<float>(),
+                disparity_tiles ? nullptr : dc.as<float>(), dout.as<uint16_t>(), out_width,
+                out_height, zr};
+
+    auto t = std::chrono::steady_clock::now();
+    if (!register_tiles(j, dc.as<float>(), disparity_tiles)) return false;
+    if (time_Reg) *time_Reg = elapsed_ms(t);
+    t = std::chrono::steady_clock::now();
+    if (!fuse(j, sw)) return false;
+    if (time_Laplacian) *time_Laplacian = elapsed_ms(t);
+    if (sw.check_laplacian && !print_laplacian_check(j)) return false;
+    if (sw.save_stitch && !save_stitch(j, out_fn)) return false;
+    Vec4f g;
+    if (sw.global_align &&
+        !global_fit(c, j.d_emap, emap, j.d_out, out_width, out_height, zr, true, g))
+        return false;
+
+    std::vector<unsigned short> data(no);
+    if (!download(data.data(), dout, no) ||
+        !Save16BitPNG(data.data(), out_width, out_height, out_fn.c_str()))
+        return false;
+    std::cout << "...All done! @" << elapsed_ms(t_begin) << std::endl;
+    if (gt_fn && gt_loaded.get())
+        score_and_mask(gt, emap, data, out_width, out_height, zr, out_fn, metrics);
+    return true;
+}
+}  // namespace
+
+bool MergeDepthMaps(std::string& emap_fn, std::vector<std::string>& pmap_fns,
+                    std::string& out_fn, std::vector<Vec4f>& fovs, std::vector<Vec4f>& ranges,
+                    int out_width, Vec2f& zr, std::string* gt_fn, Metrics* metrics,
+                    int* time_Reg, int* time_Laplacian)
+{
+    return merge_maps(emap_fn, pmap_fns, out_fn, fovs, ranges, out_width, zr, gt_fn, metrics,
+                      time_Reg, time_Laplacian, false);
+}
+
+bool MergeDisparityMaps(std::string& emap_fn, std::vector<std::string>& pmap_fns,
+                        std::string& out_fn, std::vector<Vec4f>& fovs,
+                        std::vector<Vec4f>& ranges, int out_width, Vec2f& zr,
+                        std::string* gt_fn, Metrics* metrics, int* time_Reg,
+                        int* time_Laplacian)
+{
+    return merge_maps(emap_fn, pmap_fns, out_fn, fovs, ranges, out_width, zr, gt_fn, metrics,
+                      time_Reg, time_Laplacian, true);
+}
+
+}  // namespace DepthNamespace

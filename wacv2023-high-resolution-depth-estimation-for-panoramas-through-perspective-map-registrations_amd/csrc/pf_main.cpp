@@ -38,7 +38,8 @@
 // <raw>.<a0>_<a1>_<z0>_<z1>.<ext>; "auto" takes .jpg when present, else .png (MiDaS naming).
 // --metrics-order: the .aligned.txt means in the reference's row-major float order (sequential,
 // the default: the digits Main.cpp prints) or in the fp64-tree order (tree: deterministic, within
-// ~1e-3 relative of the reference's float sums).
+// 1e-2 relative of the reference's float sums: MEAN_RTOL, the bound tests/test_gpu_metrics.py
+// asserts for the tree order).
 // --tile-model: what the tiles hold.  depth (the default: LeReS-style tiles, the cubic
 // registration) or disparity (MiDaS / DPT tiles, relative inverse depth in 0-1: each is fitted
 // with y = 1/(a x + b) + d and mapped to depth by D2DTransform).  The reference's MiDaS folder
@@ -56,68 +57,141 @@
 // registered tiles (the reference's debug file, Depth.cpp:859).
 // --check-laplacian (opt-in, takes no value, only with --fusion laplacian): print SolveDepthAll's
 // self-check "[SolveDepthAll] check Laplacian err:<err>" (Depth.cpp:1738-1758) per panorama.
-#include "../../include/panofuse.h"
-#include "../../include/pf_depth.h"
-
-#include <hip/hip_runtime.h>
+#include "pf_facade.hpp"  // the inline to_window and load_pair; it includes the two public headers
 
 #include <cstdio>
 #include <cstdlib>
-#include <iostream>
 #include <string>
 #include <vector>
 
+using pff::to_window;
+
+static const char* const kUsageExport = " export <rgb_dir> <tile_dir> [--device D] [--layout NAME|FILE]";
+static const char* const kUsageLayout = " layout NAME|FILE [--width W] [--tile-size WxH] [--device D]";
+static const char* const kUsageLap = " lap <gt_file> <given_file> [--device D]";
+static const char* const kUsageCmp =
+    " cmp <gt_file> <given_file> [--disp] [--align 0|1|2] [--no-cap] [--save FILE] [--device D]"
+    " [--metrics-order tree|sequential]";
+
+static int usage(const char* argv0, const char* text)
+{
+    std::cout << "usage: " << argv0 << text << std::endl;
+    return 1;
+}
+
+// The answer to a rejected option value, and its exit status.
+static int bad(const std::string& k, const std::string& v, const std::string& want)
+{
+    std::cout << "bad " << k << " " << v << " (want " << want << ")" << std::endl;
+    return 2;
+}
+
+static bool select_device(int dev)
+{
+    if (hipSetDevice(dev) == hipSuccess) return true;
+    std::cout << "no HIP device " << dev << std::endl;
+    return false;
+}
+
+// An option that travels to the facade in an environment variable: a switch (no values: the
+// variable becomes "1") or one of the listed values.
+struct EnvFlag {
+    const char* name;
+    std::vector<const char*> values;
+    const char* var;
+};
+static const EnvFlag kEnvFlags[] = {
+    {"--edge-metrics", {}, "PF_EDGE_METRICS"},  // read by pf_create_depth_panoramas
+    {"--tile-model", {"depth", "disparity"}, "PF_TILE_MODEL"},
+    {"--global-align", {}, "PF_GLOBAL_ALIGN"},  // read by MergeDepthMaps / MergeDisparityMaps
+    {"--save-stitch", {}, "PF_SAVE_STITCH"},
+    {"--check-laplacian", {}, "PF_CHECK_LAPLACIAN"},
+    {"--fusion", {"laplacian", "smoothing", "stitch"}, "PF_FUSION"},
+    {"--metrics-order", {"tree", "sequential"}, "PF_METRICS_ORDER"},  // when the context is made
+};
+
+// The handlers below answer 0 (taken), 2 (rejected, the message is printed) or -1 (not mine).
+// k as a switch (v null) or with its value v.
+static int take_env_flag(const std::string& k, const char* v)
+{
+    for (const EnvFlag& f : kEnvFlags) {
+        if (k != f.name || f.values.empty() != !v) continue;
+        bool ok = !v;
+        std::string want;  // "a, b or c"
+        for (size_t i = 0; i < f.values.size(); ++i) {
+            ok = ok || std::string(f.values[i]) == v;
+            want += i == 0 ? "" : i + 1 == f.values.size() ? " or " : ", ";
+            want += f.values[i];
+        }
+        if (!ok) return bad(k, v, want);
+        setenv(f.var, v ? v : "1", 1);
+        return 0;
+    }
+    return -1;
+}
+
 // --layout's value: checked here (no GPU call yet), carried to the facade in PF_LAYOUT.
-static bool take_layout(const std::string& v)
+static int take_layout(const std::string& v)
 {
     std::vector<Vec4f> fovs, ranges;
     std::string err;
     if (!pf_resolve_layout(v, fovs, ranges, &err)) {
         std::cout << "bad --layout: " << err << std::endl;
-        return false;
+        return 2;
     }
     setenv("PF_LAYOUT", v.c_str(), 1);  // read by pf_create_depth_panoramas / pf_export_rgb_tiles
-    return true;
+    return 0;
 }
 
-static int layout_command(int argc, char* argv[])
+// Walks argv[first..]: on_switch(k) takes an option that has no value, on_value(k, v) one that
+// has.  An option at the end that lacks its value ends the walk: silently when `lenient` (mode 0),
+// else with "option ... needs a value" and status 2.  Returns 0 or the status to exit with.
+template <class OnSwitch, class OnValue>
+static int walk_options(int argc, char* argv[], int first, bool lenient, OnSwitch on_switch,
+                        OnValue on_value)
 {
-    if (argc < 3) {
-        std::cout << "usage: " << argv[0]
-                  << " layout NAME|FILE [--width W] [--tile-size WxH] [--device D]" << std::endl;
-        return 1;
-    }
-    int width = 2048, tw = 1024, th = 1024, dev = 0;
-    for (int i = 3; i < argc; i += 2) {
+    for (int i = first; i < argc; ++i) {
         const std::string k(argv[i]);
-        if (i + 1 >= argc) {
-            std::cout << "option " << k << " needs a value" << std::endl;
-            return 2;
-        }
-        const std::string v(argv[i + 1]);
-        if (k == "--width") width = std::atoi(v.c_str());
-        else if (k == "--device") dev = std::atoi(v.c_str());
-        else if (k == "--tile-size") {
-            if (std::sscanf(v.c_str(), "%dx%d", &tw, &th) != 2 || tw < 2 || th < 2) {
-                std::cout << "bad --tile-size " << v << " (want WxH)" << std::endl;
+        int rc = on_switch(k);
+        if (rc < 0) {
+            if (i + 1 >= argc) {
+                if (lenient) break;
+                std::cout << "option " << k << " needs a value" << std::endl;
+                return 2;
+            }
+            rc = on_value(k, std::string(argv[++i]));
+            if (rc < 0) {
+                std::cout << "unknown option " << k << std::endl;
                 return 2;
             }
         }
-        else {
-            std::cout << "unknown option " << k << std::endl;
-            return 2;
-        }
+        if (rc > 0) return rc;
     }
+    return 0;
+}
+
+static int no_switch(const std::string&) { return -1; }
+
+static int layout_command(int argc, char* argv[])
+{
+    if (argc < 3) return usage(argv[0], kUsageLayout);
+    int width = 2048, tw = 1024, th = 1024, dev = 0;
+    const auto on_value = [&](const std::string& k, const std::string& v) {
+        if (k == "--width") width = std::atoi(v.c_str());
+        else if (k == "--device") dev = std::atoi(v.c_str());
+        else if (k != "--tile-size") return -1;
+        else if (std::sscanf(v.c_str(), "%dx%d", &tw, &th) != 2 || tw < 2 || th < 2)
+            return bad(k, v, "WxH");
+        return 0;
+    };
+    if (int rc = walk_options(argc, argv, 3, false, no_switch, on_value)) return rc;
     std::vector<Vec4f> fovs, ranges;
     std::string err;
     if (!pf_resolve_layout(argv[2], fovs, ranges, &err)) {
         std::cout << "bad layout: " << err << std::endl;
         return 2;
     }
-    if (hipSetDevice(dev) != hipSuccess) {
-        std::cout << "no HIP device " << dev << std::endl;
-        return 1;
-    }
+    if (!select_device(dev)) return 1;
     pf_ctx* c = nullptr;
     if (pf_create(dev, &c) != PF_OK) {
         std::cout << "pf_create(" << dev << ") failed" << std::endl;
@@ -127,8 +201,8 @@ static int layout_command(int argc, char* argv[])
     std::vector<pf_window> fw(n), rw(n);
     std::vector<int> tws(n, tw), ths(n, th);
     for (int i = 0; i < n; ++i) {
-        fw[i] = pf_window{fovs[i][0], fovs[i][1], fovs[i][2], fovs[i][3]};
-        rw[i] = pf_window{ranges[i][0], ranges[i][1], ranges[i][2], ranges[i][3]};
+        fw[i] = to_window(fovs[i]);
+        rw[i] = to_window(ranges[i]);
     }
     int rc = pf_set_tiles(c, fw.data(), rw.data(), n, tws.data(), ths.data(), 1, 1);
     int nlevels = 0;
@@ -153,6 +227,131 @@ static int layout_command(int argc, char* argv[])
     return rc == PF_OK ? 0 : 1;
 }
 
+static int export_command(int argc, char* argv[])
+{
+    if (argc < 4) return usage(argv[0], kUsageExport);
+    int dev = 0;
+    const auto on_value = [&](const std::string& k, const std::string& v) {
+        if (k == "--layout") return take_layout(v);
+        if (k != "--device") return -1;
+        dev = std::atoi(v.c_str());
+        return 0;
+    };
+    if (int rc = walk_options(argc, argv, 4, false, no_switch, on_value)) return rc;
+    if (!select_device(dev)) return 1;
+    return pf_export_rgb_tiles(argv[2], argv[3]);
+}
+
+static int lap_command(int argc, char* argv[])
+{
+    if (argc < 4) return usage(argv[0], kUsageLap);
+    // --device is taken as the fourth argument only
+    const int dev = argc >= 6 && std::string(argv[4]) == "--device" ? std::atoi(argv[5]) : 0;
+    if (!select_device(dev)) return 1;
+    std::string gt_fn(argv[2]), given_fn(argv[3]);
+    DepthNamespace::EquirectangularMap gt, given;
+    if (!pff::load_pair(gt_fn, given_fn, false, gt, given)) return 1;
+    double v[5];
+    long long n[3];
+    if (!DepthNamespace::ErrorLaplacian(gt, given, v[0], v[1], v[2], v[3], v[4], n)) return 1;
+    std::cout << "[ErrorLap] n_lap:" << n[0] << " n_sobel:" << n[1] << " n_lap5:" << n[2]
+              << std::endl;
+    return 0;
+}
+
+static int cmp_command(int argc, char* argv[])
+{
+    if (argc < 4) return usage(argv[0], kUsageCmp);
+    bool disp = false, cap = true;
+    int align = 1, dev = 0;
+    std::string save;
+    const auto on_switch = [&](const std::string& k) {
+        if (k == "--disp") disp = true;
+        else if (k == "--no-cap") cap = false;
+        else return -1;
+        return 0;
+    };
+    const auto on_value = [&](const std::string& k, const std::string& v) {
+        if (k == "--align") align = std::atoi(v.c_str());
+        else if (k == "--save") save = v;
+        else if (k == "--device") dev = std::atoi(v.c_str());
+        else if (k == "--metrics-order") return take_env_flag(k, v.c_str());
+        else return -1;
+        return 0;
+    };
+    if (int rc = walk_options(argc, argv, 4, false, on_switch, on_value)) return rc;
+    if (align < 0 || align > 2) return bad("--align", std::to_string(align), "0, 1 or 2");
+    // the loads come first: a file that does not load ends the command before any GPU call
+    std::string gt_fn(argv[2]), given_fn(argv[3]);
+    DepthNamespace::EquirectangularMap gt, given;
+    if (!pff::load_pair(gt_fn, given_fn, true /*mono360*/, gt, given)) return 1;
+    if (!select_device(dev)) return 1;
+    float v[7];
+    Vec2f fit, minmax;
+    int n_nonblack = 0;
+    std::vector<unsigned char> shifted;
+    if (!DepthNamespace::ErrorCompare(gt, given, disp, v[0], v[1], v[2], v[3], v[4], v[5], v[6],
+                                      align, cap, &fit, &minmax, save.empty() ? nullptr : &shifted,
+                                      &n_nonblack))
+        return 1;
+    std::printf("CMP %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", v[0], v[1], v[2], v[3], v[4], v[5],
+                v[6]);
+    if (disp)
+        std::printf("FIT %.9g %.9g %.9g %.9g %d\n", fit[0], fit[1], minmax[0], minmax[1],
+                    n_nonblack);
+    std::fflush(stdout);
+    if (!save.empty()) {
+        const bool ok = Save8BitPNG(shifted.data(), given.width, given.height, save.c_str());
+        std::cout << "[ErrorCompare] " << (ok ? 1 : 0) << " saved shifted emap:" << save
+                  << std::endl;
+        if (!ok) return 1;
+    }
+    return 0;
+}
+
+static int mode0_command(int argc, char* argv[])
+{
+    if (argc < 6) {
+        std::cout << "[CreateDepthPanormas] error: need argc>=6" << std::endl;
+        return 1;
+    }
+    std::string tiles = "test_images", ext = "auto", fusion;
+    int width = 2048, device = 0, shard = 0, nshards = 1;
+    bool check_laplacian = false;
+    const auto on_switch = [&](const std::string& k) {
+        if (k == "--check-laplacian") check_laplacian = true;
+        return take_env_flag(k, nullptr);
+    };
+    const auto on_value = [&](const std::string& k, const std::string& v) {
+        if (k == "--tiles") tiles = v;
+        else if (k == "--ext") ext = v;
+        else if (k == "--width") width = std::atoi(v.c_str());
+        else if (k == "--device") device = std::atoi(v.c_str());
+        else if (k == "--layout") return take_layout(v);
+        else if (k == "--shard") {  // R/N: one process per GPU over the sorted folder
+            if (std::sscanf(v.c_str(), "%d/%d", &shard, &nshards) != 2 || nshards < 1 ||
+                shard < 0 || shard >= nshards)
+                return bad(k, v, "R/N, 0 <= R < N");
+        }
+        else {
+            if (k == "--fusion") fusion = v;
+            return take_env_flag(k, v.c_str());
+        }
+        return 0;
+    };
+    if (int rc = walk_options(argc, argv, 6, true, on_switch, on_value)) return rc;
+    // the self-check compares the Jacobi result with its targets: only the fusion has them.  The
+    // facade has the same rule for its environment; this one fails before any GPU call.
+    if (check_laplacian && !fusion.empty() && fusion != "laplacian") {
+        std::cout << "--check-laplacian needs --fusion laplacian (got " << fusion << ")"
+                  << std::endl;
+        return 2;
+    }
+    if (!select_device(device)) return 1;
+    return pf_create_depth_panoramas(argv[2], argv[3], argv[4], argv[5], tiles, ext, width, shard,
+                                     nshards);
+}
+
 int main(int argc, char* argv[])
 {
     if (argc < 2) {
@@ -167,237 +366,16 @@ int main(int argc, char* argv[])
                      " --layout midas --tile-model disparity --tiles output --ext png)\n"
                      "         (--layout: leres (default), midas, fold4, fold3, or a file of"
                      " lines `faz0 faz1 fzen0 fzen1 raz0 raz1 rzen0 rzen1` in degrees)\n       "
-                  << argv[0] << " export <rgb_dir> <tile_dir> [--device D] [--layout NAME|FILE]\n       "
-                  << argv[0] << " layout NAME|FILE [--width W] [--tile-size WxH] [--device D]\n       "
-                  << argv[0] << " lap <gt_file> <given_file> [--device D]\n       "
-                  << argv[0]
-                  << " cmp <gt_file> <given_file> [--disp] [--align 0|1|2] [--no-cap] [--save FILE]"
-                     " [--device D] [--metrics-order tree|sequential]"
+                  << argv[0] << kUsageExport << "\n       " << argv[0] << kUsageLayout
+                  << "\n       " << argv[0] << kUsageLap << "\n       " << argv[0] << kUsageCmp
                   << std::endl;
         return 0;
     }
     const std::string cmd(argv[1]);
-    if (cmd == "export") {
-        if (argc < 4) {
-            std::cout << "usage: " << argv[0]
-                      << " export <rgb_dir> <tile_dir> [--device D] [--layout NAME|FILE]"
-                      << std::endl;
-            return 1;
-        }
-        int dev = 0;
-        for (int i = 4; i < argc; i += 2) {
-            const std::string k(argv[i]);
-            if (i + 1 >= argc) {
-                std::cout << "option " << k << " needs a value" << std::endl;
-                return 2;
-            }
-            const std::string v(argv[i + 1]);
-            if (k == "--device") dev = std::atoi(v.c_str());
-            else if (k == "--layout") {
-                if (!take_layout(v)) return 2;
-            }
-            else {
-                std::cout << "unknown option " << k << std::endl;
-                return 2;
-            }
-        }
-        if (hipSetDevice(dev) != hipSuccess) {
-            std::cout << "no HIP device " << dev << std::endl;
-            return 1;
-        }
-        return pf_export_rgb_tiles(argv[2], argv[3]);
-    }
+    if (cmd == "export") return export_command(argc, argv);
     if (cmd == "layout") return layout_command(argc, argv);
-    if (cmd == "lap") {
-        if (argc < 4) {
-            std::cout << "usage: " << argv[0] << " lap <gt_file> <given_file> [--device D]"
-                      << std::endl;
-            return 1;
-        }
-        const int dev = argc >= 6 && std::string(argv[4]) == "--device" ? std::atoi(argv[5]) : 0;
-        if (hipSetDevice(dev) != hipSuccess) {
-            std::cout << "no HIP device " << dev << std::endl;
-            return 1;
-        }
-        std::string gt_fn(argv[2]), given_fn(argv[3]);
-        DepthNamespace::EquirectangularMap gt, given;
-        if (!gt.Load(gt_fn)) {
-            std::cout << "cannot load emap_gt? " << gt_fn << std::endl;
-            return 1;
-        }
-        if (!given.Load(given_fn)) {
-            std::cout << "cannot load emap_baseline? " << given_fn << std::endl;
-            return 1;
-        }
-        double v[5];
-        long long n[3];
-        if (!DepthNamespace::ErrorLaplacian(gt, given, v[0], v[1], v[2], v[3], v[4], n)) return 1;
-        std::cout << "[ErrorLap] n_lap:" << n[0] << " n_sobel:" << n[1] << " n_lap5:" << n[2]
-                  << std::endl;
-        return 0;
-    }
-    if (cmd == "cmp") {
-        if (argc < 4) {
-            std::cout << "usage: " << argv[0]
-                      << " cmp <gt_file> <given_file> [--disp] [--align 0|1|2] [--no-cap]"
-                         " [--save FILE] [--device D] [--metrics-order tree|sequential]"
-                      << std::endl;
-            return 1;
-        }
-        bool disp = false, cap = true;
-        int align = 1, dev = 0;
-        std::string save;
-        for (int i = 4; i < argc; ++i) {
-            const std::string k(argv[i]);
-            if (k == "--disp") disp = true;
-            else if (k == "--no-cap") cap = false;
-            else if (i + 1 >= argc) {
-                std::cout << "option " << k << " needs a value" << std::endl;
-                return 2;
-            }
-            else if (k == "--align") align = std::atoi(argv[++i]);
-            else if (k == "--save") save = argv[++i];
-            else if (k == "--device") dev = std::atoi(argv[++i]);
-            else if (k == "--metrics-order") {
-                const std::string v(argv[++i]);
-                if (v != "tree" && v != "sequential") {
-                    std::cout << "bad --metrics-order " << v << " (want tree or sequential)"
-                              << std::endl;
-                    return 2;
-                }
-                setenv("PF_METRICS_ORDER", v.c_str(), 1);  // read when the facade's context is made
-            }
-            else {
-                std::cout << "unknown option " << k << std::endl;
-                return 2;
-            }
-        }
-        if (align < 0 || align > 2) {
-            std::cout << "bad --align " << align << " (want 0, 1 or 2)" << std::endl;
-            return 2;
-        }
-        // the loads come first: a file that does not load ends the command before any GPU call
-        std::string gt_fn(argv[2]), given_fn(argv[3]);
-        DepthNamespace::EquirectangularMap gt, given;
-        if (!gt.Load(gt_fn)) {
-            std::cout << "cannot load emap_gt? " << gt_fn << std::endl;
-            return 1;
-        }
-        if (!given.Load(given_fn, true /*mono360*/)) {
-            std::cout << "cannot load emap_baseline? " << given_fn << std::endl;
-            return 1;
-        }
-        if (hipSetDevice(dev) != hipSuccess) {
-            std::cout << "no HIP device " << dev << std::endl;
-            return 1;
-        }
-        float v[7];
-        Vec2f fit, minmax;
-        int n_nonblack = 0;
-        std::vector<unsigned char> shifted;
-        if (!DepthNamespace::ErrorCompare(gt, given, disp, v[0], v[1], v[2], v[3], v[4], v[5], v[6],
-                                          align, cap, &fit, &minmax, save.empty() ? nullptr : &shifted,
-                                          &n_nonblack))
-            return 1;
-        std::printf("CMP %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", v[0], v[1], v[2], v[3], v[4], v[5],
-                    v[6]);
-        if (disp)
-            std::printf("FIT %.9g %.9g %.9g %.9g %d\n", fit[0], fit[1], minmax[0], minmax[1],
-                        n_nonblack);
-        std::fflush(stdout);
-        if (!save.empty()) {
-            const bool ok = Save8BitPNG(shifted.data(), given.width, given.height, save.c_str());
-            std::cout << "[ErrorCompare] " << (ok ? 1 : 0) << " saved shifted emap:" << save
-                      << std::endl;
-            if (!ok) return 1;
-        }
-        return 0;
-    }
-    if (cmd != "0") return 0;  // Main.cpp:889-893: other commands do nothing
-    if (argc < 6) {
-        std::cout << "[CreateDepthPanormas] error: need argc>=6" << std::endl;
-        return 1;
-    }
-    std::string tiles = "test_images", ext = "auto";
-    int width = 2048, device = 0, shard = 0, nshards = 1;
-    for (int i = 6; i < argc; i += 2) {
-        const std::string k(argv[i]);
-        if (k == "--edge-metrics") {  // a flag without a value
-            setenv("PF_EDGE_METRICS", "1", 1);  // read by pf_create_depth_panoramas
-            --i;
-            continue;
-        }
-        if (k == "--global-align") {  // a flag without a value
-            setenv("PF_GLOBAL_ALIGN", "1", 1);  // read by MergeDepthMaps / MergeDisparityMaps
-            --i;
-            continue;
-        }
-        if (k == "--save-stitch") {  // a flag without a value
-            setenv("PF_SAVE_STITCH", "1", 1);  // read by MergeDepthMaps / MergeDisparityMaps
-            --i;
-            continue;
-        }
-        if (k == "--check-laplacian") {  // a flag without a value
-            setenv("PF_CHECK_LAPLACIAN", "1", 1);  // read by MergeDepthMaps / MergeDisparityMaps
-            --i;
-            continue;
-        }
-        if (i + 1 >= argc) break;
-        const std::string v(argv[i + 1]);
-        if (k == "--tiles") tiles = v;
-        else if (k == "--fusion") {
-            if (v != "laplacian" && v != "smoothing" && v != "stitch") {
-                std::cout << "bad --fusion " << v << " (want laplacian, smoothing or stitch)"
-                          << std::endl;
-                return 2;
-            }
-            setenv("PF_FUSION", v.c_str(), 1);  // read by MergeDepthMaps / MergeDisparityMaps
-        }
-        else if (k == "--ext") ext = v;
-        else if (k == "--width") width = std::atoi(v.c_str());
-        else if (k == "--device") device = std::atoi(v.c_str());
-        else if (k == "--metrics-order") {
-            if (v != "tree" && v != "sequential") {
-                std::cout << "bad --metrics-order " << v << " (want tree or sequential)" << std::endl;
-                return 2;
-            }
-            setenv("PF_METRICS_ORDER", v.c_str(), 1);  // read when the facade's context is made
-        }
-        else if (k == "--tile-model") {
-            if (v != "depth" && v != "disparity") {
-                std::cout << "bad --tile-model " << v << " (want depth or disparity)" << std::endl;
-                return 2;
-            }
-            setenv("PF_TILE_MODEL", v.c_str(), 1);  // read by pf_create_depth_panoramas
-        }
-        else if (k == "--layout") {
-            if (!take_layout(v)) return 2;
-        }
-        else if (k == "--shard") {  // R/N: one process per GPU over the sorted folder
-            if (std::sscanf(v.c_str(), "%d/%d", &shard, &nshards) != 2 || nshards < 1 ||
-                shard < 0 || shard >= nshards) {
-                std::cout << "bad --shard " << v << " (want R/N, 0 <= R < N)" << std::endl;
-                return 2;
-            }
-        }
-        else {
-            std::cout << "unknown option " << k << std::endl;
-            return 2;
-        }
-    }
-    {  // the self-check compares the Jacobi result with its targets: only the fusion has them
-        const char* ck = std::getenv("PF_CHECK_LAPLACIAN");
-        const char* fu = std::getenv("PF_FUSION");
-        if (ck && std::string(ck) == "1" && fu && *fu && std::string(fu) != "laplacian") {
-            std::cout << "--check-laplacian needs --fusion laplacian (got " << fu << ")"
-                      << std::endl;
-            return 2;
-        }
-    }
-    if (hipSetDevice(device) != hipSuccess) {
-        std::cout << "no HIP device " << device << std::endl;
-        return 1;
-    }
-    return pf_create_depth_panoramas(argv[2], argv[3], argv[4], argv[5], tiles, ext, width, shard,
-                                     nshards);
+    if (cmd == "lap") return lap_command(argc, argv);
+    if (cmd == "cmp") return cmp_command(argc, argv);
+    if (cmd == "0") return mode0_command(argc, argv);
+    return 0;  // Main.cpp:889-893: other commands do nothing
 }
