@@ -1,8 +1,8 @@
 /*
  * pf_oracle.c -- CPU restatement of the reference's fusion path.  TEST INFRASTRUCTURE ONLY:
- * see the header comment of pf_oracle.h ("parity unpinned": the reference is not buildable in
- * this image and ships no golden vectors; this file is the checker the HIP path is tested
- * against, never part of the product).
+ * see the header comment of pf_oracle.h (this file is the checker the HIP path is tested
+ * against, never part of the product; tests/golden/fusion_ref.npz pins it to the compiled
+ * reference).
  *
  * Citations are to /root/reference (Depth.cpp, Main.cpp, ilmbase22/include/ImathVec.h).
  * Compile with -O2 -ffp-contract=off: every float expression below is evaluated in the
@@ -578,6 +578,15 @@ int pfo_solve_depth_all(const float* emap, int ew, int eh, int ec, const pfo_til
     for (int level = 0; level < max_level; level++) {
         pfo_level_dims(out_w, out_h, zr0, zr1, level, &L);
         if (L.h0 < 1 || L.h1 > L.h - 2 || L.h0 >= L.h1) return PFO_EBAND;
+    }
+    /* Every level is exactly twice the one before it: the upsample reads prev[(y/2)*(w/2) + x/2]
+     * (Depth.cpp:1469-1478), which runs past the previous level's rows where it is not (4100x200:
+     * levels 512/1025/2050/4100, and the reference reads x/2 = 512 of a 512-wide row). */
+    for (int level = 1; level < max_level; level++) {
+        pfo_level P;
+        pfo_level_dims(out_w, out_h, zr0, zr1, level - 1, &P);
+        pfo_level_dims(out_w, out_h, zr0, zr1, level, &L);
+        if (L.w != 2 * P.w || L.h != 2 * P.h) return PFO_ELEVELS;
     }
     float* prev = NULL;
     long long oops_all = 0;

@@ -4,14 +4,20 @@
  * TEST INFRASTRUCTURE ONLY.  Nothing in the product library links, loads or calls this code;
  * only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use it, as the checker.
  *
- * PARITY STATUS: "parity unpinned" against the reference's own outputs.  The reference path
- * (Depth.cpp) cannot be built in this image without stand-ins (it includes <windows.h>, links
- * OpenCV's Windows libraries and needs a CMake-built Ceres with a generated config.h), and the
- * reference ships no tests, fixtures or golden vectors for this path.
- * This file is a line-by-line restatement of the reference arithmetic (every function cites the
- * Depth.cpp / ImathVec.h lines it follows); it is pinned only by the structural facts the survey
- * measured on the compiled reference (level bands, seam widths, out-of-tile tap counts), which
- * tests/test_oracle.py checks.
+ * PARITY STATUS: pinned to the compiled reference on the registration, fusion, smoothing and
+ * ErrorData path.  This file is a line-by-line restatement of the reference arithmetic (every
+ * function cites the Depth.cpp / ImathVec.h lines it follows).  The reference ships no tests or
+ * golden vectors, but its unmodified Depth.cpp builds with two shim headers and the vendored
+ * Ceres 1.13, and tests/golden/fusion_ref.npz (tools/make_fusion_golden.py) records what its own
+ * SolveDepthToDepth (per tile and joint), Depth2DepthTransform, SolveDepthAll,
+ * SolveDepthBySmoothing and ErrorData return.  tests/test_fusion_ref.py holds this oracle to the
+ * record: transformed tiles, panoramas and metrics in every bit, coefficients in every bit on
+ * well-conditioned tiles and within 1e-5 relative on ill-conditioned ones (DESIGN.md section 4
+ * has the measured distances).  The global fit, the stitch, ErrorCompare, ErrorLaplacian and
+ * the codecs have goldens of their own.  Not pinned: the E->P warps (the reference renders them
+ * with OpenGL), ErrorEmap outside what ErrorCompare reaches, and the disparity fit (the
+ * reference declares SolveDisparityToDepth without defining it).  tests/test_oracle.py checks
+ * the structural facts the survey measured (level bands, seam widths, out-of-tile tap counts).
  *
  * Numeric contract: fp32 for projection and fusion with no FMA
  * contraction (compile with -ffp-contract=off), fp64 where the reference promotes through the
@@ -145,8 +151,12 @@ void pfo_jacobi(float* buf, float* tmp, const float* Lnorm, const pfo_level* L, 
 void pfo_quantize(const float* buf, int n, uint16_t* out);
 /* SolveDepthAll (Depth.cpp:1416-1771).  Returns 0 or a negative error: -1 from pfo_targets, or
  * PFO_EBAND, before any buffer is touched, for a level with h0 < 1, h1 > h - 2 or h0 >= h1 (the
- * reference reads and writes outside its buffers there). */
+ * reference reads and writes outside its buffers there), or PFO_ELEVELS, also before any buffer,
+ * for a size whose levels are not each exactly twice the one before (502x251: 125/251/502;
+ * 4100x200: 512/1025/2050/4100 -- the reference's upsample reads past the previous level's rows
+ * there; the library refuses the same sizes in prepare_levels). */
 #define PFO_EBAND (-3)
+#define PFO_ELEVELS (-4)
 int  pfo_solve_depth_all(const float* emap, int ew, int eh, int ec, const pfo_tile* tiles,
                          int ntiles, const float* tile_data, int out_w, int out_h, float zr0,
                          float zr1, uint16_t* out, long long* oops);

@@ -6,8 +6,9 @@
  * linear_solver_type = DENSE_SCHUR).
  *
  * TEST INFRASTRUCTURE ONLY (see pf_oracle.h).  Ceres is a third-party dependency vendored in the
- * reference (ceres-solver/, VERSION 1.13.0, commit 19333b0f); it is built with CMake and is
- * therefore not buildable here, so its published algorithm is restated from its sources:
+ * reference (ceres-solver/, VERSION 1.13.0, commit 19333b0f); the oracle does not link it: its
+ * published algorithm is restated from its sources, and tests/golden/fusion_ref.npz and
+ * global_ref.npz hold the restatement to the real solver's results:
  *
  *  - options: include/ceres/solver.h:62-128 (max_num_iterations 50, initial radius 1e4, max
  *    radius 1e16, min radius 1e-32, min_relative_decrease 1e-3, min/max LM diagonal 1e-6/1e32,

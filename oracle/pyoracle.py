@@ -1,7 +1,7 @@
 """ctypes binding of the CPU oracle (oracle/liboracle.so).
 
 TEST INFRASTRUCTURE ONLY -- imported by tests/, __graft_entry__.smoke() and bench.py's
-cpu_baseline leg, never by the product path.  Parity unpinned (see pf_oracle.h).
+cpu_baseline leg, never by the product path.  Parity status: see pf_oracle.h.
 """
 import ctypes as C
 import os
@@ -201,6 +201,7 @@ def quantize(buf):
 
 
 EBAND = -3  # PFO_EBAND: a level's band touches a pole row or has no interior
+ELEVELS = -4  # PFO_ELEVELS: a level is not exactly twice the one before it
 
 
 def solve_depth_all(emap, tiles, tile_data, out_w, zr, out_h=None):
@@ -215,6 +216,9 @@ def solve_depth_all(emap, tiles, tile_data, out_w, zr, out_h=None):
     if rc == EBAND:
         raise ValueError(f"pfo_solve_depth_all rc={rc}: {out_w}x{out_h} has a level whose band "
                          "is not inside rows [1, h-2]")
+    if rc == ELEVELS:
+        raise ValueError(f"pfo_solve_depth_all rc={rc}: {out_w}x{out_h} has a level that is not "
+                         "exactly twice the one before it")
     if rc != 0:
         raise ValueError(f"pfo_solve_depth_all rc={rc}")
     return out.reshape(out_h, out_w), oops.value

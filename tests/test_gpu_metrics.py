@@ -14,8 +14,9 @@ Two summation orders (pf_set_metrics_order):
   1e-2 relative of the oracle's fp32 sequential sums (measured 1.1e-3 drift on mselog at C2; the
   a-priori bound n*u is 7e-2) and within 1e-5 of an fp64 numpy sum of the same fp32 terms; the
   least-squares {s, o} pinned to an fp64 solve (1e-4).
-Oracle parity against the reference is unpinned (pf_oracle.h): the reference ships no metric
-fixtures.
+The oracle's ErrorData is held to the compiled reference's in every bit by
+tests/test_fusion_ref.py (tests/golden/fusion_ref.npz), its ErrorEmap through ErrorCompare by
+tests/test_compare_ref.py; ErrorEmap outside what ErrorCompare reaches is not pinned.
 """
 import math
 

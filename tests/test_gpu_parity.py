@@ -4,7 +4,8 @@ Bars: bit-exact for everything -- tile index maps, level s
 targets, Jacobi buffers, registration coefficients, the u16 output, and the E->P warps (depth
 tiles and RGB tiles: their coordinate maps are built on the host with glibc atan2f / atan2, as
 the reference and the oracle call them, so the warped tiles are array_equal to the oracle's).
-Oracle parity against the reference itself is unpinned (pf_oracle.h).
+The oracle itself is held to the compiled reference by tests/test_fusion_ref.py (registration,
+fusion, smoothing, ErrorData); the E->P warps are not: the reference renders them with OpenGL.
 """
 import numpy as np
 import pytest

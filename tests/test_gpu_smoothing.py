@@ -1,8 +1,9 @@
 """SolveDepthBySmoothing (Depth.cpp:1773-1878) on the GPU against the oracle.
 
 pf_solve_smoothing reproduces the reference's lexicographic in-place Gauss-Seidel with a
-wavefront schedule (pf_smooth.hip); bar: bit-exact u16 output.  Parity against the reference
-itself is unpinned (pf_oracle.h), as for every path here.
+wavefront schedule (pf_smooth.hip); bar: bit-exact u16 output.  The oracle's smoothing equals the
+compiled reference's at 256x128 and 200x100 (tests/test_fusion_ref.py), and so does the library's
+(tests/test_gpu_fusion_ref.py).
 """
 import numpy as np
 import pytest

@@ -1,7 +1,7 @@
 """CPU checks of the metrics oracle (ErrorData/ErrorEmap restatement, Depth.cpp:1980-2458)
 against an independent numpy statement of the same definitions: medians are the element at
 index n//2 of the sorted compare values, counts are exact, the means agree to fp32 summation
-rounding.  (Parity with the reference itself is unpinned: it ships no metric fixtures.)"""
+rounding.  (Parity with the compiled reference's ErrorData: tests/test_fusion_ref.py.)"""
 import numpy as np
 import pytest
 
