@@ -662,7 +662,9 @@ static inline int wrap_signed(int d, int n)
 
 // Footprint of a patch of nrow rows: per panorama row v (unwrapped from the patch's first
 // corner) the x-range [xlo, xhi] of the corners that read it (pixels whose y0 is v or v-1, with
-// their x0 and x0 + 1), rounded out to 16-B units of the u8 RGB row.  Returns the unit count.
+// their x0 and x0 + 1), rounded out to 16-B units of the u8 RGB row.  Returns the unit count,
+// also left in F.units: INT32_MAX when the footprint cannot be staged (more than ph / 2 rows, or
+// a row wider than pw / 2).
 static inline long long floor_div16(long long x) { return x >= 0 ? x / 16 : -((15 - x) / 16); }
 
 struct RgbFoot {
@@ -682,6 +684,7 @@ static int rgb_footprint(const RgbTap* taps, int w, int X0, int X1, int Y0, int 
         }
     F.vmin = vmin;
     F.nv = vmax - vmin + 2;
+    F.units = INT32_MAX;  // until the footprint is known to be stageable
     if (F.nv > ph / 2) return INT32_MAX;
     F.xlo.assign(F.nv, INT32_MAX);
     F.xhi.assign(F.nv, INT32_MIN);
@@ -698,16 +701,23 @@ static int rgb_footprint(const RgbTap* taps, int w, int X0, int X1, int Y0, int 
     F.u0.resize(F.nv);
     F.nu.resize(F.nv);
     F.off.resize(F.nv);
-    F.units = 0;
+    int units = 0;
     for (int r = 0; r < F.nv; r++) {
+        if (F.xlo[r] > F.xhi[r]) {  // a row no corner reads (the tile's rows are more than two
+            F.u0[r] = 0;            // panorama rows apart): no units, no arithmetic on the
+            F.nu[r] = 0;            // untouched INT32_MAX / INT32_MIN bounds
+            F.off[r] = units;
+            continue;
+        }
         if (F.xhi[r] - F.xlo[r] + 1 > pw / 2) return INT32_MAX;
         const long long b0 = 3LL * (rx + F.xlo[r]), b1 = 3LL * (rx + F.xhi[r]) + 3;  // unwrapped
         const long long q0 = floor_div16(b0), q1 = floor_div16(b1 + 15);
         F.u0[r] = (int)q0;
         F.nu[r] = (int)(q1 - q0);
-        F.off[r] = F.units;
-        F.units += F.nu[r];
+        F.off[r] = units;
+        units += F.nu[r];
     }
+    F.units = units;
     return F.units;
 }
 
