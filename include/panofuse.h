@@ -80,6 +80,45 @@ int pf_set_tiles(pf_ctx* ctx, const pf_window* fovs, const pf_window* ranges, in
 #define PF_SOLVER_LM 1
 int pf_set_solver(pf_ctx* ctx, int solver);
 
+/* Tile-pixel validity rule (an extension: the reference reads every tile pixel as depth).  Real
+ * tiles hold NaN / Inf from a depth net, holes and sky masks written as 0, letter-box bars, or
+ * pixels a caller masked with NaN; read as depth, one such pixel spoils the whole band.
+ *   PF_VALID_ALL (default)  every pixel is read, as the reference does: every entry point
+ *                           launches the kernels and returns the bits it always did;
+ *   PF_VALID_RANGE          a raw tile value v (channel 0, before any transform) is valid iff
+ *                           lo < v && v < hi, compared in fp32; NaN fails both.  Needs lo < hi.
+ * lo = -INFINITY, hi = +INFINITY rejects exactly NaN and +-Inf (an arbitrary mask is expressed by
+ * writing NaN); lo = 0 also rejects holes written as 0; hi = 1 rejects saturated pixels.
+ * Under PF_VALID_RANGE:
+ *   pf_register, pf_register_joint, pf_merge's registration: a sample whose raw tile value is
+ *     invalid or whose baseline value is not finite is skipped (it adds nothing to the moment
+ *     sums).  A problem left with fewer than degree + 1 samples, or whose solution is not finite,
+ *     gets four quiet NaNs as coefficients (fp32 and fp64).  apply != 0 transforms the valid
+ *     pixels and writes NaN into the invalid ones, which so stay invalid under any later lo / hi.
+ *   pf_fuse, pf_merge, pf_fuse_targets, pf_fuse_check (and pf_fuse_level on their targets): tile
+ *     p contributes to a pixel of a panorama iff all five taps of its stencil are valid -- the
+ *     raw value passes the rule and, with coeffs, the transformed value is finite, so a tile with
+ *     NaN coefficients drops out.  The covering tiles are counted per pixel and panorama; a pixel
+ *     left with none is un-windowed: it keeps its seed / upsampled value and is a boundary for
+ *     its neighbours.  Coverage then depends on the data, so the levels run the marker-reading
+ *     Jacobi passes, not the packed form or the resident kernel.  The baseline emap
+ *     must be finite where the fusion seeds from it: documented, not checked.
+ *   pf_stitch: a pixel takes the first tile whose box holds it and whose sampled value is valid
+ *     (as a tap above); 0 if there is none.
+ *   They return PF_ESTATE, never silently ignoring the rule: pf_register_disparity,
+ *     pf_merge_disparity, pf_solve_smoothing, and the sharded pieces that derive coverage from the
+ *     layout alone: pf_fuse_partial, pf_fuse_partial_rows, pf_fuse_coverage_rows,
+ *     pf_fuse_multicover, pf_fuse_multicover_patch. */
+#define PF_VALID_ALL 0
+#define PF_VALID_RANGE 1
+int pf_set_tile_validity(pf_ctx* ctx, int mode, float lo, float hi);
+
+/* Valid counts under the context's rule: counts [batch][ntiles][2] (DEVICE, long long) =
+ * {registration samples pf_register keeps, valid pixels} per panorama and tile; with
+ * PF_VALID_ALL the totals.  Stream-ordered. */
+int pf_tile_valid_counts(pf_ctx* ctx, const float* tiles, const float* emap, int ew, int eh,
+                         int ec, int batch, float zr0, float zr1, long long* counts);
+
 /* SolveDepthToDepth (Depth.cpp:1261-1414) for every tile with only that tile active
  * (MergeDepthMaps' loop, Depth.cpp:794-805), fp64 least squares of degree `degree`
  * (3 = the reference's FunctorDepth2Depth3, with the context's solver; 1 = scale/shift);

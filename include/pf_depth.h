@@ -44,6 +44,14 @@
  * active path; smoothing and stitch run on the registered tiles), PF_SAVE_STITCH=1 also writes
  * <out>.pmap.png (:859), PF_CHECK_LAPLACIAN=1 prints "[SolveDepthAll] check Laplacian err:<err>"
  * (:1757) after the fusion and is refused with any other PF_FUSION.
+ * SetTileValidity (an extension too) sets the tile-pixel validity rule of the library
+ * (pf_set_tile_validity, include/panofuse.h): SolveDepthToDepth, SolveDepthAll, MergeDepthMaps,
+ * StitchDepthMaps and CheckLaplacian then skip the tile pixels outside (lo, hi);
+ * SolveDisparityToDepth, MergeDisparityMaps and SolveDepthBySmoothing fail with the library's
+ * message while it is on.  MergeDepthMaps also reads PF_TILE_VALID=LO:HI (panofuse_main
+ * --tile-valid; "-inf" / "inf" allowed, a malformed value is an error), which holds for that call,
+ * and under the rule prints "[mask] tile <i>: <n> of <N> pixels invalid, <m> of <M> samples" per
+ * tile that has invalid pixels.
  *
  * Not provided: a SolveDisparityToDepth over several active maps (a joint nonlinear solve), the
  * triangulation/subdivision members (vertices, faces, subd_*: never used on the path).
@@ -303,6 +311,12 @@ bool SolveDepthAll(EquirectangularMap& emap, std::vector<PerspectiveMap>& pmaps,
 // grid, 500 Gauss-Seidel smoothing iterations near the tile-box edges), on the GPU, bit-exact.
 bool SolveDepthBySmoothing(std::vector<PerspectiveMap>& pmaps, unsigned short* data,
                            int& out_width, int& out_height, Vec2f& zenith_range);
+/* EXTENSION (not in the reference, which reads every tile pixel as depth): the tile-pixel
+ * validity rule of every later call of this facade, process-wide.  on: a raw tile value v
+ * (channel 0) counts only if lo < v && v < hi in fp32 -- NaN never does; lo = -INFINITY,
+ * hi = INFINITY rejects exactly NaN and +-Inf, lo = 0 also holes written as 0.  off (the default):
+ * every pixel is read.  false (and a message) for on with !(lo < hi). */
+bool SetTileValidity(bool on, float lo, float hi);
 /* EXTENSION (in the reference an `if (false)` block of MergeDepthMaps, Depth.cpp:817-865): the
  * direct stitch of the tiles as they are into data (width * height u16) -- every pixel takes the
  * first map whose range box contains it, no fusion -- on the GPU (pf_stitch), bit-exact. */

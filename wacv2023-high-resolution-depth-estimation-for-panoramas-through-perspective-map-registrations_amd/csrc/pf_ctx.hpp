@@ -64,6 +64,8 @@ struct pf_ctx {
     int ntiles = 0, tile_c = 1;
     int solver = PF_SOLVER_LM;  // degree-3 registration solver (pf_set_solver)
     int metrics_order = PF_METRICS_TREE;  // pf_set_metrics_order
+    // tile-pixel validity rule (pf_set_tile_validity); valid.on == 0: every pixel is read
+    pf::TileValid valid{0, 0.0f, 0.0f};
     std::vector<pf_window> fov, rng;
     std::vector<int> tw_h, th_h;
     bool layout_ok = false;  // the stored layout was set completely
@@ -255,6 +257,21 @@ inline int check_emap(pf_ctx* c, const float* emap, int ew, int eh, int ec)
         return fail(c, PF_EINVAL, "emap %dx%dx%d too large", ew, eh, ec);
     return PF_OK;
 }
+
+// The entry points that cannot honour the tile-pixel validity rule refuse to run under it.
+inline int check_unmasked(pf_ctx* c, const char* entry)
+{
+    if (c && c->valid.on)
+        return fail(c, PF_ESTATE,
+                    "%s does not honour the tile validity rule: call pf_set_tile_validity(ctx, "
+                    "PF_VALID_ALL, 0, 0) first",
+                    entry);
+    return PF_OK;
+}
+
+// Whether level l may take the coverage shortcuts (the packed Jacobi form, the resident kernel):
+// it holds the separable-coverage certificate and coverage does not depend on the data.
+inline bool level_full(const pf_ctx* c, int l) { return c->lc.full[l] && !c->valid.on; }
 
 inline int check_tile_range(pf_ctx* c, int t0, int t1)
 {

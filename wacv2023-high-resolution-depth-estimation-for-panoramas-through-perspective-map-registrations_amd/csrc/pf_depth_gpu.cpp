@@ -12,7 +12,25 @@
 
 namespace pff __attribute__((visibility("hidden"))) {
 
+static std::mutex g_rule_mu;
+static TileRule g_rule{false, 0.0f, 0.0f};
+
+TileRule tile_rule()
+{
+    std::lock_guard<std::mutex> lk(g_rule_mu);
+    return g_rule;
+}
+
+static pf_ctx* device_ctx();
+
 pf_ctx* facade_ctx()
+{
+    pf_ctx* c = device_ctx();
+    if (c) apply_rule(c, tile_rule());  // a checked rule (SetTileValidity): cannot fail
+    return c;
+}
+
+static pf_ctx* device_ctx()
 {
     static std::mutex mu;
     static std::map<int, pf_ctx*> ctxs;
@@ -179,6 +197,18 @@ bool solve(EquirectangularMap& emap, const std::vector<PerspectiveMap*>& pm, con
 }  // namespace
 
 namespace DepthNamespace {
+
+bool SetTileValidity(bool on, float lo, float hi)
+{  // EXTENSION: pf_set_tile_validity for every later facade call
+    if (on && !(lo < hi)) {
+        std::cout << "[SetTileValidity] needs lo < hi (got " << lo << ", " << hi << ")"
+                  << std::endl;
+        return false;
+    }
+    std::lock_guard<std::mutex> lk(pff::g_rule_mu);
+    pff::g_rule = pff::TileRule{on, on ? lo : 0.0f, on ? hi : 0.0f};
+    return true;
+}
 
 // ---- the four map members that run on the GPU ----
 void EquirectangularMap::CopyInvalidPixels(EquirectangularMap& ref)  // Depth.cpp:703-725

@@ -6,6 +6,7 @@
 // file writes stay on the host (they are file formats), every per-pixel computation of the path
 // (registration, transform, fusion, quantisation, metrics) is a libpanofuse HIP kernel.
 #include "pf_facade.hpp"
+#include "pf_valid.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -26,6 +27,9 @@ using namespace pff;
 struct MergeSwitches {
     enum { LAPLACIAN, SMOOTHING, STITCH } fusion = LAPLACIAN;
     bool save_stitch = false, check_laplacian = false, global_align = false;
+    // PF_TILE_VALID=LO:HI (panofuse_main --tile-valid): the tile-pixel validity rule of this
+    // call; without it the rule is SetTileValidity's
+    TileRule rule{false, 0.0f, 0.0f};
 };
 
 bool read_merge_switches(MergeSwitches& s)
@@ -42,6 +46,15 @@ bool read_merge_switches(MergeSwitches& s)
                       << " (want laplacian, smoothing or stitch)" << std::endl;
             return false;
         }
+    }
+    s.rule = tile_rule();
+    if (const char* tv = std::getenv("PF_TILE_VALID")) {
+        std::string err;
+        if (!pfv::parse_range(tv, s.rule.lo, s.rule.hi, err)) {
+            std::cout << "[MergeDepthMaps] PF_TILE_VALID: " << err << std::endl;
+            return false;
+        }
+        s.rule.on = true;
     }
     s.save_stitch = env_on("PF_SAVE_STITCH");
     s.check_laplacian = env_on("PF_CHECK_LAPLACIAN");
@@ -146,6 +159,34 @@ bool fuse(const Job& j, const MergeSwitches& s)
     }
 }
 
+// Under the validity rule: one "[mask] tile <i>: ..." line per tile that has invalid pixels, from
+// pf_tile_valid_counts under the rule and, for the totals, without it.
+bool print_mask_lines(const Job& j, int ntiles, const TileRule& rule)
+{
+    const EquirectangularMap& e = j.emap;
+    const size_t n = (size_t)ntiles * 2;
+    DevMem dv(sizeof(long long) * n), dt(sizeof(long long) * n);
+    std::vector<long long> valid(n), total(n);
+    const auto counts = [&](DevMem& d) {
+        return pf_tile_valid_counts(j.c, j.d_tiles, j.d_emap, e.width, e.height, e.channels, 1,
+                                    j.zr[0], j.zr[1], d.as<long long>());
+    };
+    if (!dv.ok || !dt.ok || !pf_ok(j.c, counts(dv), "pf_tile_valid_counts")) return false;
+    pf_set_tile_validity(j.c, PF_VALID_ALL, 0.0f, 0.0f);
+    const int rc = counts(dt);
+    apply_rule(j.c, rule);
+    if (!call_sync(j.c, rc, "pf_tile_valid_counts") || !download(valid.data(), dv, n) ||
+        !download(total.data(), dt, n))
+        return false;
+    std::vector<std::string> lines;
+    if (!pfv::mask_lines(valid.data(), total.data(), ntiles, lines)) {
+        std::cout << "[MergeDepthMaps] inconsistent validity counts" << std::endl;
+        return false;
+    }
+    for (const std::string& ln : lines) std::cout << ln << std::endl;
+    return true;
+}
+
 // Depth.cpp:1738-1758: the last level's number, in the reference's words.
 bool print_laplacian_check(const Job& j)
 {
@@ -240,6 +281,16 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
     const auto t_begin = std::chrono::steady_clock::now();
     MergeSwitches sw;
     if (!read_merge_switches(sw)) return false;
+    // the entry points that cannot honour the validity rule: refused before any file is read
+    if (sw.rule.on && (disparity_tiles || sw.fusion == MergeSwitches::SMOOTHING)) {
+        std::cout << "[MergeDepthMaps] "
+                  << (disparity_tiles ? "pf_register_disparity" : "pf_solve_smoothing")
+                  << " does not honour the tile validity rule (pf_set_tile_validity): unset "
+                     "PF_TILE_VALID / SetTileValidity(false, 0, 0), or use depth tiles with "
+                     "PF_FUSION=laplacian or stitch"
+                  << std::endl;
+        return false;
+    }
     EquirectangularMap emap, gt;
     std::vector<PerspectiveMap> pmaps;
     // the ground truth decodes on a host thread while the tiles load and the GPU fuses
@@ -258,6 +309,12 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
 
     pf_ctx* c = facade_ctx();
     if (!c) return false;
+    // this call's rule (PF_TILE_VALID over SetTileValidity's); the stored one comes back at exit
+    struct RuleScope {
+        pf_ctx* c;
+        ~RuleScope() { apply_rule(c, tile_rule()); }
+    } rule_scope{c};
+    if (!pf_ok(c, apply_rule(c, sw.rule), "pf_set_tile_validity")) return false;
     DevMem dt = tiles_on_device(c, pmaps);
     if (!dt.ok) return false;
     DevMem de = on_device(emap), dc(sizeof(float) * 4 * pmaps.size()), dout(no * 2);
@@ -266,6 +323,7 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
                 disparity_tiles ? nullptr : dc.as<float>(), dout.as<uint16_t>(), out_width,
                 out_height, zr};
 
+    if (sw.rule.on && !print_mask_lines(j, (int)pmaps.size(), sw.rule)) return false;
     auto t = std::chrono::steady_clock::now();
     if (!register_tiles(j, dc.as<float>(), disparity_tiles)) return false;
     if (time_Reg) *time_Reg = elapsed_ms(t);

@@ -12,6 +12,7 @@ int pf_register_disparity(pf_ctx* c, const float* emap, int ew, int eh, int ec, 
 {
     int rc;
     if ((rc = check_common(c, batch))) return rc;
+    if ((rc = check_unmasked(c, "pf_register_disparity"))) return rc;
     if ((rc = check_emap(c, emap, ew, eh, ec))) return rc;
     if (!tiles) return fail(c, PF_EINVAL, "tiles is NULL");
     if ((rc = prepare_registration(c, zr0, zr1))) return rc;
@@ -57,6 +58,7 @@ int pf_merge_disparity(pf_ctx* c, const float* emap, int ew, int eh, int ec, con
 {
     int rc;
     if ((rc = check_common(c, batch))) return rc;
+    if ((rc = check_unmasked(c, "pf_merge_disparity"))) return rc;
     if ((rc = check_emap(c, emap, ew, eh, ec))) return rc;
     if (!tiles || !out) return fail(c, PF_EINVAL, "tiles/out is NULL");
     const size_t bytes = sizeof(float) * (size_t)c->tile_elems * batch;

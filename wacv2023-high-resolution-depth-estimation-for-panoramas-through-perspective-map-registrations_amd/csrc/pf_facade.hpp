@@ -23,6 +23,18 @@ using DepthNamespace::PerspectiveMap;
 // re-entrant; so is this facade per device).  PF_METRICS_ORDER is read here, once per context.
 pf_ctx* facade_ctx();
 
+// The tile-pixel validity rule of the facade (SetTileValidity): process-wide, and put on the
+// context every time facade_ctx() hands it out, so every entry point starts from it.
+struct TileRule {
+    bool on;
+    float lo, hi;
+};
+TileRule tile_rule();
+inline int apply_rule(pf_ctx* c, const TileRule& r)
+{
+    return pf_set_tile_validity(c, r.on ? PF_VALID_RANGE : PF_VALID_ALL, r.lo, r.hi);
+}
+
 inline bool hip_ok(hipError_t e, const char* what)
 {
     if (e == hipSuccess) return true;

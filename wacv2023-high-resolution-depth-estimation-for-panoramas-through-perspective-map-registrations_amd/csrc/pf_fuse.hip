@@ -226,7 +226,8 @@ static int fuse_range(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
         }
         StageTimer t(c, PF_STAGE_TARGETS, bytes, 1);
         launch_targets_multi(c->stream, (const TileGeom*)c->geom.p, c->ntiles, tiles,
-                             c->tile_elems, coeffs, M, (const int2*)lc.tgt_order.p, batch);
+                             c->tile_elems, coeffs, M, (const int2*)lc.tgt_order.p, batch,
+                             c->valid);
     }
     for (int l = 0; l < lc.nlevels; l++) {
         const LevelDims& L = lc.dims[l];
@@ -279,7 +280,7 @@ static int fuse_range(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
                 int rc;
                 if ((rc = seed_tables(c, L, ew, eh, ec))) return rc;
             }
-            const JresPlan jp = jres_plan(c, L, batch, lc.full[l]);
+            const JresPlan jp = jres_plan(c, L, batch, level_full(c, l));
             if (jp.on) {  // outside the timed stage too (first allocation synchronises)
                 int rc;
                 if ((rc = jres_prepare(c, L, batch, jp))) return rc;
@@ -296,7 +297,7 @@ static int fuse_range(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
                 r.lnorm = lnorm_l; r.a = a; r.b = b;
                 r.out = last ? out : nullptr; r.ostride = plane;
                 r.batch = batch;
-                r.hcol = lc.full[l] ? (const float*)lc.hcol[l].p : nullptr;
+                r.hcol = level_full(c, l) ? (const float*)lc.hcol[l].p : nullptr;
                 r.jp = &jp;
                 res = run_jacobi(c, L, r, &passes);
                 t.set_launches(passes);  // k_jlag launches (rocprof's count for that kernel)
@@ -358,10 +359,11 @@ int pf_register(pf_ctx* c, const float* emap, int ew, int eh, int ec, float* til
         launch_register(c->stream, (const TileGeom*)c->geom.p, (const RegGrid*)c->reg.p,
                         (const GridCol*)c->rcols.p, (const GridRow*)c->rrows.p, c->ntiles, emap,
                         ew, eh, ec, (long long)ew * eh * ec, tiles, c->tile_elems, degree,
-                        c->solver, cf, coeffs64, batch, nullptr, nullptr, sidx);
+                        c->solver, cf, coeffs64, batch, nullptr, nullptr, sidx, c->valid);
         if (apply)
             launch_apply_cubic(c->stream, (const TileGeom*)c->geom.p, c->ntiles,
-                               c->tile_elems / c->tile_c, tiles, c->tile_elems, cf, batch);
+                               c->tile_elems / c->tile_c, tiles, c->tile_elems, cf, batch,
+                               c->valid);
     }
     HIPCHK(c, hipGetLastError());
     return PF_OK;
@@ -426,9 +428,41 @@ int pf_register_joint(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
                     (const GridCol*)c->rcols.p, (const GridRow*)c->rrows.p, c->ntiles, emap, ew,
                     eh, ec, (long long)ew * eh * ec, tiles, c->tile_elems, degree, c->solver,
                     nullptr, nullptr, batch, (double*)c->reg_sums.p,
-                    (const int*)c->reg_active.p, reg_sample_index(c, ew, eh, ec));
+                    (const int*)c->reg_active.p, reg_sample_index(c, ew, eh, ec), c->valid);
     launch_register_joint(c->stream, (const double*)c->reg_sums.p, (const int*)c->reg_active.p,
-                          c->ntiles, batch, degree, c->solver, cf, coeffs64);
+                          c->ntiles, batch, degree, c->solver, cf, coeffs64, c->valid.on != 0);
+    HIPCHK(c, hipGetLastError());
+    return PF_OK;
+}
+
+int pf_set_tile_validity(pf_ctx* c, int mode, float lo, float hi)
+{
+    if (!c) return PF_EINVAL;
+    if (mode != PF_VALID_ALL && mode != PF_VALID_RANGE)
+        return fail(c, PF_EINVAL, "pf_set_tile_validity: unknown mode %d", mode);
+    if (mode == PF_VALID_RANGE && !(lo < hi))
+        return fail(c, PF_EINVAL, "pf_set_tile_validity: needs lo < hi (got %g, %g)", (double)lo,
+                    (double)hi);
+    c->valid.on = mode == PF_VALID_RANGE ? 1 : 0;
+    c->valid.lo = c->valid.on ? lo : 0.0f;
+    c->valid.hi = c->valid.on ? hi : 0.0f;
+    return PF_OK;
+}
+
+int pf_tile_valid_counts(pf_ctx* c, const float* tiles, const float* emap, int ew, int eh, int ec,
+                         int batch, float zr0, float zr1, long long* counts)
+{
+    int rc;
+    if ((rc = check_common(c, batch))) return rc;
+    if ((rc = check_emap(c, emap, ew, eh, ec))) return rc;
+    if (!tiles || !counts) return fail(c, PF_EINVAL, "tiles/counts is NULL");
+    if ((rc = prepare_registration(c, zr0, zr1))) return rc;
+    if ((rc = check_reg_grids(c, nullptr))) return rc;
+    const int2* sidx = reg_sample_index(c, ew, eh, ec);
+    if (!sidx) return fail(c, PF_ENOMEM, "pf_tile_valid_counts: no registration sample index");
+    launch_valid_counts(c->stream, (const TileGeom*)c->geom.p, (const RegGrid*)c->reg.p, c->ntiles,
+                        emap, (long long)ew * eh * ec, tiles, c->tile_elems, sidx, c->valid,
+                        counts, batch);
     HIPCHK(c, hipGetLastError());
     return PF_OK;
 }

@@ -118,6 +118,15 @@ struct LevelDims {
     int w, h, h0, h1, iters, nlevels;
 };
 
+// The tile-pixel validity rule (pf_set_tile_validity).  on == 0: every pixel is read (the
+// launchers then take the kernels they always took); else a raw tile value v is valid iff
+// lo < v && v < hi in fp32, which NaN fails on both sides.
+struct TileValid {
+    int on;
+    float lo, hi;
+};
+__host__ __device__ inline bool tile_ok(float v, float lo, float hi) { return lo < v && v < hi; }
+
 // ------------------------------------------------------------------------------------------
 // Imath Vec3<float> arithmetic in source order (ImathVec.h:1467-1486, 1631-1700).
 __host__ __device__ inline float dot3(const float* a, const float* b)
@@ -269,7 +278,7 @@ void launch_targets_patch(hipStream_t s, const TileGeom* geom, const TileBox* bo
                           const TapBox* tb, int ntiles, const int32_t* map, const float* tiles,
                           long long tstride, const float* coeffs, LevelDims L, float* lnorm,
                           long long lstride, int batch, const uint32_t* tmask = nullptr,
-                          int nmw = 0);
+                          int nmw = 0, TileValid tv = TileValid{0, 0.0f, 0.0f});
 // All levels' targets in one launch (pf_targets.hip): per level its tables and plane, and a host
 // table of (level, patch) entries in gather order (fuse_range builds it once per level set).
 struct TgtLevel {
@@ -292,7 +301,7 @@ int targets_patch_h();
 int targets_batch();
 void launch_targets_multi(hipStream_t s, const TileGeom* geom, int ntiles, const float* tiles,
                           long long tstride, const float* coeffs, const TgtMulti& M,
-                          const int2* order, int batch);
+                          const int2* order, int batch, TileValid tv = TileValid{0, 0.0f, 0.0f});
 bool jstream_supported_T(int T);
 int jstream_waves_per_cu(int T, bool fast);
 void launch_jstream(hipStream_t s, const JacobiPass& P, int T, int batch, bool fast);
@@ -340,17 +349,25 @@ void launch_register(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
                      int ew, int eh, int ec, long long estride, const float* tiles,
                      long long tstride, int degree, int solver, float* coeffs, double* coeffs64,
                      int batch, double* sums = nullptr, const int* active = nullptr,
-                     const int2* sidx = nullptr);
+                     const int2* sidx = nullptr, TileValid tv = TileValid{0, 0.0f, 0.0f});
 // the registration samples' tile-element and baseline indices (layout- and baseline-size-only),
 // built once per (layout, zenith range, baseline size) so k_register only gathers
 void launch_regidx(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
                    const GridCol* rcols, const GridRow* rrows, int ntiles, int max_samples,
                    int ew, int eh, int ec, int2* sidx);
 int register_sums_per_tile();
+// guard: the masked rule's NaN coefficients (too few samples, a non-finite solution)
 void launch_register_joint(hipStream_t s, const double* sums, const int* active, int ntiles,
-                           int batch, int degree, int solver, float* coeffs, double* coeffs64);
+                           int batch, int degree, int solver, float* coeffs, double* coeffs64,
+                           bool guard = false);
 void launch_apply_cubic(hipStream_t s, const TileGeom* geom, int ntiles, long long tile_elems,
-                        float* tiles, long long tstride, const float* coeffs, int batch);
+                        float* tiles, long long tstride, const float* coeffs, int batch,
+                        TileValid tv = TileValid{0, 0.0f, 0.0f});
+// pf_tile_valid_counts: per (panorama, tile) {valid registration samples, valid pixels}
+void launch_valid_counts(hipStream_t s, const TileGeom* geom, const RegGrid* grids, int ntiles,
+                         const float* emap, long long estride, const float* tiles,
+                         long long tstride, const int2* sidx, TileValid tv, long long* counts,
+                         int batch);
 // Disparity-tile registration (pf_disp.hip): the LM fit of y = 1/(a x + b) + d per (panorama,
 // tile) on the samples of sidx (launch_regidx), abcd = (a, b, 1, d); summary (optional):
 // [batch][ntiles] x {initial cost, final cost, iterations, termination code}.
@@ -452,6 +469,11 @@ void launch_stitch_map(hipStream_t s, const TileGeom* geom, const SmoothBox* box
 void launch_stitch(hipStream_t s, const TileGeom* geom, int ntiles, const int2* src,
                    const float* tiles, long long tstride, const float* coeffs, int w, int h,
                    uint16_t* out, int batch);
+// the stitch under the validity rule: the first covering tile whose sampled value is valid
+void launch_stitch_valid(hipStream_t s, const TileGeom* geom, const SmoothBox* box, int ntiles,
+                         const GridCol* cols, const GridRow* rows, const float* tiles,
+                         long long tstride, const float* coeffs, int w, int h, TileValid tv,
+                         uint16_t* out, int batch);
 // err[b] = the reference-order float chain over rows h0+1..h1-1, columns 1..w-2 of plane b
 void launch_lap_residual(hipStream_t s, const float* buf, const float* lnorm, int w, int h,
                          int h0, int h1, int batch, float* err);

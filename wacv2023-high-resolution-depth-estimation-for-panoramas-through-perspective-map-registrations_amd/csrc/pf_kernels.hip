@@ -525,15 +525,38 @@ __device__ void solve_store(const double* S, int degree, int solver, float* coef
     }
 }
 
-__global__ void __launch_bounds__(kRegLanes) k_register(
+// The masked rule's store (pf_set_tile_validity): four quiet NaNs for a problem with fewer than
+// degree + 1 valid samples (S[9] is their count) or with a non-finite solution.
+__device__ void solve_store_valid(const double* S, int degree, int solver, float* coeffs,
+                                  double* coeffs64, long long o)
+{
+    float c32[4];
+    double c64[4];
+    bool ok = S[9] >= (double)(degree + 1);
+    if (ok) {
+        solve_store(S, degree, solver, c32, c64, 0);
+        for (int i = 0; i < 4; i++) ok = ok && isfinite(c64[i]);
+    }
+    for (int i = 0; i < 4; i++) {
+        if (coeffs) coeffs[o + i] = ok ? c32[i] : __uint_as_float(0x7FC00000u);
+        if (coeffs64) coeffs64[o + i] = ok ? c64[i] : __longlong_as_double(0x7FF8000000000000LL);
+    }
+}
+
+// One block's registration of tile p of panorama b.  MASK (k_register_valid): a sample whose raw
+// tile value fails the rule, or whose baseline value is not finite, adds nothing to the sums; the
+// lane-to-sample assignment and the halving tree are the unmasked ones, so acc[9] is the count of
+// valid samples.  With MASK false this is k_register as it was.
+template <bool MASK>
+__device__ __forceinline__ void register_tile(
     const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids,
     const GridCol* __restrict__ rcols, const GridRow* __restrict__ rrows, int ntiles,
     const float* __restrict__ emap, int ew, int eh, int ec, long long estride,
     const float* __restrict__ tiles, long long tstride, int degree, int solver,
     float* __restrict__ coeffs, double* __restrict__ coeffs64, double* __restrict__ sums,
-    const int* __restrict__ active, const int2* __restrict__ sidx)
+    const int* __restrict__ active, const int2* __restrict__ sidx, float vlo, float vhi,
+    double (*part)[kRegLanes])
 {
-    __shared__ double part[kRegSums][kRegLanes];
     // one linear grid, XCD-contiguous: the tiles of one panorama run on one XCD, so its emap is
     // fetched into one L2 (the samples of neighbouring tiles overlap in the emap)
     const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
@@ -581,6 +604,8 @@ __global__ void __launch_bounds__(kRegLanes) k_register(
 #pragma unroll
         for (int u = 0; u < kRegU; u++) {
             if (s0 + u * kRegLanes >= ns) break;
+            if constexpr (MASK)
+                if (!(tile_ok(tv[u], vlo, vhi) && isfinite(ev[u]))) continue;
             double X = clamp_depth((double)tv[u]);
             double Yv = clamp_depth((double)ev[u]);
             double X2 = X * X, X3 = X * X * X;
@@ -608,15 +633,89 @@ __global__ void __launch_bounds__(kRegLanes) k_register(
             for (int k = 0; k < kRegSums; k++) sums[((long long)b * ntiles + p) * kRegSums + k] = S[k];
             return;
         }
-        solve_store(S, degree, solver, coeffs, coeffs64, ((long long)b * ntiles + p) * 4);
+        if constexpr (MASK)
+            solve_store_valid(S, degree, solver, coeffs, coeffs64, ((long long)b * ntiles + p) * 4);
+        else
+            solve_store(S, degree, solver, coeffs, coeffs64, ((long long)b * ntiles + p) * 4);
     }
+}
+
+__global__ void __launch_bounds__(kRegLanes) k_register(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids,
+    const GridCol* __restrict__ rcols, const GridRow* __restrict__ rrows, int ntiles,
+    const float* __restrict__ emap, int ew, int eh, int ec, long long estride,
+    const float* __restrict__ tiles, long long tstride, int degree, int solver,
+    float* __restrict__ coeffs, double* __restrict__ coeffs64, double* __restrict__ sums,
+    const int* __restrict__ active, const int2* __restrict__ sidx)
+{
+    __shared__ double part[kRegSums][kRegLanes];
+    register_tile<false>(geom, grids, rcols, rrows, ntiles, emap, ew, eh, ec, estride, tiles,
+                         tstride, degree, solver, coeffs, coeffs64, sums, active, sidx, 0.0f, 0.0f,
+                         part);
+}
+
+__global__ void __launch_bounds__(kRegLanes) k_register_valid(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids,
+    const GridCol* __restrict__ rcols, const GridRow* __restrict__ rrows, int ntiles,
+    const float* __restrict__ emap, int ew, int eh, int ec, long long estride,
+    const float* __restrict__ tiles, long long tstride, int degree, int solver,
+    float* __restrict__ coeffs, double* __restrict__ coeffs64, double* __restrict__ sums,
+    const int* __restrict__ active, const int2* __restrict__ sidx, float vlo, float vhi)
+{
+    __shared__ double part[kRegSums][kRegLanes];
+    register_tile<true>(geom, grids, rcols, rrows, ntiles, emap, ew, eh, ec, estride, tiles,
+                        tstride, degree, solver, coeffs, coeffs64, sums, active, sidx, vlo, vhi,
+                        part);
+}
+
+// pf_tile_valid_counts: block (p, b) counts the registration samples k_register_valid keeps and
+// the tile's pixels that pass the rule (every one with the rule off), as wave ballots summed
+// through LDS.
+__global__ void __launch_bounds__(256) k_valid_counts(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, const int2* __restrict__ sidx, TileValid tv, long long* __restrict__ counts)
+{
+    __shared__ long long part[4][2];
+    const int p = blockIdx.x % ntiles, b = blockIdx.x / ntiles, l = threadIdx.x;
+    const TileGeom g = geom[p];
+    const RegGrid rg = grids[p];
+    const float* tile = tiles + b * tstride + g.off;
+    const float* em = emap + b * estride;
+    const int ns = (rg.cols + 1) * (rg.rows + 1);
+    const int npx = g.w * g.h;
+    long long nsamp = 0, npix = 0;  // wave-uniform
+    for (int s0 = 0; s0 < ns; s0 += 256) {
+        const int s = s0 + l;
+        bool ok = s < ns;
+        if (ok && tv.on) {
+            const int2 ix = sidx[rg.soff + s];
+            ok = tile_ok(tile[ix.x], tv.lo, tv.hi) && isfinite(em[ix.y]);
+        }
+        nsamp += __popcll(__ballot(ok));
+    }
+    for (int i0 = 0; i0 < npx; i0 += 256) {
+        const int i = i0 + l;
+        bool ok = i < npx;
+        if (ok && tv.on) ok = tile_ok(tile[(long long)i * g.c], tv.lo, tv.hi);
+        npix += __popcll(__ballot(ok));
+    }
+    if ((l & 63) == 0) {
+        part[l >> 6][0] = nsamp;
+        part[l >> 6][1] = npix;
+    }
+    __syncthreads();
+    if (l < 2)
+        counts[((long long)b * ntiles + p) * 2 + l] =
+            part[0][l] + part[1][l] + part[2][l] + part[3][l];
 }
 
 // SolveDepthToDepth with several active maps (Depth.cpp:1274-1376: every active map's sample
 // grid feeds one problem): the active tiles' sums added in tile order, one solve per panorama.
 __global__ void k_register_joint(const double* __restrict__ sums, const int* __restrict__ active,
                                  int ntiles, int batch, int degree, int solver,
-                                 float* __restrict__ coeffs, double* __restrict__ coeffs64)
+                                 float* __restrict__ coeffs, double* __restrict__ coeffs64,
+                                 int guard)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
@@ -626,7 +725,8 @@ __global__ void k_register_joint(const double* __restrict__ sums, const int* __r
         if (active[p])
             for (int k = 0; k < kRegSums; k++)
                 S[k] = S[k] + sums[((long long)b * ntiles + p) * kRegSums + k];
-    solve_store(S, degree, solver, coeffs, coeffs64, (long long)b * 4);
+    if (guard) solve_store_valid(S, degree, solver, coeffs, coeffs64, (long long)b * 4);
+    else solve_store(S, degree, solver, coeffs, coeffs64, (long long)b * 4);
 }
 
 // Pixels covered by three or more tiles (pf_fuse_multicover, sharded fusion): the contribution
@@ -682,6 +782,28 @@ __global__ void __launch_bounds__(kBlock) k_apply_cubic(const TileGeom* __restri
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < npx;
          i += (long long)gridDim.x * kBlock)
         t[i * g.c] = cubic_map(t[i * g.c], abcd.x, abcd.y, abcd.z, abcd.w);
+}
+
+// The same under the validity rule: a valid pixel is transformed, an invalid one becomes a quiet
+// NaN (and so stays invalid under any later lo / hi).
+__global__ void __launch_bounds__(kBlock) k_apply_cubic_valid(const TileGeom* __restrict__ geom,
+                                                              int ntiles,
+                                                              float* __restrict__ tiles,
+                                                              long long tstride,
+                                                              const float* __restrict__ coeffs,
+                                                              float vlo, float vhi)
+{
+    const int p = blockIdx.y, b = blockIdx.z;
+    const TileGeom g = geom[p];
+    long long npx = (long long)g.w * g.h;
+    const float4 abcd = *reinterpret_cast<const float4*>(coeffs + ((long long)b * ntiles + p) * 4);
+    float* t = tiles + b * tstride + g.off;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < npx;
+         i += (long long)gridDim.x * kBlock) {
+        const float v = t[i * g.c];
+        t[i * g.c] = tile_ok(v, vlo, vhi) ? cubic_map(v, abcd.x, abcd.y, abcd.z, abcd.w)
+                                          : __uint_as_float(0x7FC00000u);
+    }
 }
 
 // Depth2DepthTransform of one map (PerspectiveMap::Depth2DepthTransform, Depth.cpp:245-274),
@@ -831,12 +953,26 @@ void launch_register(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
                      const GridCol* rcols, const GridRow* rrows, int ntiles, const float* emap,
                      int ew, int eh, int ec, long long estride, const float* tiles,
                      long long tstride, int degree, int solver, float* coeffs, double* coeffs64,
-                     int batch, double* sums, const int* active, const int2* sidx)
+                     int batch, double* sums, const int* active, const int2* sidx, TileValid tv)
 {
     dim3 grid((unsigned)(ntiles * batch));
-    hipLaunchKernelGGL(k_register, grid, dim3(kRegLanes), 0, s, geom, grids, rcols, rrows,
-                       ntiles, emap, ew, eh, ec, estride, tiles, tstride, degree, solver, coeffs,
-                       coeffs64, sums, active, sidx);
+    if (tv.on)
+        hipLaunchKernelGGL(k_register_valid, grid, dim3(kRegLanes), 0, s, geom, grids, rcols,
+                           rrows, ntiles, emap, ew, eh, ec, estride, tiles, tstride, degree,
+                           solver, coeffs, coeffs64, sums, active, sidx, tv.lo, tv.hi);
+    else
+        hipLaunchKernelGGL(k_register, grid, dim3(kRegLanes), 0, s, geom, grids, rcols, rrows,
+                           ntiles, emap, ew, eh, ec, estride, tiles, tstride, degree, solver,
+                           coeffs, coeffs64, sums, active, sidx);
+}
+
+void launch_valid_counts(hipStream_t s, const TileGeom* geom, const RegGrid* grids, int ntiles,
+                         const float* emap, long long estride, const float* tiles,
+                         long long tstride, const int2* sidx, TileValid tv, long long* counts,
+                         int batch)
+{
+    hipLaunchKernelGGL(k_valid_counts, dim3((unsigned)(ntiles * batch)), dim3(256), 0, s, geom,
+                       grids, ntiles, emap, estride, tiles, tstride, sidx, tv, counts);
 }
 
 // One thread per registration sample: the tile element (SphericalTo2D, clamp, Value's index) and
@@ -929,22 +1065,28 @@ void launch_global_solve(hipStream_t s, const double* partials, int nchunks, int
 }
 
 void launch_register_joint(hipStream_t s, const double* sums, const int* active, int ntiles,
-                           int batch, int degree, int solver, float* coeffs, double* coeffs64)
+                           int batch, int degree, int solver, float* coeffs, double* coeffs64,
+                           bool guard)
 {
     hipLaunchKernelGGL(k_register_joint, dim3((batch + 63) / 64), dim3(64), 0, s, sums, active,
-                       ntiles, batch, degree, solver, coeffs, coeffs64);
+                       ntiles, batch, degree, solver, coeffs, coeffs64, guard ? 1 : 0);
 }
 
 void launch_apply_cubic(hipStream_t s, const TileGeom* geom, int ntiles, long long tile_elems,
-                        float* tiles, long long tstride, const float* coeffs, int batch)
+                        float* tiles, long long tstride, const float* coeffs, int batch,
+                        TileValid tv)
 {
     long long per = tile_elems / (ntiles > 0 ? ntiles : 1);
     unsigned gx = nblocks(per);
     if (gx > 1024) gx = 1024;
     if (gx == 0) gx = 1;
     dim3 grid(gx, ntiles, batch);
-    hipLaunchKernelGGL(k_apply_cubic, grid, dim3(kBlock), 0, s, geom, ntiles, tiles, tstride,
-                       coeffs);
+    if (tv.on)
+        hipLaunchKernelGGL(k_apply_cubic_valid, grid, dim3(kBlock), 0, s, geom, ntiles, tiles,
+                           tstride, coeffs, tv.lo, tv.hi);
+    else
+        hipLaunchKernelGGL(k_apply_cubic, grid, dim3(kBlock), 0, s, geom, ntiles, tiles, tstride,
+                           coeffs);
 }
 
 void launch_d2d_map(hipStream_t s, float* data, long long npx, int c, const float* abcd)

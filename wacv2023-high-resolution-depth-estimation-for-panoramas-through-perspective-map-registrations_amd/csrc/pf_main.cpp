@@ -4,6 +4,7 @@
 //                 [--metrics-order tree|sequential] [--edge-metrics]
 //                 [--tile-model depth|disparity] [--global-align] [--layout NAME|FILE]
 //                 [--fusion laplacian|smoothing|stitch] [--save-stitch] [--check-laplacian]
+//                 [--tile-valid LO:HI]
 //   panofuse_main export <rgb_dir> <tile_dir> [--device D] [--layout NAME|FILE]
 //   panofuse_main layout NAME|FILE [--width W] [--tile-size WxH] [--device D]
 //   panofuse_main lap <gt_file> <given_file> [--device D]
@@ -57,7 +58,15 @@
 // registered tiles (the reference's debug file, Depth.cpp:859).
 // --check-laplacian (opt-in, takes no value, only with --fusion laplacian): print SolveDepthAll's
 // self-check "[SolveDepthAll] check Laplacian err:<err>" (Depth.cpp:1738-1758) per panorama.
+// --tile-valid LO:HI (opt-in): the tile-pixel validity rule (pf_set_tile_validity).  A tile pixel
+// is read as depth only if LO < v < HI, v being the file's value after it is scaled to 0..1; LO
+// and HI are floats, "-inf" and "inf" included (0:inf skips black bars and holes written as 0,
+// 0:1 saturated pixels as well).  Registration, fusion and stitch skip the others, and the run
+// prints "[mask] tile <i>: <n> of <N> pixels invalid, <m> of <M> samples" per tile that has any.
+// Not with --tile-model disparity or --fusion smoothing.  Carried in PF_TILE_VALID.  (The usage
+// text of the bare command is pinned by the tests and does not list it.)
 #include "pf_facade.hpp"  // the inline to_window and load_pair; it includes the two public headers
+#include "pf_valid.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -328,6 +337,12 @@ static int mode0_command(int argc, char* argv[])
         else if (k == "--width") width = std::atoi(v.c_str());
         else if (k == "--device") device = std::atoi(v.c_str());
         else if (k == "--layout") return take_layout(v);
+        else if (k == "--tile-valid") {
+            float lo, hi;
+            std::string err;
+            if (!pfv::parse_range(v.c_str(), lo, hi, err)) return bad(k, v, "LO:HI, LO < HI");
+            setenv("PF_TILE_VALID", v.c_str(), 1);  // read by MergeDepthMaps
+        }
         else if (k == "--shard") {  // R/N: one process per GPU over the sorted folder
             if (std::sscanf(v.c_str(), "%d/%d", &shard, &nshards) != 2 || nshards < 1 ||
                 shard < 0 || shard >= nshards)

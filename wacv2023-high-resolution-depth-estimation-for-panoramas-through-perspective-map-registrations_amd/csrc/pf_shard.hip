@@ -11,7 +11,7 @@ using namespace pf;
 // The level's packed-form certificate (LevelCache::hcol), or nullptr where it has none.
 static const float* level_hcol(const pf_ctx* c, int level)
 {
-    return c->lc.full[level] ? (const float*)c->lc.hcol[level].p : nullptr;
+    return level_full(c, level) ? (const float*)c->lc.hcol[level].p : nullptr;
 }
 
 // The sweeps' result `res` back into `buf`: its band rows (the other rows of the two are equal).
@@ -63,6 +63,7 @@ int pf_fuse_partial(pf_ctx* c, const float* tiles, const float* coeffs, int t0, 
     int rc;
     const LevelDims* L = nullptr;
     if ((rc = check_common(c, 1))) return rc;
+    if ((rc = check_unmasked(c, "pf_fuse_partial"))) return rc;
     if (!tiles || !lsum || !cnt) return fail(c, PF_EINVAL, "NULL buffer");
     if ((rc = check_tile_range(c, t0, t1))) return rc;
     if ((rc = level_at(c, out_w, out_h, zr0, zr1, level, &L))) return rc;
@@ -77,6 +78,7 @@ int pf_fuse_partial_rows(pf_ctx* c, const float* tiles, const float* coeffs, int
 {
     int rc;
     const LevelDims* L = nullptr;
+    if ((rc = check_unmasked(c, "pf_fuse_partial_rows"))) return rc;
     if ((rc = level_rows(c, out_w, out_h, zr0, zr1, level, row0, row1, &L))) return rc;
     if (!tiles || !lsum || !cnt) return fail(c, PF_EINVAL, "NULL buffer");
     if ((rc = check_tile_range(c, t0, t1))) return rc;
@@ -89,6 +91,7 @@ int pf_fuse_coverage_rows(pf_ctx* c, int out_w, int out_h, float zr0, float zr1,
 {
     int rc;
     const LevelDims* L = nullptr;
+    if ((rc = check_unmasked(c, "pf_fuse_coverage_rows"))) return rc;
     if ((rc = level_rows(c, out_w, out_h, zr0, zr1, level, row0, row1, &L))) return rc;
     if (!cnt) return fail(c, PF_EINVAL, "NULL buffer");
     launch_coverage_rows(c->stream, (const TileBox*)c->lc.box[level].p, c->ntiles, *L, cnt, row0,
@@ -246,7 +249,7 @@ int pf_fuse_targets(pf_ctx* c, const float* tiles, const float* coeffs, int out_
                          (const TapBox*)lc.tapbox[level].p, c->ntiles,
                          (const int32_t*)lc.tapmap[level].p, tiles, c->tile_elems, coeffs, *L,
                          lnorm, (long long)L->w * L->h, 1, (const uint32_t*)lc.tmask[level].p,
-                         (c->ntiles + 31) / 32);
+                         (c->ntiles + 31) / 32, c->valid);
     HIPCHK(c, hipGetLastError());
     return PF_OK;
 }
@@ -294,7 +297,7 @@ int pf_fuse_level(pf_ctx* c, const float* emap, int ew, int eh, int ec, const fl
         return PF_OK;
     }
     if (level == 0 && (rc = seed_tables(c, L, ew, eh, ec))) return rc;
-    const JresPlan jp = jres_plan(c, L, 1, lc.full[level]);
+    const JresPlan jp = jres_plan(c, L, 1, level_full(c, level));
     if (jp.on && (rc = jres_prepare(c, L, 1, jp))) return rc;
     // the rows outside the band, in both planes (the u16 rows too on the last level)
     launch_border(c->stream, level == 0 ? nullptr : prev, 0, L, buf, other, st, o, st, 1);
@@ -336,6 +339,7 @@ int pf_fuse_multicover(pf_ctx* c, const float* tiles, const float* coeffs, int t
     int rc;
     const LevelDims* L = nullptr;
     if ((rc = check_common(c, 1))) return rc;
+    if ((rc = check_unmasked(c, "pf_fuse_multicover"))) return rc;
     if ((rc = level_at(c, out_w, out_h, zr0, zr1, level, &L))) return rc;
     const LevelCache& lc = c->lc;
     if (npairs) *npairs = lc.nmc[level];
@@ -355,6 +359,7 @@ int pf_fuse_multicover_patch(pf_ctx* c, int out_w, int out_h, float zr0, float z
     int rc;
     const LevelDims* L = nullptr;
     if ((rc = check_common(c, 1))) return rc;
+    if ((rc = check_unmasked(c, "pf_fuse_multicover_patch"))) return rc;
     if ((rc = level_at(c, out_w, out_h, zr0, zr1, level, &L))) return rc;
     const LevelCache& lc = c->lc;
     if (lc.nmc[level] == 0) return PF_OK;
@@ -396,7 +401,7 @@ int pf_fuse_band_plan(pf_ctx* c, int out_w, int out_h, float zr0, float zr1, int
         return fail(c, PF_EINVAL, "level %d: the zenith band leaves no room for band passes", level);
     const int band = L->h1 - L->h0 + 1;
     // the sweep depths depend only on (level, nbands): every rank derives the same plan
-    std::vector<PassPlan> plan = plan_level(c, *L, jacobi_tcap(*L), 1, c->lc.full[level],
+    std::vector<PassPlan> plan = plan_level(c, *L, jacobi_tcap(*L), 1, level_full(c, level),
                                             (band + nbands - 1) / nbands);
     if ((int)plan.size() > cap) return fail(c, PF_EINVAL, "plan of %zu passes > cap %d", plan.size(), cap);
     for (size_t i = 0; i < plan.size(); i++) T[i] = plan[i].T;
@@ -424,7 +429,7 @@ int pf_fuse_band_pass(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
         return fail(c, PF_EINVAL, "pass depth %d not available at level %d", T, level);
     if (row0 < L.h0 || row1 > L.h1 + 1 || row0 >= row1)
         return fail(c, PF_EINVAL, "rows [%d,%d) outside the band [%d,%d]", row0, row1, L.h0, L.h1);
-    const bool fast = lc.full[level];
+    const bool fast = level_full(c, level);
     if (src_mode == 2 && (rc = seed_tables(c, L, ew, eh, ec))) return rc;
     JacobiRun r{};
     r.first = src_mode;

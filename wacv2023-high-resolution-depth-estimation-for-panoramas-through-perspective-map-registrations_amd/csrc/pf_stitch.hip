@@ -94,6 +94,56 @@ __global__ void __launch_bounds__(256) k_stitch(const TileGeom* __restrict__ geo
     else if (has1) o[i1] = (uint16_t)q1;
 }
 
+// The stitch under the validity rule (pf_set_tile_validity): which tile a pixel takes depends on
+// the data, so the cached first-tile map does not apply.  A pixel walks the tiles in ascending
+// order and takes the first whose box holds it and whose sampled value is valid (its raw value
+// passes the rule and, with coefficients, its transformed value is finite); 0 if there is none.
+// The box test, the projection and the clamp are k_stitch_map's, the quantiser k_stitch's.
+__global__ void __launch_bounds__(256) k_stitch_valid(const TileGeom* __restrict__ geom,
+                                                      const SmoothBox* __restrict__ box,
+                                                      int ntiles,
+                                                      const GridCol* __restrict__ cols,
+                                                      const GridRow* __restrict__ rows, int w,
+                                                      int npx, const float* __restrict__ tiles,
+                                                      long long tstride,
+                                                      const float* __restrict__ coeffs, float vlo,
+                                                      float vhi, uint16_t* __restrict__ out)
+{
+    const int b = blockIdx.y;
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (i >= npx) return;
+    const int Y = i / w, X = i - Y * w;
+    const float* const t = tiles + (long long)b * tstride;
+    const GridCol c = cols[X + 1];
+    const GridRow r = rows[Y + 1];
+    uint16_t q = 0;
+    for (int p = 0; p < ntiles; p++) {
+        const SmoothBox bx = box[p];
+        if (!(X >= min(bx.x0, bx.x1) && X <= max(bx.x0, bx.x1) && Y >= bx.y0 && Y <= bx.y1))
+            continue;
+        const TileGeom& g = geom[p];
+        float x, y;
+        sph_to_2d(g, r.sz, r.cz, c.ca, c.sa, x, y);
+        long long idx = tile_index(g, x, y);
+        const long long lim = (long long)g.w * g.h * g.c;
+        if (idx < 0) idx = 0;
+        if (idx >= lim) idx = lim - g.c;
+        const float raw = t[g.off + idx];
+        float v = raw;
+        if (coeffs) {
+            const float4 k =
+                *reinterpret_cast<const float4*>(coeffs + ((long long)b * ntiles + p) * 4);
+            v = cubic_map(v, k.x, k.y, k.z, k.w);
+        }
+        if (!(tile_ok(raw, vlo, vhi) && isfinite(v))) continue;
+        if (v < 0) v = 0;
+        if (v > 1) v = 1;
+        q = (uint16_t)(v * 65535.0f);
+        break;
+    }
+    out[(long long)b * npx + i] = q;
+}
+
 __device__ __forceinline__ float lap_sq_step(float acc, float v)
 {  // err += pow(d, 2) (Depth.cpp:1754): sq_step of pf_metrics.hip
     const double t = (double)v;
@@ -156,6 +206,17 @@ void launch_stitch(hipStream_t s, const TileGeom* geom, int ntiles, const int2* 
     const int lanes = n / 2 + 1;  // pairs, plus the pixel an odd plane offset leaves alone
     hipLaunchKernelGGL(k_stitch, dim3((unsigned)((lanes + 255) / 256), batch), dim3(256), 0, s,
                        geom, ntiles, src, n, tiles, tstride, coeffs, out);
+}
+
+void launch_stitch_valid(hipStream_t s, const TileGeom* geom, const SmoothBox* box, int ntiles,
+                         const GridCol* cols, const GridRow* rows, const float* tiles,
+                         long long tstride, const float* coeffs, int w, int h, TileValid tv,
+                         uint16_t* out, int batch)
+{
+    const int n = w * h;
+    hipLaunchKernelGGL(k_stitch_valid, dim3((unsigned)((n + 255) / 256), batch), dim3(256), 0, s,
+                       geom, box, ntiles, cols, rows, w, n, tiles, tstride, coeffs, tv.lo, tv.hi,
+                       out);
 }
 
 void launch_lap_residual(hipStream_t s, const float* buf, const float* lnorm, int w, int h,

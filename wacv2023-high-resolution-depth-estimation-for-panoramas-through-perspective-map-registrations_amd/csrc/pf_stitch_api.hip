@@ -47,8 +47,13 @@ int pf_stitch(pf_ctx* c, const float* tiles, const float* coeffs, int batch, int
         c->st_key[0] = out_w;
         c->st_key[1] = out_h;
     }
-    launch_stitch(c->stream, (const TileGeom*)c->geom.p, c->ntiles, (const int2*)c->st_src.p,
-                  tiles, c->tile_elems, coeffs, out_w, out_h, out, batch);
+    if (c->valid.on)  // the first VALID tile depends on the data: the tables, not the cached map
+        launch_stitch_valid(c->stream, (const TileGeom*)c->geom.p, (const SmoothBox*)c->st_box.p,
+                            c->ntiles, (const GridCol*)c->st_cols.p, (const GridRow*)c->st_rows.p,
+                            tiles, c->tile_elems, coeffs, out_w, out_h, c->valid, out, batch);
+    else
+        launch_stitch(c->stream, (const TileGeom*)c->geom.p, c->ntiles, (const int2*)c->st_src.p,
+                      tiles, c->tile_elems, coeffs, out_w, out_h, out, batch);
     HIPCHK(c, hipGetLastError());
     return PF_OK;
 }

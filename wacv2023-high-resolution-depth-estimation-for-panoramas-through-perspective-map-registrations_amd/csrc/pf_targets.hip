@@ -154,7 +154,14 @@ static constexpr int kTGW = kTPW + 2, kTGH = kTPH + 2, kTG = kTGW * kTGH;  // gr
 static constexpr int kTNB = 8;
 
 // One block's work: patch `pid` of level L for panoramas [bgrp*NB, +NB).
-template <bool XFORM, int NB>
+//
+// MASK (pf_set_tile_validity, the *_valid kernels): an invalid tap -- its raw value fails the
+// rule, or its transformed value is not finite -- is staged as NaN, and tile p contributes to a
+// pixel of panorama q iff its five-point sum is not NaN, i.e. iff all five taps are valid (finite
+// taps cannot sum to NaN: the partial sums may overflow to one infinity, never to both).  Coverage
+// then depends on the data, so the count n is kept per panorama; the order of the tiles and the
+// normalisation are the unmasked ones.  With MASK false this is the code it always was.
+template <bool XFORM, int NB, bool MASK = false>
 __device__ __forceinline__ void targets_patch(const TileGeom* __restrict__ geom,
                                               const TileBox* __restrict__ box,
                                               const TapBox* __restrict__ tb, int ntiles,
@@ -164,7 +171,8 @@ __device__ __forceinline__ void targets_patch(const TileGeom* __restrict__ geom,
                                               int npx, int pid, int bgrp,
                                               float* __restrict__ lnorm, long long lstride,
                                               int batch, float (*sv)[kTG],
-                                              const uint32_t* __restrict__ tmask, int nmw)
+                                              const uint32_t* __restrict__ tmask, int nmw,
+                                              float vlo = 0.0f, float vhi = 0.0f)
 {
     const int X0 = (pid % npx) * kTPW, Y0 = L.h0 + (pid / npx) * kTPH;
     const int t = threadIdx.x;
@@ -172,11 +180,16 @@ __device__ __forceinline__ void targets_patch(const TileGeom* __restrict__ geom,
     const int bbeg = bgrp * NB;
     float acc[kTPP][NB];
     int n[kTPP];
+    int nq[kTPP][MASK ? NB : 1];  // MASK: the covering tiles per panorama
 #pragma unroll
     for (int j = 0; j < kTPP; j++) {
         n[j] = 0;
 #pragma unroll
         for (int q = 0; q < NB; q++) acc[j][q] = 0.0f;
+        if constexpr (MASK) {
+#pragma unroll
+            for (int q = 0; q < NB; q++) nq[j][q] = 0;
+        }
     }
     const int X1 = min(X0 + kTPW - 1, L.w - 1), Y1 = min(Y0 + kTPH - 1, L.h1);
     // one tile's contribution to the patch (tiles come in index order: the reference's
@@ -208,6 +221,8 @@ __device__ __forceinline__ void targets_patch(const TileGeom* __restrict__ geom,
             for (int q = 0; q < NB; q++) {
                 float x = v[q];
                 if constexpr (XFORM) x = cubic_map(x, k[q].x, k[q].y, k[q].z, k[q].w);
+                if constexpr (MASK)
+                    if (!(tile_ok(v[q], vlo, vhi) && isfinite(x))) x = __uint_as_float(0x7FC00000u);
                 sv[q][g] = x;
             }
         }
@@ -227,7 +242,14 @@ __device__ __forceinline__ void targets_patch(const TileGeom* __restrict__ geom,
                     Lp += sv[q][c] * 1.0f;
                     Lp += sv[q][c + kTGW] * -0.25f;
                     Lp += sv[q][c + 1] * -0.25f;
-                    acc[j][q] += Lp;
+                    if constexpr (MASK) {
+                        if (Lp == Lp) {
+                            acc[j][q] += Lp;
+                            nq[j][q]++;
+                        }
+                    } else {
+                        acc[j][q] += Lp;
+                    }
                 }
                 n[j]++;
             }
@@ -264,7 +286,13 @@ __device__ __forceinline__ void targets_patch(const TileGeom* __restrict__ geom,
             const int b = bbeg + q;
             if (b >= batch) break;
             float out;
-            if (n[j] == 0) out = __uint_as_float(PF_NAN_MARKER);
+            if constexpr (MASK) {
+                // 1 / center with center = 1 + 1 + ... (nq times) = (float)nq exactly
+                const int m = nq[j][q];
+                if (m == 0) out = __uint_as_float(PF_NAN_MARKER);
+                else if (m == 1) out = acc[j][q];
+                else out = acc[j][q] * (1.0f / (float)m);
+            } else if (n[j] == 0) out = __uint_as_float(PF_NAN_MARKER);
             else if (n[j] == 1) out = acc[j][q];
             else out = acc[j][q] * scale;
             // nt: the planes' stores keep the tiles' lines in L2 for the neighbouring patches
@@ -321,17 +349,64 @@ __global__ void __launch_bounds__(256) k_targets_multi(const TileGeom* __restric
                              ent.y, bgrp, T.lnorm, T.lstride, batch, sv, T.tmask, T.nmw);
 }
 
+// The two gathers under the validity rule (MASK): the same blocks, tables and order.
+template <bool XFORM, int NB>
+__global__ void __launch_bounds__(256) k_targets_patch_valid(
+    const TileGeom* __restrict__ geom, const TileBox* __restrict__ box,
+    const TapBox* __restrict__ tb, int ntiles, const int32_t* __restrict__ map,
+    const float* __restrict__ tiles, long long tstride, const float* __restrict__ coeffs,
+    LevelDims L, int npx, int npatch, float* __restrict__ lnorm, long long lstride, int batch,
+    const uint32_t* __restrict__ tmask, int nmw, float vlo, float vhi)
+{
+    __shared__ float sv[NB][kTG];
+    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
+    const int pid = (int)(lb % (unsigned)npatch), bgrp = (int)(lb / (unsigned)npatch);
+    targets_patch<XFORM, NB, true>(geom, box, tb, ntiles, map, tiles, tstride, coeffs, L, npx, pid,
+                                   bgrp, lnorm, lstride, batch, sv, tmask, nmw, vlo, vhi);
+}
+
+template <bool XFORM, int NB>
+__global__ void __launch_bounds__(256) k_targets_multi_valid(
+    const TileGeom* __restrict__ geom, int ntiles, const float* __restrict__ tiles,
+    long long tstride, const float* __restrict__ coeffs, TgtMulti M,
+    const int2* __restrict__ order, int batch, float vlo, float vhi)
+{
+    __shared__ float sv[NB][kTG];
+    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
+    const int e = (int)(lb % (unsigned)M.nentries), bgrp = (int)(lb / (unsigned)M.nentries);
+    const int2 ent = order[e];  // (level, patch)
+    const TgtLevel& T = M.lv[ent.x];
+    targets_patch<XFORM, NB, true>(geom, T.box, T.tb, ntiles, T.map, tiles, tstride, coeffs, T.L,
+                                   T.npx, ent.y, bgrp, T.lnorm, T.lstride, batch, sv, T.tmask,
+                                   T.nmw, vlo, vhi);
+}
+
 int targets_patch_w() { return kTPW; }
 int targets_patch_h() { return kTPH; }
 int targets_batch() { return kTNB; }
 
 void launch_targets_multi(hipStream_t s, const TileGeom* geom, int ntiles, const float* tiles,
                           long long tstride, const float* coeffs, const TgtMulti& M,
-                          const int2* order, int batch)
+                          const int2* order, int batch, TileValid tv)
 {
     // one panorama (pf_merge, C2 / C5): blocks of one panorama, not kTNB copies of it
     const int nb = batch == 1 ? 1 : kTNB;
     const dim3 g((unsigned)((long long)M.nentries * ((batch + nb - 1) / nb)));
+    if (tv.on) {
+        if (nb == 1 && coeffs)
+            hipLaunchKernelGGL((k_targets_multi_valid<true, 1>), g, dim3(256), 0, s, geom, ntiles,
+                               tiles, tstride, coeffs, M, order, batch, tv.lo, tv.hi);
+        else if (nb == 1)
+            hipLaunchKernelGGL((k_targets_multi_valid<false, 1>), g, dim3(256), 0, s, geom, ntiles,
+                               tiles, tstride, coeffs, M, order, batch, tv.lo, tv.hi);
+        else if (coeffs)
+            hipLaunchKernelGGL((k_targets_multi_valid<true, kTNB>), g, dim3(256), 0, s, geom,
+                               ntiles, tiles, tstride, coeffs, M, order, batch, tv.lo, tv.hi);
+        else
+            hipLaunchKernelGGL((k_targets_multi_valid<false, kTNB>), g, dim3(256), 0, s, geom,
+                               ntiles, tiles, tstride, coeffs, M, order, batch, tv.lo, tv.hi);
+        return;
+    }
     if (nb == 1 && coeffs)
         hipLaunchKernelGGL((k_targets_multi<true, 1>), g, dim3(256), 0, s, geom, ntiles, tiles,
                            tstride, coeffs, M, order, batch);
@@ -349,13 +424,33 @@ void launch_targets_multi(hipStream_t s, const TileGeom* geom, int ntiles, const
 void launch_targets_patch(hipStream_t s, const TileGeom* geom, const TileBox* box,
                           const TapBox* tb, int ntiles, const int32_t* map, const float* tiles,
                           long long tstride, const float* coeffs, LevelDims L, float* lnorm,
-                          long long lstride, int batch, const uint32_t* tmask, int nmw)
+                          long long lstride, int batch, const uint32_t* tmask, int nmw,
+                          TileValid tv)
 {
     const int npx = (L.w + kTPW - 1) / kTPW;
     const int npy = (L.h1 - L.h0 + 1 + kTPH - 1) / kTPH;
     const int npatch = npx * npy;
     const int nb = batch == 1 ? 1 : kTNB;
     const dim3 g((unsigned)((long long)npatch * ((batch + nb - 1) / nb)));
+    if (tv.on) {
+        if (nb == 1 && coeffs)
+            hipLaunchKernelGGL((k_targets_patch_valid<true, 1>), g, dim3(256), 0, s, geom, box, tb,
+                               ntiles, map, tiles, tstride, coeffs, L, npx, npatch, lnorm, lstride,
+                               batch, tmask, nmw, tv.lo, tv.hi);
+        else if (nb == 1)
+            hipLaunchKernelGGL((k_targets_patch_valid<false, 1>), g, dim3(256), 0, s, geom, box,
+                               tb, ntiles, map, tiles, tstride, coeffs, L, npx, npatch, lnorm,
+                               lstride, batch, tmask, nmw, tv.lo, tv.hi);
+        else if (coeffs)
+            hipLaunchKernelGGL((k_targets_patch_valid<true, kTNB>), g, dim3(256), 0, s, geom, box,
+                               tb, ntiles, map, tiles, tstride, coeffs, L, npx, npatch, lnorm,
+                               lstride, batch, tmask, nmw, tv.lo, tv.hi);
+        else
+            hipLaunchKernelGGL((k_targets_patch_valid<false, kTNB>), g, dim3(256), 0, s, geom, box,
+                               tb, ntiles, map, tiles, tstride, coeffs, L, npx, npatch, lnorm,
+                               lstride, batch, tmask, nmw, tv.lo, tv.hi);
+        return;
+    }
     if (nb == 1 && coeffs)
         hipLaunchKernelGGL((k_targets_patch<true, 1>), g, dim3(256), 0, s, geom, box, tb, ntiles,
                            map, tiles, tstride, coeffs, L, npx, npatch, lnorm, lstride, batch,

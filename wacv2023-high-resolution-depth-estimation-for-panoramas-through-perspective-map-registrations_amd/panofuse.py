@@ -36,7 +36,8 @@ EXPORTS = [
     "pf_error_compare", "pf_disp_depth_convert", "pf_register_disparity",
     "pf_disparity_transform", "pf_merge_disparity", "pf_register_global",
     "pf_result_transform", "pf_median_scale", "pf_copy_invalid", "pf_layout_audit",
-    "pf_stitch", "pf_laplacian_residual", "pf_fuse_check",
+    "pf_stitch", "pf_laplacian_residual", "pf_fuse_check", "pf_set_tile_validity",
+    "pf_tile_valid_counts",
 ]
 NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
           "pf_debug_smooth_fault", "pf_fuse_partial_rows", "pf_fuse_coverage_rows",
@@ -44,6 +45,7 @@ NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
           "pf_fuse_targets", "pf_rows_add_batch", "pf_set_jacobi_share"}
 METRICS_ORDERS = {"tree": 0, "sequential": 1}  # PF_METRICS_*; "sequential" = the reference's
 SOLVERS = {"normal": 0, "lm": 1}  # PF_SOLVER_*; "lm" = the reference's Ceres LM (default)
+PF_VALID_ALL, PF_VALID_RANGE = 0, 1  # pf_set_tile_validity's modes
 
 STAGES = ["warp", "register", "seed", "targets", "jacobi", "quantize", "metrics"]
 
@@ -127,6 +129,8 @@ def load():
     L.pf_median_scale.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, ip, ip, vp, vp]
     L.pf_copy_invalid.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, ip, ip]
     L.pf_set_solver.argtypes = [vp, ip]
+    L.pf_set_tile_validity.argtypes = [vp, ip, fp, fp]
+    L.pf_tile_valid_counts.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, vp]
     L.pf_fuse_normalize.argtypes = [vp, vp, vp, ip, ip, fp, fp, ip, vp]
     L.pf_fuse_multicover.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, ip, vp,
                                      C.POINTER(C.c_int)]
@@ -265,6 +269,34 @@ class Fuser:
     def set_solver(self, solver):
         """Degree-3 registration solver: "lm" (the reference's Ceres LM, default) or "normal"."""
         self._check(self.L.pf_set_solver(self.h, SOLVERS[solver]))
+
+    def set_tile_validity(self, lo=None, hi=None):
+        """The tile-pixel validity rule (pf_set_tile_validity).  None, None: every pixel is read,
+        as the reference does (the default).  Otherwise a raw tile value v is valid iff
+        lo < v < hi in fp32 (NaN never is); a bound left None is infinite, so
+        set_tile_validity(float("-inf"), float("inf")) rejects exactly NaN and +-Inf and
+        set_tile_validity(lo=0.0) also rejects holes written as 0.  Registration, fusion and
+        stitch then skip invalid pixels; the entry points that cannot raise PF_ESTATE."""
+        if lo is None and hi is None:
+            self._check(self.L.pf_set_tile_validity(self.h, PF_VALID_ALL, 0.0, 0.0))
+            return
+        lo = float("-inf") if lo is None else float(lo)
+        hi = float("inf") if hi is None else float(hi)
+        self._check(self.L.pf_set_tile_validity(self.h, PF_VALID_RANGE, lo, hi))
+
+    def tile_valid_counts(self, emap, tiles, zr, counts=None):
+        """pf_tile_valid_counts: int64 [B, ntiles, 2] device tensor (made when None) of {valid
+        registration samples, valid pixels} per panorama and tile under the context's rule.
+        No sync."""
+        import torch
+        ew, eh, ec = _emap_dims(emap)
+        B = emap.shape[0]
+        if counts is None:
+            counts = torch.zeros((B, self.layout.ntiles, 2), dtype=torch.int64,
+                                 device=emap.device)
+        self._check(self.L.pf_tile_valid_counts(self.h, _ptr(tiles), _ptr(emap), ew, eh, ec, B,
+                                                float(zr[0]), float(zr[1]), _ptr(counts)))
+        return counts
 
     def register(self, emap, tiles, zr, degree=3, apply=True, coeffs=None, coeffs64=None):
         ew, eh, ec = _emap_dims(emap)
