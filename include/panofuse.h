@@ -176,6 +176,51 @@ int pf_disparity_transform(pf_ctx* ctx, float* data, long long npix, int channel
 int pf_merge_disparity(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, const float* tiles,
                        int batch, int out_w, float zr0, float zr1, float* coeffs, uint16_t* out);
 
+/* ---- robust registration (an extension: the reference passes NULL as the loss at both call
+ * sites, Depth.cpp:1232, 1393; a user of it writes new ceres::HuberLoss(a) there) ----
+ *
+ * The per-tile fits above are unweighted least squares, and one gross outlier (a depth edge, glass,
+ * sky, a mirror: finite, in range and wrong, so no validity rule removes it) bends the cubic.
+ * With a loss set, the tile registrations minimise sum 0.5 rho(r^2) by the same Ceres 1.13
+ * Levenberg-Marquardt, with Ceres' loss semantics (s = r^2 of the unscaled residual, b = a a):
+ *   PF_LOSS_HUBER  (loss_function.h:177, loss_function.cc:47-61)
+ *     s > b:  rho = 2 a sqrt(s) - b, rho' = max(DBL_MIN, a / sqrt(s));  else rho = s, rho' = 1
+ *   PF_LOSS_SOFTL1 (loss_function.h:193, loss_function.cc:63-70), c = 1 / b, t = sqrt(1 + s c)
+ *     rho = 2 b (t - 1), rho' = max(DBL_MIN, 1 / t)
+ * rho'' <= 0 for both, so Corrector (corrector.cc:81-85) scales the residual and the Jacobian row
+ * by sqrt(rho') and nothing else; the cost term is 0.5 rho (residual_block.cc:164-166).  The
+ * gradient, J'J, the Jacobi scaling, the model cost change and every tolerance are formed from
+ * the corrected quantities.  A loss cannot be carried by the 15 moment sums of the cubic, so the
+ * cubic runs sample-wise (k_register_robust, csrc/pf_robust.hip) in the fixed summation order of
+ * the disparity fit: reproducible bit for bit.  CauchyLoss, ArctanLoss, TolerantLoss
+ * and the others need log, atan2 or exp in fp64, whose device and glibc versions are not the same
+ * bits: out of scope.
+ *
+ * a must be finite and > 0 for a loss (PF_EINVAL otherwise) and is ignored for PF_LOSS_NONE.
+ * With PF_LOSS_NONE (the default, also after a loss was set and unset) every entry point launches
+ * the kernels and returns the bits it always did.  With a loss set:
+ *   pf_register, pf_register_ex, pf_merge   run the sample-wise kernel; they need degree == 3 and
+ *     PF_SOLVER_LM (PF_EINVAL otherwise).  The start is (1,1,1,1).  apply and the transform fused
+ *     into the fusion are unchanged.  Under PF_VALID_RANGE a sample whose raw tile value fails the
+ *     rule or whose baseline value is not finite is skipped; a problem left with fewer than 4
+ *     samples, or with a non-finite solution, gets four quiet NaNs and termination 5.
+ *   pf_register_disparity, pf_merge_disparity   fit their model under the loss; the summary of
+ *     pf_register_disparity then has the 6 entries of pf_register_ex's.
+ *   pf_register_joint, pf_register_global   return PF_ESTATE: the robust joint and global solves
+ *     are out of scope. */
+#define PF_LOSS_NONE 0 /* default */
+#define PF_LOSS_HUBER 1
+#define PF_LOSS_SOFTL1 2
+int pf_set_register_loss(pf_ctx* ctx, int kind, double a);
+
+/* pf_register with a per-tile solver summary (optional, DEVICE, [batch][ntiles][6] doubles):
+ * {initial cost, final cost, iterations, termination as pf_register_disparity's, samples used,
+ * inliers = samples with r^2 <= a^2 at the returned coefficients}.  summary is allowed only while
+ * a loss is set (PF_EINVAL otherwise); with summary == NULL this is pf_register. */
+int pf_register_ex(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, float* tiles,
+                   int batch, float zr0, float zr1, int degree, int apply, float* coeffs,
+                   double* coeffs64, double* summary);
+
 /* ---- post-fusion calibration (no tile layout needed; all pointers are device pointers) ----
  *
  * SolveDepthToDepth2 (Depth.cpp:1158-1259): one cubic per panorama from the fused u16 result

@@ -317,6 +317,17 @@ bool SolveDepthBySmoothing(std::vector<PerspectiveMap>& pmaps, unsigned short* d
  * hi = INFINITY rejects exactly NaN and +-Inf, lo = 0 also holes written as 0.  off (the default):
  * every pixel is read.  false (and a message) for on with !(lo < hi). */
 bool SetTileValidity(bool on, float lo, float hi);
+/* EXTENSION (the reference passes NULL as the loss, Depth.cpp:1232, 1393): the robust loss of the
+ * tile registrations of every later call of this facade, process-wide (pf_set_register_loss,
+ * include/panofuse.h): kind 0 none (the default), 1 Ceres' HuberLoss(a), 2 SoftLOneLoss(a), a
+ * finite and > 0.  Honoured by MergeDepthMaps, SolveDepthToDepth with one active map,
+ * MergeDisparityMaps and SolveDisparityToDepth; SolveDepthToDepth with several active maps and
+ * SolveDepthToDepth2 print the library's message and return false while it is set.
+ * MergeDepthMaps / MergeDisparityMaps also read PF_REG_LOSS=huber:A|softl1:A (panofuse_main
+ * --reg-loss), which holds for that call, and under a loss print per tile "[robust] tile <i>: <m>
+ * of <n> samples beyond a=<A>, cost <c0> -> <c1>, <it> iterations, <termination>".  false (and a
+ * message) for an unknown kind or a bad scale. */
+bool SetRegistrationLoss(int kind, double a);
 /* EXTENSION (in the reference an `if (false)` block of MergeDepthMaps, Depth.cpp:817-865): the
  * direct stitch of the tiles as they are into data (width * height u16) -- every pixel takes the
  * first map whose range box contains it, no fusion -- on the GPU (pf_stitch), bit-exact. */

@@ -66,6 +66,9 @@ struct pf_ctx {
     int metrics_order = PF_METRICS_TREE;  // pf_set_metrics_order
     // tile-pixel validity rule (pf_set_tile_validity); valid.on == 0: every pixel is read
     pf::TileValid valid{0, 0.0f, 0.0f};
+    // robust loss of the tile registrations (pf_set_register_loss); PF_LOSS_NONE: least squares
+    int loss_kind = PF_LOSS_NONE;
+    double loss_a = 0.0;
     std::vector<pf_window> fov, rng;
     std::vector<int> tw_h, th_h;
     bool layout_ok = false;  // the stored layout was set completely
@@ -265,6 +268,16 @@ inline int check_unmasked(pf_ctx* c, const char* entry)
         return fail(c, PF_ESTATE,
                     "%s does not honour the tile validity rule: call pf_set_tile_validity(ctx, "
                     "PF_VALID_ALL, 0, 0) first",
+                    entry);
+    return PF_OK;
+}
+
+// The entry points that have no robust form refuse to run while a loss is set.
+inline int check_no_loss(pf_ctx* c, const char* entry)
+{
+    if (c && c->loss_kind != PF_LOSS_NONE)
+        return fail(c, PF_ESTATE,
+                    "%s has no robust form: call pf_set_register_loss(ctx, PF_LOSS_NONE, 0) first",
                     entry);
     return PF_OK;
 }

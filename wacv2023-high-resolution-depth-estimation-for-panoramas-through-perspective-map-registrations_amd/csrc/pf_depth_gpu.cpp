@@ -21,12 +21,23 @@ TileRule tile_rule()
     return g_rule;
 }
 
+static RegLossRule g_loss{PF_LOSS_NONE, 0.0};
+
+RegLossRule reg_loss()
+{
+    std::lock_guard<std::mutex> lk(g_rule_mu);
+    return g_loss;
+}
+
 static pf_ctx* device_ctx();
 
 pf_ctx* facade_ctx()
 {
     pf_ctx* c = device_ctx();
-    if (c) apply_rule(c, tile_rule());  // a checked rule (SetTileValidity): cannot fail
+    if (c) {
+        apply_rule(c, tile_rule());  // a checked rule (SetTileValidity): cannot fail
+        apply_loss(c, reg_loss());   // a checked loss (SetRegistrationLoss): neither
+    }
     return c;
 }
 
@@ -210,6 +221,20 @@ bool SetTileValidity(bool on, float lo, float hi)
     return true;
 }
 
+bool SetRegistrationLoss(int kind, double a)
+{  // EXTENSION: pf_set_register_loss for every later facade call
+    const bool known = kind == PF_LOSS_NONE || kind == PF_LOSS_HUBER || kind == PF_LOSS_SOFTL1;
+    if (!known || (kind != PF_LOSS_NONE && !(a > 0.0 && a < HUGE_VAL))) {
+        std::cout << "[SetRegistrationLoss] needs PF_LOSS_NONE, or PF_LOSS_HUBER / PF_LOSS_SOFTL1 "
+                     "with a finite scale a > 0 (got "
+                  << kind << ", " << a << ")" << std::endl;
+        return false;
+    }
+    std::lock_guard<std::mutex> lk(pff::g_rule_mu);
+    pff::g_loss = pff::RegLossRule{kind, kind == PF_LOSS_NONE ? 0.0 : a};
+    return true;
+}
+
 // ---- the four map members that run on the GPU ----
 void EquirectangularMap::CopyInvalidPixels(EquirectangularMap& ref)  // Depth.cpp:703-725
 {
@@ -258,6 +283,14 @@ bool SolveDepthToDepth(EquirectangularMap& emap, std::vector<PerspectiveMap>& pm
         return false;
     }
     const std::vector<int> all(pm.size(), 1);
+    // under a loss (SetRegistrationLoss) one active map is the robust per-tile fit; several go to
+    // the joint solve, which has no robust form and answers with the library's message
+    if (pm.size() == 1 && reg_loss().kind != PF_LOSS_NONE)
+        return solve(emap, pm, "pf_register", abcd,
+                     [&](pf_ctx* c, const float* de, float* dt, float* dc) {
+                         return pf_register(c, de, emap.width, emap.height, emap.channels, dt, 1,
+                                            zr[0], zr[1], 3, 0, dc, nullptr);
+                     });
     return solve(emap, pm, "pf_register_joint", abcd,
                  [&](pf_ctx* c, const float* de, const float* dt, float* dc) {
                      return pf_register_joint(c, de, emap.width, emap.height, emap.channels, dt, 1,

@@ -30,6 +30,9 @@ struct MergeSwitches {
     // PF_TILE_VALID=LO:HI (panofuse_main --tile-valid): the tile-pixel validity rule of this
     // call; without it the rule is SetTileValidity's
     TileRule rule{false, 0.0f, 0.0f};
+    // PF_REG_LOSS=huber:A|softl1:A (panofuse_main --reg-loss): the registration loss of this
+    // call; without it the loss is SetRegistrationLoss's
+    RegLossRule loss{PF_LOSS_NONE, 0.0};
 };
 
 bool read_merge_switches(MergeSwitches& s)
@@ -55,6 +58,14 @@ bool read_merge_switches(MergeSwitches& s)
             return false;
         }
         s.rule.on = true;
+    }
+    s.loss = reg_loss();
+    if (const char* rl = std::getenv("PF_REG_LOSS")) {
+        if (!parse_reg_loss(rl, s.loss)) {
+            std::cout << "[MergeDepthMaps] bad PF_REG_LOSS " << rl
+                      << " (want huber:A or softl1:A, A > 0)" << std::endl;
+            return false;
+        }
     }
     s.save_stitch = env_on("PF_SAVE_STITCH");
     s.check_laplacian = env_on("PF_CHECK_LAPLACIAN");
@@ -126,9 +137,38 @@ struct Job {
 
 // Registration (Depth.cpp:789-808): every tile alone; depth tiles: cubic, the transform fused
 // into the fusion; disparity tiles: y = 1/(a x + b) + d, D2DTransform on the uploaded copy.
-bool register_tiles(const Job& j, float* d_coeffs, bool disparity_tiles)
+bool register_tiles(const Job& j, float* d_coeffs, bool disparity_tiles, int ntiles,
+                    const RegLossRule& loss)
 {
     const EquirectangularMap& e = j.emap;
+    if (loss.kind != PF_LOSS_NONE) {  // the same calls with the solver summary, one line per tile
+        static const char* const kTerm[] = {"no convergence", "function tolerance",
+                                            "parameter tolerance", "gradient tolerance",
+                                            "minimum trust-region radius", "failure"};
+        DevMem ds(sizeof(double) * 6 * ntiles);
+        std::vector<double> sm((size_t)6 * ntiles);
+        if (!ds.ok ||
+            !call_sync(j.c,
+                       disparity_tiles
+                           ? pf_register_disparity(j.c, j.d_emap, e.width, e.height, e.channels,
+                                                   j.d_tiles, 1, j.zr[0], j.zr[1], 1, d_coeffs,
+                                                   nullptr, ds.as<double>())
+                           : pf_register_ex(j.c, j.d_emap, e.width, e.height, e.channels,
+                                            j.d_tiles, 1, j.zr[0], j.zr[1], 3, 0, d_coeffs,
+                                            nullptr, ds.as<double>()),
+                       disparity_tiles ? "pf_register_disparity" : "pf_register_ex") ||
+            !download(sm.data(), ds, sm.size()))
+            return false;
+        for (int p = 0; p < ntiles; p++) {
+            const double* s = &sm[(size_t)6 * p];
+            const int term = s[3] >= 0 && s[3] <= 5 ? (int)s[3] : 5;
+            std::cout << "[robust] tile " << p << ": " << (long long)(s[4] - s[5]) << " of "
+                      << (long long)s[4] << " samples beyond a=" << loss.a << ", cost " << s[0]
+                      << " -> " << s[1] << ", " << (int)s[2] << " iterations, " << kTerm[term]
+                      << std::endl;
+        }
+        return true;
+    }
     return call_sync(j.c,
                      disparity_tiles
                          ? pf_register_disparity(j.c, j.d_emap, e.width, e.height, e.channels,
@@ -291,6 +331,17 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
                   << std::endl;
         return false;
     }
+    // the global fit has no robust form: refused with the library's message before any file is read
+    if (sw.loss.kind != PF_LOSS_NONE && sw.global_align) {
+        if (pf_ctx* c = facade_ctx()) {
+            apply_loss(c, sw.loss);
+            pf_ok(c, pf_register_global(c, nullptr, 0, 0, 0, nullptr, 1, 0, 0, 0.0f, 0.0f, 0,
+                                        nullptr, nullptr, nullptr),
+                  "pf_register_global");
+            apply_loss(c, reg_loss());
+        }
+        return false;
+    }
     EquirectangularMap emap, gt;
     std::vector<PerspectiveMap> pmaps;
     // the ground truth decodes on a host thread while the tiles load and the GPU fuses
@@ -312,9 +363,14 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
     // this call's rule (PF_TILE_VALID over SetTileValidity's); the stored one comes back at exit
     struct RuleScope {
         pf_ctx* c;
-        ~RuleScope() { apply_rule(c, tile_rule()); }
+        ~RuleScope()
+        {
+            apply_rule(c, tile_rule());
+            apply_loss(c, reg_loss());
+        }
     } rule_scope{c};
     if (!pf_ok(c, apply_rule(c, sw.rule), "pf_set_tile_validity")) return false;
+    if (!pf_ok(c, apply_loss(c, sw.loss), "pf_set_register_loss")) return false;
     DevMem dt = tiles_on_device(c, pmaps);
     if (!dt.ok) return false;
     DevMem de = on_device(emap), dc(sizeof(float) * 4 * pmaps.size()), dout(no * 2);
@@ -325,7 +381,8 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
 
     if (sw.rule.on && !print_mask_lines(j, (int)pmaps.size(), sw.rule)) return false;
     auto t = std::chrono::steady_clock::now();
-    if (!register_tiles(j, dc.as<float>(), disparity_tiles)) return false;
+    if (!register_tiles(j, dc.as<float>(), disparity_tiles, (int)pmaps.size(), sw.loss))
+        return false;
     if (time_Reg) *time_Reg = elapsed_ms(t);
     t = std::chrono::steady_clock::now();
     if (!fuse(j, sw)) return false;

@@ -12,47 +12,42 @@
 // Summation order (part of the contract; tests/disp_ref.py restates it): lane l adds its samples
 // l, l + 256, ... in order from 0.0, then the halving tree of k_register (stride 128, 64, ..., 1:
 // p[l] = p[l] + p[l + stride]).  Only fp64 + - * / sqrt, no contraction.
-#include "pf_internal.hpp"
-
-#include <cfloat>
+#include "pf_lm.hpp"
 
 namespace pf {
 
 namespace {
-constexpr int kDispLanes = 256;
-// Resident capacity: samples of one tile kept in registers across the LM iterations
-// (kDispPerLane (X, Y) pairs per lane, as the floats they were read as: the clamp to fp64 is
-// repeated per use).  Samples past it are gathered again from the cached indices in every
-// evaluation, in the same per-lane order.
-constexpr int kDispPerLane = 32;
-constexpr int kDispResident = kDispLanes * kDispPerLane;
 constexpr int kDispSums = 10;  // cost, J'r (3), upper J'J (6)
-
-constexpr int kLmMaxIter = 50;
-constexpr double kLmInitRadius = 1e4, kLmMaxRadius = 1e16, kLmMinRadius = 1e-32;
-constexpr double kLmMinRelDecrease = 1e-3, kLmMinDiag = 1e-6, kLmMaxDiag = 1e32;
-constexpr int kLmMaxInvalid = 5;
-constexpr double kLmFuncTol = 1e-6, kLmGradTol = 1e-10, kLmParamTol = 1e-8;
-// termination codes of the summary (the order of pfo_lm_summary's)
-enum { kTermNoConvergence = 0, kTermFunctionTol, kTermParameterTol, kTermGradientTol,
-       kTermMinRadius, kTermFailure };
-
-__device__ __forceinline__ double clamp_sample(double v)
-{  // Depth.cpp:1352-1362, as k_register
-    if (v < 1e-4) v = 1e-4;
-    else if (v > (1 - 1e-4)) v = 1 - 1e-4;
-    return v;
-}
 
 // One sample's terms at p = (a, b, d): r = (q + d) - Y with q = 1 / (a X + b), Jacobian row
 // (-(X q q), -(q q), 1).
+// With LOSS (pf_set_register_loss) the cost term is 0.5 rho(r r) and the residual and the row
+// are scaled by sqrt(rho'(r r)) first (pf_lm.hpp); without, this is the code it always was.
+template <bool LOSS>
 __device__ __forceinline__ void disp_terms(double X, double Y, const double p[3],
-                                           double acc[kDispSums])
+                                           double acc[kDispSums], const RegLoss& L)
 {
     const double q = 1.0 / (p[0] * X + p[1]);
     const double r = (q + p[2]) - Y;
     const double qq = q * q;
     const double j0 = -(X * qq), j1 = -qq;
+    if constexpr (LOSS) {
+        double rho0, rho1;
+        loss_eval(L, r * r, rho0, rho1);
+        const double w = sqrt(rho1);
+        const double rc = w * r, k0 = w * j0, k1 = w * j1, k2 = w;
+        acc[0] = acc[0] + 0.5 * rho0;
+        acc[1] = acc[1] + k0 * rc;
+        acc[2] = acc[2] + k1 * rc;
+        acc[3] = acc[3] + k2 * rc;
+        acc[4] = acc[4] + k0 * k0;
+        acc[5] = acc[5] + k0 * k1;
+        acc[6] = acc[6] + k0 * k2;
+        acc[7] = acc[7] + k1 * k1;
+        acc[8] = acc[8] + k1 * k2;
+        acc[9] = acc[9] + k2 * k2;
+        return;
+    }
     acc[0] = acc[0] + 0.5 * (r * r);
     acc[1] = acc[1] + j0 * r;
     acc[2] = acc[2] + j1 * r;
@@ -65,41 +60,19 @@ __device__ __forceinline__ void disp_terms(double X, double Y, const double p[3]
     acc[9] = acc[9] + 1.0;
 }
 
-__device__ __forceinline__ void disp_cost_term(double X, double Y, const double p[3], double& acc)
+template <bool LOSS>
+__device__ __forceinline__ void disp_cost_term(double X, double Y, const double p[3], double& acc,
+                                               const RegLoss& L)
 {
     const double q = 1.0 / (p[0] * X + p[1]);
     const double r = (q + p[2]) - Y;
-    acc = acc + 0.5 * (r * r);
-}
-
-// The halving tree over the 256 lanes' partial sums, every lane receiving the totals.  Strides
-// 128 and 64 are wave 0 reading the four waves' values from LDS, strides 32..1 its lane shifts:
-// the same additions in the same association as p[l] = p[l] + p[l + stride].
-template <int N>
-__device__ __forceinline__ void disp_reduce(double* acc, double (*part)[kDispLanes], double* tot,
-                                            int l)
-{
-#pragma unroll
-    for (int k = 0; k < N; k++) part[k][l] = acc[k];
-    __syncthreads();
-    if (l < 64) {
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-            double v = (part[k][l] + part[k][l + 128]) + (part[k][l + 64] + part[k][l + 192]);
-#pragma unroll
-            for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_down(v, s, 64);
-            if (l == 0) tot[k] = v;
-        }
+    if constexpr (LOSS) {
+        double rho0, rho1;
+        loss_eval(L, r * r, rho0, rho1);
+        acc = acc + 0.5 * rho0;
+        return;
     }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) acc[k] = tot[k];
-}
-
-__device__ __forceinline__ double inv_psd1(double v)
-{  // Eigen LLT of a 1x1 block solved against 1 (InvertPSDMatrix, full rank)
-    const double l = sqrt(v);
-    return (1.0 / l) / l;
+    acc = acc + 0.5 * (r * r);
 }
 
 __device__ __forceinline__ bool llt2_solve(const double S[2][2], const double rhs[2], double z[2])
@@ -127,14 +100,16 @@ __device__ __forceinline__ double norm3(const double v[3])
 }
 }  // namespace
 
-__global__ void __launch_bounds__(kDispLanes) k_register_disp(
+// One block's fit of tile p of panorama b.  LOSS: under the robust loss L, with the 6-entry
+// summary of pf_register_ex; without, k_register_disp as it was.
+template <bool LOSS>
+__device__ __forceinline__ void register_disp_tile(
     const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
     const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
     long long tstride, const int2* __restrict__ sidx, float* __restrict__ coeffs,
-    double* __restrict__ coeffs64, double* __restrict__ summary)
+    double* __restrict__ coeffs64, double* __restrict__ summary, const RegLoss L,
+    double (*part)[kDispLanes], double* tot)
 {
-    __shared__ double part[kDispSums][kDispLanes];
-    __shared__ double tot[kDispSums];
     // k_register's block order: the tiles of one panorama on one XCD
     const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
     const int p = (int)(lb % (unsigned)ntiles), b = (int)(lb / (unsigned)ntiles), l = threadIdx.x;
@@ -164,10 +139,12 @@ __global__ void __launch_bounds__(kDispLanes) k_register_disp(
 #pragma unroll
         for (int u = 0; u < kDispPerLane; u++)
             if (l + u * kDispLanes < ns)
-                disp_terms(clamp_sample((double)xs[u]), clamp_sample((double)ys[u]), q, S);
+                disp_terms<LOSS>(clamp_sample((double)xs[u]), clamp_sample((double)ys[u]), q, S,
+                                 L);
         for (int s = l + kDispResident; s < ns; s += kDispLanes) {  // past the capacity
             const int2 i2 = ix[s];
-            disp_terms(clamp_sample((double)tile[i2.x]), clamp_sample((double)em[i2.y]), q, S);
+            disp_terms<LOSS>(clamp_sample((double)tile[i2.x]), clamp_sample((double)em[i2.y]), q,
+                             S, L);
         }
         disp_reduce<kDispSums>(S, part, tot, l);
     };
@@ -176,10 +153,12 @@ __global__ void __launch_bounds__(kDispLanes) k_register_disp(
 #pragma unroll
         for (int u = 0; u < kDispPerLane; u++)
             if (l + u * kDispLanes < ns)
-                disp_cost_term(clamp_sample((double)xs[u]), clamp_sample((double)ys[u]), q, c);
+                disp_cost_term<LOSS>(clamp_sample((double)xs[u]), clamp_sample((double)ys[u]), q,
+                                     c, L);
         for (int s = l + kDispResident; s < ns; s += kDispLanes) {
             const int2 i2 = ix[s];
-            disp_cost_term(clamp_sample((double)tile[i2.x]), clamp_sample((double)em[i2.y]), q, c);
+            disp_cost_term<LOSS>(clamp_sample((double)tile[i2.x]), clamp_sample((double)em[i2.y]),
+                                 q, c, L);
         }
         disp_reduce<1>(&c, part, tot, l);
         return c;
@@ -304,6 +283,24 @@ __global__ void __launch_bounds__(kDispLanes) k_register_disp(
             successful = false;
         }
     }
+    double inliers = 0.0;
+    if constexpr (LOSS) {
+        if (summary) {  // the samples with r r <= a a at the returned parameters (exact counts)
+            auto count = [&](double X, double Y) {
+                const double r = (1.0 / (best[0] * X + best[1]) + best[2]) - Y;
+                if (r * r <= L.b) inliers = inliers + 1.0;
+            };
+#pragma unroll
+            for (int u = 0; u < kDispPerLane; u++)
+                if (l + u * kDispLanes < ns)
+                    count(clamp_sample((double)xs[u]), clamp_sample((double)ys[u]));
+            for (int s = l + kDispResident; s < ns; s += kDispLanes) {
+                const int2 i2 = ix[s];
+                count(clamp_sample((double)tile[i2.x]), clamp_sample((double)em[i2.y]));
+            }
+            disp_reduce<1>(&inliers, part, tot, l);
+        }
+    }
     if (l == 0) {
         // abcd = (a, b, 1, d): the order D2DTransform reads (Depth.cpp:216-219, 233)
         const double full[4] = {best[0], best[1], 1.0, best[2]};
@@ -313,12 +310,41 @@ __global__ void __launch_bounds__(kDispLanes) k_register_disp(
             if (coeffs64) coeffs64[o * 4 + i] = full[i];
         }
         if (summary) {
-            summary[o * 4 + 0] = initial_cost;
-            summary[o * 4 + 1] = min_cost;
-            summary[o * 4 + 2] = (double)iteration;
-            summary[o * 4 + 3] = (double)term;
+            constexpr int kN = LOSS ? 6 : 4;
+            summary[o * kN + 0] = initial_cost;
+            summary[o * kN + 1] = min_cost;
+            summary[o * kN + 2] = (double)iteration;
+            summary[o * kN + 3] = (double)term;
+            if constexpr (LOSS) {
+                summary[o * kN + 4] = (double)ns;
+                summary[o * kN + 5] = inliers;
+            }
         }
     }
+}
+
+__global__ void __launch_bounds__(kDispLanes) k_register_disp(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, const int2* __restrict__ sidx, float* __restrict__ coeffs,
+    double* __restrict__ coeffs64, double* __restrict__ summary)
+{
+    __shared__ double part[kDispSums][kDispLanes];
+    __shared__ double tot[kDispSums];
+    register_disp_tile<false>(geom, grids, ntiles, emap, estride, tiles, tstride, sidx, coeffs,
+                              coeffs64, summary, RegLoss{PF_LOSS_NONE, 0.0, 0.0, 0.0}, part, tot);
+}
+
+__global__ void __launch_bounds__(kDispLanes) k_register_disp_loss(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, const int2* __restrict__ sidx, float* __restrict__ coeffs,
+    double* __restrict__ coeffs64, double* __restrict__ summary, RegLoss loss)
+{
+    __shared__ double part[kDispSums][kDispLanes];
+    __shared__ double tot[kDispSums];
+    register_disp_tile<true>(geom, grids, ntiles, emap, estride, tiles, tstride, sidx, coeffs,
+                             coeffs64, summary, loss, part, tot);
 }
 
 // D2DTransform's per-pixel map (Depth.cpp:225-240).  The X clamps compare the float against the
@@ -361,8 +387,15 @@ __global__ void __launch_bounds__(256) k_disp_map(float* __restrict__ data, long
 void launch_register_disp(hipStream_t s, const TileGeom* geom, const RegGrid* grids, int ntiles,
                           const float* emap, long long estride, const float* tiles,
                           long long tstride, const int2* sidx, float* coeffs, double* coeffs64,
-                          double* summary, int batch)
+                          double* summary, int batch, int loss_kind, double loss_a)
 {
+    if (loss_kind != PF_LOSS_NONE) {
+        hipLaunchKernelGGL(k_register_disp_loss, dim3((unsigned)(ntiles * batch)),
+                           dim3(kDispLanes), 0, s, geom, grids, ntiles, emap, estride, tiles,
+                           tstride, sidx, coeffs, coeffs64, summary,
+                           make_loss(loss_kind, loss_a));
+        return;
+    }
     hipLaunchKernelGGL(k_register_disp, dim3((unsigned)(ntiles * batch)), dim3(kDispLanes), 0, s,
                        geom, grids, ntiles, emap, estride, tiles, tstride, sidx, coeffs, coeffs64,
                        summary);

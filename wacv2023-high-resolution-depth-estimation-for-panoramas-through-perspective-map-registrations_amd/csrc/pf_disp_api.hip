@@ -32,7 +32,7 @@ int pf_register_disparity(pf_ctx* c, const float* emap, int ew, int eh, int ec, 
                      apply ? 2 : 1);
         launch_register_disp(c->stream, (const TileGeom*)c->geom.p, (const RegGrid*)c->reg.p,
                              c->ntiles, emap, (long long)ew * eh * ec, tiles, c->tile_elems, sidx,
-                             cf, coeffs64, summary, batch);
+                             cf, coeffs64, summary, batch, c->loss_kind, c->loss_a);
         if (apply)
             launch_apply_disp(c->stream, (const TileGeom*)c->geom.p, c->ntiles,
                               c->tile_elems / c->tile_c, tiles, c->tile_elems, cf, batch);

@@ -10,7 +10,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <cstdlib>
 #include <iostream>
+#include <string>
 #include <utility>
 
 // hidden: nothing in pff is an export of the library
@@ -33,6 +36,31 @@ TileRule tile_rule();
 inline int apply_rule(pf_ctx* c, const TileRule& r)
 {
     return pf_set_tile_validity(c, r.on ? PF_VALID_RANGE : PF_VALID_ALL, r.lo, r.hi);
+}
+
+// The robust registration loss of the facade (SetRegistrationLoss), carried the same way.
+struct RegLossRule {
+    int kind;  // PF_LOSS_*
+    double a;
+};
+RegLossRule reg_loss();
+inline int apply_loss(pf_ctx* c, const RegLossRule& r)
+{
+    return pf_set_register_loss(c, r.kind, r.a);
+}
+// "huber:A" or "softl1:A" with a finite A > 0 (PF_REG_LOSS / --reg-loss).
+inline bool parse_reg_loss(const char* s, RegLossRule& r)
+{
+    const std::string v(s ? s : "");
+    const size_t colon = v.find(':');
+    if (colon == std::string::npos) return false;
+    const std::string name = v.substr(0, colon), num = v.substr(colon + 1);
+    if (name == "huber") r.kind = PF_LOSS_HUBER;
+    else if (name == "softl1") r.kind = PF_LOSS_SOFTL1;
+    else return false;
+    char* end = nullptr;
+    r.a = std::strtod(num.c_str(), &end);
+    return !num.empty() && end && *end == '\0' && r.a > 0.0 && r.a < HUGE_VAL;
 }
 
 inline bool hip_ok(hipError_t e, const char* what)

@@ -332,16 +332,27 @@ static int fuse_impl(pf_ctx* c, const float* emap, int ew, int eh, int ec, const
                       (float*)c->lnorm.p);
 }
 
-extern "C" {
-
-int pf_register(pf_ctx* c, const float* emap, int ew, int eh, int ec, float* tiles, int batch,
-                float zr0, float zr1, int degree, int apply, float* coeffs, double* coeffs64)
+// pf_register / pf_register_ex.  The launchers branch on the context's loss: without one this
+// launches what pf_register always did.
+static int register_impl(pf_ctx* c, const float* emap, int ew, int eh, int ec, float* tiles,
+                         int batch, float zr0, float zr1, int degree, int apply, float* coeffs,
+                         double* coeffs64, double* summary)
 {
     int rc;
     if ((rc = check_common(c, batch))) return rc;
     if ((rc = check_emap(c, emap, ew, eh, ec))) return rc;
     if (!tiles) return fail(c, PF_EINVAL, "tiles is NULL");
     if (degree < 0 || degree > 3) return fail(c, PF_EINVAL, "degree %d not in [0,3]", degree);
+    const bool robust = c->loss_kind != PF_LOSS_NONE;
+    if (summary && !robust)
+        return fail(c, PF_EINVAL,
+                    "pf_register_ex: summary needs a loss (pf_set_register_loss); the moment-sum "
+                    "solve has none to report");
+    if (robust && (degree != 3 || c->solver != PF_SOLVER_LM))
+        return fail(c, PF_EINVAL,
+                    "the loss of pf_set_register_loss needs degree 3 and PF_SOLVER_LM (got degree "
+                    "%d, solver %d)",
+                    degree, c->solver);
     if ((rc = prepare_registration(c, zr0, zr1))) return rc;
     if ((rc = check_reg_grids(c, nullptr))) return rc;
     float* cf = coeffs;
@@ -352,20 +363,57 @@ int pf_register(pf_ctx* c, const float* emap, int ew, int eh, int ec, float* til
     double nsamp = 0;
     for (const RegGrid& g : c->reg_h) nsamp += (double)(g.cols + 1) * (g.rows + 1);
     const int2* sidx = reg_sample_index(c, ew, eh, ec);  // before the stage timer: built once
+    if (robust && !sidx) return fail(c, PF_EHIP, "robust registration: no sample-index table");
     {
         StageTimer t(c, PF_STAGE_REGISTER,
                      batch * (8.0 * nsamp + (apply ? 8.0 * (double)c->tile_elems / c->tile_c : 0.0)),
                      apply ? 2 : 1);
-        launch_register(c->stream, (const TileGeom*)c->geom.p, (const RegGrid*)c->reg.p,
-                        (const GridCol*)c->rcols.p, (const GridRow*)c->rrows.p, c->ntiles, emap,
-                        ew, eh, ec, (long long)ew * eh * ec, tiles, c->tile_elems, degree,
-                        c->solver, cf, coeffs64, batch, nullptr, nullptr, sidx, c->valid);
+        if (robust)
+            launch_register_robust(c->stream, (const TileGeom*)c->geom.p, (const RegGrid*)c->reg.p,
+                                   c->ntiles, emap, (long long)ew * eh * ec, tiles, c->tile_elems,
+                                   sidx, cf, coeffs64, summary, batch, c->loss_kind, c->loss_a,
+                                   c->valid);
+        else
+            launch_register(c->stream, (const TileGeom*)c->geom.p, (const RegGrid*)c->reg.p,
+                            (const GridCol*)c->rcols.p, (const GridRow*)c->rrows.p, c->ntiles,
+                            emap, ew, eh, ec, (long long)ew * eh * ec, tiles, c->tile_elems,
+                            degree, c->solver, cf, coeffs64, batch, nullptr, nullptr, sidx,
+                            c->valid);
         if (apply)
             launch_apply_cubic(c->stream, (const TileGeom*)c->geom.p, c->ntiles,
                                c->tile_elems / c->tile_c, tiles, c->tile_elems, cf, batch,
                                c->valid);
     }
     HIPCHK(c, hipGetLastError());
+    return PF_OK;
+}
+
+extern "C" {
+
+int pf_register(pf_ctx* c, const float* emap, int ew, int eh, int ec, float* tiles, int batch,
+                float zr0, float zr1, int degree, int apply, float* coeffs, double* coeffs64)
+{
+    return register_impl(c, emap, ew, eh, ec, tiles, batch, zr0, zr1, degree, apply, coeffs,
+                         coeffs64, nullptr);
+}
+
+int pf_register_ex(pf_ctx* c, const float* emap, int ew, int eh, int ec, float* tiles, int batch,
+                   float zr0, float zr1, int degree, int apply, float* coeffs, double* coeffs64,
+                   double* summary)
+{
+    return register_impl(c, emap, ew, eh, ec, tiles, batch, zr0, zr1, degree, apply, coeffs,
+                         coeffs64, summary);
+}
+
+int pf_set_register_loss(pf_ctx* c, int kind, double a)
+{
+    if (!c) return PF_EINVAL;
+    if (kind != PF_LOSS_NONE && kind != PF_LOSS_HUBER && kind != PF_LOSS_SOFTL1)
+        return fail(c, PF_EINVAL, "pf_set_register_loss: unknown loss %d", kind);
+    if (kind != PF_LOSS_NONE && !(std::isfinite(a) && a > 0.0))
+        return fail(c, PF_EINVAL, "pf_set_register_loss: needs a finite scale a > 0 (got %g)", a);
+    c->loss_kind = kind;
+    c->loss_a = kind == PF_LOSS_NONE ? 0.0 : a;
     return PF_OK;
 }
 
@@ -406,6 +454,7 @@ int pf_register_joint(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
 {
     int rc;
     if ((rc = check_common(c, batch))) return rc;
+    if ((rc = check_no_loss(c, "pf_register_joint"))) return rc;
     if ((rc = check_emap(c, emap, ew, eh, ec))) return rc;
     if (!tiles || !active) return fail(c, PF_EINVAL, "tiles/active is NULL");
     if (degree < 0 || degree > 3) return fail(c, PF_EINVAL, "degree %d not in [0,3]", degree);

@@ -75,6 +75,7 @@ int pf_register_global(pf_ctx* c, const float* emap, int ew, int eh, int ec, uin
 {
     int rc, h0, h1;
     if ((rc = check_device(c))) return rc;
+    if ((rc = check_no_loss(c, "pf_register_global"))) return rc;
     if (batch <= 0 || batch > 65535) return fail(c, PF_EINVAL, "batch %d out of range", batch);
     if ((rc = check_emap(c, emap, ew, eh, ec))) return rc;
     if (!data) return fail(c, PF_EINVAL, "pf_register_global: data is NULL");

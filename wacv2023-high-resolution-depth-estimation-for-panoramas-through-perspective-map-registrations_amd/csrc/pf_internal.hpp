@@ -370,11 +370,22 @@ void launch_valid_counts(hipStream_t s, const TileGeom* geom, const RegGrid* gri
                          int batch);
 // Disparity-tile registration (pf_disp.hip): the LM fit of y = 1/(a x + b) + d per (panorama,
 // tile) on the samples of sidx (launch_regidx), abcd = (a, b, 1, d); summary (optional):
-// [batch][ntiles] x {initial cost, final cost, iterations, termination code}.
+// [batch][ntiles] x {initial cost, final cost, iterations, termination code}.  With a loss
+// (pf_set_register_loss) the loss instantiation runs, and summary has launch_register_robust's 6.
 void launch_register_disp(hipStream_t s, const TileGeom* geom, const RegGrid* grids, int ntiles,
                           const float* emap, long long estride, const float* tiles,
                           long long tstride, const int2* sidx, float* coeffs, double* coeffs64,
-                          double* summary, int batch);
+                          double* summary, int batch, int loss_kind = PF_LOSS_NONE,
+                          double loss_a = 0.0);
+// Robust cubic registration (pf_robust.hip): the sample-wise LM fit of y = a x^3 + b x^2 + c x + d
+// per (panorama, tile) under the loss, from (1,1,1,1); summary (optional): [batch][ntiles] x
+// {initial cost, final cost, iterations, termination code, samples used, inliers}.  tv: the
+// validity rule (a skipped sample adds nothing; fewer than 4 left: NaN coefficients, code 5).
+void launch_register_robust(hipStream_t s, const TileGeom* geom, const RegGrid* grids, int ntiles,
+                            const float* emap, long long estride, const float* tiles,
+                            long long tstride, const int2* sidx, float* coeffs, double* coeffs64,
+                            double* summary, int batch, int loss_kind, double loss_a,
+                            TileValid tv);
 // D2DTransform (Depth.cpp:214-243) on all tiles / on one map, channel 0, in place
 void launch_apply_disp(hipStream_t s, const TileGeom* geom, int ntiles, long long tile_pixels,
                        float* tiles, long long tstride, const float* coeffs, int batch);

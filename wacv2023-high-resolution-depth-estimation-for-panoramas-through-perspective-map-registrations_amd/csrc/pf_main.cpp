@@ -65,6 +65,10 @@
 // prints "[mask] tile <i>: <n> of <N> pixels invalid, <m> of <M> samples" per tile that has any.
 // Not with --tile-model disparity or --fusion smoothing.  Carried in PF_TILE_VALID.  (The usage
 // text of the bare command is pinned by the tests and does not list it.)
+// --reg-loss huber:A|softl1:A (opt-in): the tile registrations run under Ceres' HuberLoss(A) or
+// SoftLOneLoss(A) (pf_set_register_loss), and the run prints per tile "[robust] tile <i>: <m> of
+// <n> samples beyond a=<A>, cost <c0> -> <c1>, <it> iterations, <termination>".  Not with
+// --global-align.  Carried in PF_REG_LOSS; not in the usage text either.
 #include "pf_facade.hpp"  // the inline to_window and load_pair; it includes the two public headers
 #include "pf_valid.hpp"
 
@@ -342,6 +346,11 @@ static int mode0_command(int argc, char* argv[])
             std::string err;
             if (!pfv::parse_range(v.c_str(), lo, hi, err)) return bad(k, v, "LO:HI, LO < HI");
             setenv("PF_TILE_VALID", v.c_str(), 1);  // read by MergeDepthMaps
+        }
+        else if (k == "--reg-loss") {
+            pff::RegLossRule r;
+            if (!pff::parse_reg_loss(v.c_str(), r)) return bad(k, v, "huber:A or softl1:A, A > 0");
+            setenv("PF_REG_LOSS", v.c_str(), 1);  // read by MergeDepthMaps / MergeDisparityMaps
         }
         else if (k == "--shard") {  // R/N: one process per GPU over the sorted folder
             if (std::sscanf(v.c_str(), "%d/%d", &shard, &nshards) != 2 || nshards < 1 ||

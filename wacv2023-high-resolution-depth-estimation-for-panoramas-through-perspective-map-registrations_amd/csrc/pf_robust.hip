@@ -1,0 +1,371 @@
+// pf_robust.hip -- robust cubic tile registration (pf_set_register_loss): the per-tile fit of
+// y = a x^3 + b x^2 + c x + d under Ceres 1.13's HuberLoss or SoftLOneLoss, by the reference's
+// trust-region Levenberg-Marquardt.
+//
+// k_register solves the cubic from 15 moment sums; a loss weights every sample by a function of
+// its own residual, which moments cannot carry, so this kernel is sample-wise, in the form of
+// k_register_disp (pf_disp.hip): one 256-lane workgroup owns one (panorama, tile) pair, gathers the
+// samples once through the cached indices, keeps up to 32 (x, y) float pairs per lane in
+// registers, and runs the whole LM on them.  A Jacobian evaluation reduces 15 fp64 sums (cost, 4
+// of J'r, 10 of upper J'J, all of the corrected residual sqrt(rho') r and row sqrt(rho') J), a
+// trial evaluation 1.  Every lane runs the scalar LM algebra on the same reduced sums, so every
+// branch is block-uniform; blocks never talk to each other.
+//
+// Summation order (part of the contract; tests/robust_ref.py restates it): lane l adds its samples
+// l, l + 256, ... in order from 0.0, then the halving tree of disp_reduce.  Only fp64 + - * / sqrt,
+// no contraction.  LDS: 15 x 256 doubles (+ 15 totals).
+#include "pf_lm.hpp"
+
+namespace pf {
+
+namespace {
+constexpr int kRobSums = 15;  // cost, J'r (4), upper J'J (10, row-major)
+
+// One sample's residual at p = (a, b, c, d), and its powers: the Jacobian row is (X3, X2, X, 1).
+__device__ __forceinline__ double cubic_residual(double X, double Y, const double p[4], double& X2,
+                                                 double& X3)
+{
+    X2 = X * X;
+    X3 = X * X * X;
+    return (((X3 * p[0] + X2 * p[1]) + X * p[2]) + p[3]) - Y;
+}
+
+__device__ __forceinline__ void rob_terms(double X, double Y, const double p[4],
+                                          double acc[kRobSums], const RegLoss& L)
+{
+    double X2, X3, rho0, rho1;
+    const double r = cubic_residual(X, Y, p, X2, X3);
+    loss_eval(L, r * r, rho0, rho1);
+    const double w = sqrt(rho1);
+    const double rc = w * r, j0 = w * X3, j1 = w * X2, j2 = w * X, j3 = w;
+    acc[0] = acc[0] + 0.5 * rho0;
+    acc[1] = acc[1] + j0 * rc;
+    acc[2] = acc[2] + j1 * rc;
+    acc[3] = acc[3] + j2 * rc;
+    acc[4] = acc[4] + j3 * rc;
+    acc[5] = acc[5] + j0 * j0;
+    acc[6] = acc[6] + j0 * j1;
+    acc[7] = acc[7] + j0 * j2;
+    acc[8] = acc[8] + j0 * j3;
+    acc[9] = acc[9] + j1 * j1;
+    acc[10] = acc[10] + j1 * j2;
+    acc[11] = acc[11] + j1 * j3;
+    acc[12] = acc[12] + j2 * j2;
+    acc[13] = acc[13] + j2 * j3;
+    acc[14] = acc[14] + j3 * j3;
+}
+
+__device__ __forceinline__ void rob_cost_term(double X, double Y, const double p[4], double& acc,
+                                              const RegLoss& L)
+{
+    double X2, X3, rho0, rho1;
+    const double r = cubic_residual(X, Y, p, X2, X3);
+    loss_eval(L, r * r, rho0, rho1);
+    acc = acc + 0.5 * rho0;
+}
+
+__device__ bool llt3_solve(double S[3][3], const double rhs[3], double z[3])
+{  // Eigen LLT<Upper> of the 3x3 reduced Schur system (schur_complement_solver.cc:197-213), as
+   // lm_moments' (pf_kernels.hip)
+    double Lo[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    for (int k = 0; k < 3; k++) {
+        double x = S[k][k];
+        if (k > 0) {
+            double sq = 0.0;
+            for (int i = 0; i < k; i++) sq = sq + Lo[k][i] * Lo[k][i];
+            x = x - sq;
+        }
+        if (!(x > 0.0)) return false;
+        Lo[k][k] = x = sqrt(x);
+        for (int j = k + 1; j < 3; j++) {
+            double a = S[k][j];
+            for (int i = 0; i < k; i++) a = a - Lo[j][i] * Lo[k][i];
+            Lo[j][k] = a / x;
+        }
+    }
+    double y[3] = {rhs[0], rhs[1], rhs[2]};
+    for (int k = 0; k < 3; k++) {
+        y[k] = y[k] / Lo[k][k];
+        for (int j = k + 1; j < 3; j++) y[j] = y[j] - Lo[j][k] * y[k];
+    }
+    for (int k = 2; k >= 0; k--) {
+        y[k] = y[k] / Lo[k][k];
+        for (int j = 0; j < k; j++) y[j] = y[j] - Lo[k][j] * y[k];
+    }
+    z[0] = y[0]; z[1] = y[1]; z[2] = y[2];
+    return true;
+}
+
+__device__ __forceinline__ double norm4(const double v[4])
+{
+    return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
+}
+}  // namespace
+
+// MASK: under the validity rule (k_register_valid's: a sample whose raw tile value fails the rule,
+// or whose baseline value is not finite, is skipped and adds nothing).
+template <bool MASK>
+__global__ void __launch_bounds__(kDispLanes) k_register_robust(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, const int2* __restrict__ sidx, float* __restrict__ coeffs,
+    double* __restrict__ coeffs64, double* __restrict__ summary, RegLoss L, float vlo, float vhi)
+{
+    __shared__ double part[kRobSums][kDispLanes];
+    __shared__ double tot[kRobSums];
+    // k_register_disp's block order: the tiles of one panorama on one XCD
+    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
+    const int p = (int)(lb % (unsigned)ntiles), b = (int)(lb / (unsigned)ntiles), l = threadIdx.x;
+    const RegGrid rg = grids[p];
+    const float* tile = tiles + b * tstride + geom[p].off;
+    const float* em = emap + b * estride;
+    const int2* ix = sidx + rg.soff;
+    const int ns = (rg.cols + 1) * (rg.rows + 1);
+    auto kept = [&](float tv, float ev) {
+        if constexpr (MASK) return tile_ok(tv, vlo, vhi) && isfinite(ev);
+        return true;
+    };
+
+    // the lane's resident samples l, l + 256, ...: gathered once (independent loads); bit u of
+    // live: sample u exists and is kept
+    float xs[kDispPerLane], ys[kDispPerLane];
+    unsigned live = 0u;
+#pragma unroll
+    for (int u = 0; u < kDispPerLane; u++) {
+        const int s = l + u * kDispLanes;
+        xs[u] = 0.5f;
+        ys[u] = 0.5f;
+        if (s < ns) {
+            const int2 i2 = ix[s];
+            xs[u] = tile[i2.x];
+            ys[u] = em[i2.y];
+            if (kept(xs[u], ys[u])) live |= 1u << u;
+        }
+    }
+
+    // each(f): f(X, Y) on the lane's kept samples in order, X and Y clamped in fp64.  The empty
+    // asm keeps the compiler from widening the 64 resident floats to clamped doubles once and
+    // holding those across the evaluations: that form spills to scratch.
+    auto each = [&](auto&& f) {
+#pragma unroll
+        for (int u = 0; u < kDispPerLane; u++)
+            if (live >> u & 1u) {
+                float xv = xs[u], yv = ys[u];
+                asm volatile("" : "+v"(xv), "+v"(yv));
+                f(clamp_sample((double)xv), clamp_sample((double)yv));
+            }
+        for (int s = l + kDispResident; s < ns; s += kDispLanes) {  // past the capacity
+            const int2 i2 = ix[s];
+            const float tv = tile[i2.x], ev = em[i2.y];
+            if (kept(tv, ev)) f(clamp_sample((double)tv), clamp_sample((double)ev));
+        }
+    };
+    auto eval_full = [&](const double* q, double* S) {
+#pragma unroll
+        for (int k = 0; k < kRobSums; k++) S[k] = 0.0;
+        each([&](double X, double Y) { rob_terms(X, Y, q, S, L); });
+        disp_reduce<kRobSums>(S, part, tot, l);
+    };
+    auto eval_cost = [&](const double* q) {
+        double c = 0.0;
+        each([&](double X, double Y) { rob_cost_term(X, Y, q, c, L); });
+        disp_reduce<1>(&c, part, tot, l);
+        return c;
+    };
+
+    const long long o = (long long)b * ntiles + p;
+    const double qnan = __longlong_as_double(0x7FF8000000000000LL);
+    double used = (double)ns;
+    if constexpr (MASK) {
+        used = 0.0;
+        each([&](double, double) { used = used + 1.0; });
+        disp_reduce<1>(&used, part, tot, l);
+        if (used < 4.0) {  // block-uniform: too few samples for the four coefficients
+            if (l == 0) {
+                for (int i = 0; i < 4; i++) {
+                    if (coeffs) coeffs[o * 4 + i] = __uint_as_float(0x7FC00000u);
+                    if (coeffs64) coeffs64[o * 4 + i] = qnan;
+                }
+                if (summary) {
+                    summary[o * 6 + 0] = qnan;
+                    summary[o * 6 + 1] = qnan;
+                    summary[o * 6 + 2] = 0.0;
+                    summary[o * 6 + 3] = (double)kTermFailure;
+                    summary[o * 6 + 4] = used;
+                    summary[o * 6 + 5] = 0.0;
+                }
+            }
+            return;
+        }
+    }
+
+    // Ceres 1.13 trust-region LM, the control flow of k_register_disp for four parameter blocks:
+    // DENSE_SCHUR eliminates a, the reduced system is the 3x3 one of lm_moments in (b, c, d).
+    // Every lane holds the same sums, hence the same state: all exits below are block-uniform.
+    double x[4] = {1.0, 1.0, 1.0, 1.0}, best[4] = {1.0, 1.0, 1.0, 1.0};  // Depth.cpp:1270-1274
+    double S[kRobSums], sc[4], Ms[4][4], g[4], gs[4], diag[4] = {0, 0, 0, 0}, D[4], step[4],
+        cand[4];
+    auto take = [&]() {  // g and the scaled J'J from the sums of a Jacobian evaluation
+        const double M[4][4] = {{S[5], S[6], S[7], S[8]}, {S[6], S[9], S[10], S[11]},
+                                {S[7], S[10], S[12], S[13]}, {S[8], S[11], S[13], S[14]}};
+        for (int i = 0; i < 4; i++) {
+            g[i] = S[1 + i];
+            for (int j = 0; j < 4; j++) Ms[i][j] = (M[i][j] * sc[i]) * sc[j];
+        }
+    };
+    eval_full(x, S);
+    sc[0] = 1.0 / (1.0 + sqrt(S[5]));  // Jacobi scaling, fixed at iteration 0
+    sc[1] = 1.0 / (1.0 + sqrt(S[9]));
+    sc[2] = 1.0 / (1.0 + sqrt(S[12]));
+    sc[3] = 1.0 / (1.0 + sqrt(S[14]));
+    take();
+    double x_cost = S[0];
+    const double initial_cost = x_cost;
+    double radius = kLmInitRadius, decrease = 2.0, x_norm = -1.0, min_cost = DBL_MAX;
+    bool reuse_diag = false, successful = true;
+    int invalid_run = 0, iteration = 0, term = kTermNoConvergence;
+    for (;;) {
+        if (successful && x_cost < min_cost) {
+            min_cost = x_cost;
+            for (int k = 0; k < 4; k++) best[k] = x[k];
+        }
+        if (iteration >= kLmMaxIter) { term = kTermNoConvergence; break; }
+        if (successful) {
+            double gmax = 0.0;
+            for (int k = 0; k < 4; k++) {
+                const double d = fabs(x[k] - (x[k] + -g[k]));
+                if (d > gmax) gmax = d;
+            }
+            if (gmax <= kLmGradTol) { term = kTermGradientTol; break; }
+        }
+        if (radius <= kLmMinRadius) { term = kTermMinRadius; break; }
+        iteration++;
+        if (!reuse_diag)
+            for (int k = 0; k < 4; k++) {
+                const double d = Ms[k][k] > kLmMinDiag ? Ms[k][k] : kLmMinDiag;
+                diag[k] = d < kLmMaxDiag ? d : kLmMaxDiag;
+            }
+        for (int k = 0; k < 4; k++) D[k] = sqrt(diag[k] / radius);
+        for (int k = 0; k < 4; k++) gs[k] = sc[k] * g[k];
+        const double ete = D[0] * D[0] + Ms[0][0];
+        double R[3][3], rhs[3], z[3];
+        for (int a = 0; a < 3; a++)
+            for (int c = a; c < 3; c++)
+                R[a][c] = Ms[1 + a][1 + c] + (a == c ? D[1 + a] * D[1 + a] : 0.0);
+        const double inv = inv_psd1(ete);
+        const double inv_g = inv * gs[0];
+        for (int a = 0; a < 3; a++) rhs[a] = gs[1 + a] - Ms[0][1 + a] * inv_g;
+        for (int a = 0; a < 3; a++) {
+            const double bt = Ms[0][1 + a] * inv;
+            for (int c = a; c < 3; c++) R[a][c] = R[a][c] - bt * Ms[0][1 + c];
+        }
+        bool ok = llt3_solve(R, rhs, z);
+        if (ok) {
+            double ya = gs[0];
+            for (int a = 0; a < 3; a++) ya = ya - Ms[0][1 + a] * z[a];
+            step[0] = inv * ya;
+            step[1] = z[0];
+            step[2] = z[1];
+            step[3] = z[2];
+            for (int k = 0; ok && k < 4; k++) ok = isfinite(step[k]);
+        }
+        reuse_diag = true;
+        double mcc = 0.0, cand_cost = 0.0;
+        bool valid = false;
+        if (ok) {
+            for (int k = 0; k < 4; k++) step[k] = step[k] * -1.0;
+            double sJr = 0.0, sMs = 0.0;
+            for (int i = 0; i < 4; i++) {
+                double q = 0.0;
+                for (int j = 0; j < 4; j++) q = q + Ms[i][j] * step[j];
+                sMs = sMs + step[i] * q;
+                sJr = sJr + step[i] * gs[i];
+            }
+            mcc = -(sJr + sMs / 2.0);
+            valid = mcc > 0.0;
+        }
+        if (valid) {
+            for (int k = 0; k < 4; k++) cand[k] = x[k] + step[k] * sc[k];
+            cand_cost = eval_cost(cand);
+            // a trial whose cost is not finite is a failed evaluation: an invalid step
+            valid = isfinite(cand_cost);
+        }
+        if (!valid) {
+            if (++invalid_run >= kLmMaxInvalid) { term = kTermFailure; break; }
+            radius = radius / decrease;
+            decrease *= 2.0;
+            successful = false;
+            continue;
+        }
+        invalid_run = 0;
+        double dx[4];
+        for (int k = 0; k < 4; k++) dx[k] = x[k] - cand[k];
+        if (norm4(dx) <= kLmParamTol * (x_norm + kLmParamTol)) { term = kTermParameterTol; break; }
+        if (fabs(x_cost - cand_cost) <= kLmFuncTol * x_cost) { term = kTermFunctionTol; break; }
+        const double rel = (x_cost - cand_cost) / mcc;
+        if (rel > kLmMinRelDecrease) {
+            for (int k = 0; k < 4; k++) x[k] = cand[k];
+            x_norm = norm4(x);
+            eval_full(x, S);
+            take();
+            x_cost = S[0];
+            const double q = 2.0 * rel - 1.0;
+            const double f = 1.0 - q * q * q;
+            radius = radius / (f > 1.0 / 3.0 ? f : 1.0 / 3.0);
+            radius = radius < kLmMaxRadius ? radius : kLmMaxRadius;
+            decrease = 2.0;
+            reuse_diag = false;
+            successful = true;
+        } else {
+            radius = radius / decrease;
+            decrease *= 2.0;
+            successful = false;
+        }
+    }
+
+    // one more pass at the returned parameters: the samples with r r <= a a (exact counts)
+    double inliers = 0.0;
+    each([&](double X, double Y) {
+        double X2, X3;
+        const double r = cubic_residual(X, Y, best, X2, X3);
+        if (r * r <= L.b) inliers = inliers + 1.0;
+    });
+    disp_reduce<1>(&inliers, part, tot, l);
+    if (l == 0) {
+        bool finite = true;
+        for (int i = 0; i < 4; i++) finite = finite && isfinite(best[i]);
+        if (!finite) term = kTermFailure;
+        for (int i = 0; i < 4; i++) {
+            if (coeffs)  // Vec4f(vars), Depth.cpp:1408
+                coeffs[o * 4 + i] = finite ? (float)best[i] : __uint_as_float(0x7FC00000u);
+            if (coeffs64) coeffs64[o * 4 + i] = finite ? best[i] : qnan;
+        }
+        if (summary) {
+            summary[o * 6 + 0] = initial_cost;
+            summary[o * 6 + 1] = min_cost;
+            summary[o * 6 + 2] = (double)iteration;
+            summary[o * 6 + 3] = (double)term;
+            summary[o * 6 + 4] = used;
+            summary[o * 6 + 5] = inliers;
+        }
+    }
+}
+
+void launch_register_robust(hipStream_t s, const TileGeom* geom, const RegGrid* grids, int ntiles,
+                            const float* emap, long long estride, const float* tiles,
+                            long long tstride, const int2* sidx, float* coeffs, double* coeffs64,
+                            double* summary, int batch, int loss_kind, double loss_a, TileValid tv)
+{
+    const dim3 grid((unsigned)(ntiles * batch)), block(kDispLanes);
+    const RegLoss L = make_loss(loss_kind, loss_a);
+    if (tv.on)
+        hipLaunchKernelGGL(k_register_robust<true>, grid, block, 0, s, geom, grids, ntiles, emap,
+                           estride, tiles, tstride, sidx, coeffs, coeffs64, summary, L, tv.lo,
+                           tv.hi);
+    else
+        hipLaunchKernelGGL(k_register_robust<false>, grid, block, 0, s, geom, grids, ntiles, emap,
+                           estride, tiles, tstride, sidx, coeffs, coeffs64, summary, L, 0.0f,
+                           0.0f);
+}
+
+}  // namespace pf

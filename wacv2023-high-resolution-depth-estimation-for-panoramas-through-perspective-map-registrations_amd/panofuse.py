@@ -37,7 +37,7 @@ EXPORTS = [
     "pf_disparity_transform", "pf_merge_disparity", "pf_register_global",
     "pf_result_transform", "pf_median_scale", "pf_copy_invalid", "pf_layout_audit",
     "pf_stitch", "pf_laplacian_residual", "pf_fuse_check", "pf_set_tile_validity",
-    "pf_tile_valid_counts",
+    "pf_tile_valid_counts", "pf_set_register_loss", "pf_register_ex",
 ]
 NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
           "pf_debug_smooth_fault", "pf_fuse_partial_rows", "pf_fuse_coverage_rows",
@@ -46,6 +46,7 @@ NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
 METRICS_ORDERS = {"tree": 0, "sequential": 1}  # PF_METRICS_*; "sequential" = the reference's
 SOLVERS = {"normal": 0, "lm": 1}  # PF_SOLVER_*; "lm" = the reference's Ceres LM (default)
 PF_VALID_ALL, PF_VALID_RANGE = 0, 1  # pf_set_tile_validity's modes
+LOSSES = {None: 0, "none": 0, "huber": 1, "softl1": 2}  # PF_LOSS_* of pf_set_register_loss
 
 STAGES = ["warp", "register", "seed", "targets", "jacobi", "quantize", "metrics"]
 
@@ -131,6 +132,8 @@ def load():
     L.pf_set_solver.argtypes = [vp, ip]
     L.pf_set_tile_validity.argtypes = [vp, ip, fp, fp]
     L.pf_tile_valid_counts.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, vp]
+    L.pf_set_register_loss.argtypes = [vp, ip, C.c_double]
+    L.pf_register_ex.argtypes = [vp, vp, ip, ip, ip, vp, ip, fp, fp, ip, ip, vp, vp, vp]
     L.pf_fuse_normalize.argtypes = [vp, vp, vp, ip, ip, fp, fp, ip, vp]
     L.pf_fuse_multicover.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, ip, vp,
                                      C.POINTER(C.c_int)]
@@ -298,9 +301,35 @@ class Fuser:
                                                 float(zr[0]), float(zr[1]), _ptr(counts)))
         return counts
 
-    def register(self, emap, tiles, zr, degree=3, apply=True, coeffs=None, coeffs64=None):
+    def set_register_loss(self, kind=None, a=0.0):
+        """The robust loss of the tile registrations (pf_set_register_loss): None / "none" (least
+        squares, the default), "huber" or "softl1" with Ceres' scale a > 0.  With a loss set,
+        register / merge fit the cubic sample-wise under it (degree 3, the "lm" solver),
+        register_disparity / merge_disparity their model; register_joint and register_global
+        raise PF_ESTATE."""
+        if kind not in LOSSES:
+            raise ValueError(f"unknown loss {kind!r}: one of {sorted(k for k in LOSSES if k)}")
+        self._check(self.L.pf_set_register_loss(self.h, LOSSES[kind], float(a)))
+        self._loss = LOSSES[kind]
+
+    def _summary_ptr(self, summary, B, width):
+        if summary is not None and summary.numel() != B * self.layout.ntiles * width:
+            raise ValueError(f"summary holds {summary.numel()} values, not [B, ntiles, {width}]")
+        return _ptr(summary)
+
+    def register(self, emap, tiles, zr, degree=3, apply=True, coeffs=None, coeffs64=None,
+                 summary=None):
+        """pf_register; summary (pf_register_ex, only while a loss is set): float64
+        [B, ntiles, 6] device tensor of {initial cost, final cost, iterations, termination code,
+        samples used, inliers}.  No sync."""
         ew, eh, ec = _emap_dims(emap)
         B = emap.shape[0]
+        if summary is not None:
+            self._check(self.L.pf_register_ex(self.h, _ptr(emap), ew, eh, ec, _ptr(tiles), B,
+                                              float(zr[0]), float(zr[1]), degree,
+                                              1 if apply else 0, _ptr(coeffs), _ptr(coeffs64),
+                                              self._summary_ptr(summary, B, 6)))
+            return
         self._check(self.L.pf_register(self.h, _ptr(emap), ew, eh, ec, _ptr(tiles), B,
                                        float(zr[0]), float(zr[1]), degree, 1 if apply else 0,
                                        _ptr(coeffs), _ptr(coeffs64)))
@@ -324,12 +353,16 @@ class Fuser:
         """The disparity-tile registration (pf_register_disparity): y = 1/(a x + b) + d fitted per
         tile by the reference's LM, abcd = (a, b, 1, d).  coeffs: float32 [B, ntiles, 4], coeffs64 /
         summary: float64 [B, ntiles, 4] device tensors (summary = initial cost, final cost,
-        iterations, termination code); apply runs D2DTransform on the tiles.  No sync."""
+        iterations, termination code); apply runs D2DTransform on the tiles.  While a loss is set
+        (set_register_loss) the fit runs under it and summary is [B, ntiles, 6], as register's.
+        No sync."""
         ew, eh, ec = _emap_dims(emap)
         B = emap.shape[0]
+        width = 6 if getattr(self, "_loss", 0) else 4
         self._check(self.L.pf_register_disparity(self.h, _ptr(emap), ew, eh, ec, _ptr(tiles), B,
                                                  float(zr[0]), float(zr[1]), 1 if apply else 0,
-                                                 _ptr(coeffs), _ptr(coeffs64), _ptr(summary)))
+                                                 _ptr(coeffs), _ptr(coeffs64),
+                                                 self._summary_ptr(summary, B, width)))
 
     def disparity_transform(self, t, abcd, channels=1):
         """D2DTransform (Depth.cpp:214-243) in place on a float32 device tensor: channel 0 of its
