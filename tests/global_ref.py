@@ -7,24 +7,18 @@ sums are taken in their documented order (chunks of 16,384 consecutive samples; 
 of 256 adds its samples l, l + 256, ... in order from 0.0, then the halving tree
 p[l] = p[l] + p[l + stride] for stride 128 ... 1; the chunk partials are added in chunk order
 from 0.0) with elementwise numpy operations and explicit ordered adds, and the moment-form LM
-(lm_moments of csrc/pf_kernels.hip) runs on Python floats from a start point.  Every operation is
+(lm_moments of csrc/pf_register.hip, over lm_ref.solve) runs on Python floats from a start point.  Every operation is
 an IEEE-754 fp64 + - * / or sqrt, correctly rounded on both sides, so the two agree bit for bit.
 """
 import math
 
 import numpy as np
 
+import lm_ref
+
 MYPI = 3.14159265359  # Basic.h:11
 LANES = 256
 CHUNK = 16384
-MAX_ITER = 50
-INIT_RADIUS, MAX_RADIUS, MIN_RADIUS = 1e4, 1e16, 1e-32
-MIN_REL_DECREASE, MIN_DIAG, MAX_DIAG = 1e-3, 1e-6, 1e32
-MAX_INVALID = 5
-FUNC_TOL, GRAD_TOL, PARAM_TOL = 1e-6, 1e-10, 1e-8
-DBL_MAX = float(np.finfo(np.float64).max)
-TERMINATION = ("no_convergence", "function_tolerance", "parameter_tolerance",
-               "gradient_tolerance", "min_trust_region_radius", "failure")
 START_GLOBAL = (0.0, 0.0, 1.0, 0.0)  # Depth.cpp:1169-1173
 START_TILE = (1.0, 1.0, 1.0, 1.0)    # Depth.cpp:1270-1274
 
@@ -142,168 +136,16 @@ def _mom_gradient(M, Jy, p):
     return g
 
 
-def _inv_psd1(v):
-    l = math.sqrt(v)
-    return (1.0 / l) / l
-
-
-def _llt3_solve(S, rhs):
-    L = [[0.0] * 3 for _ in range(3)]
-    for k in range(3):
-        x = S[k][k]
-        if k > 0:
-            sq = 0.0
-            for i in range(k):
-                sq = sq + L[k][i] * L[k][i]
-            x = x - sq
-        if not x > 0.0:
-            return None
-        x = math.sqrt(x)
-        L[k][k] = x
-        for j in range(k + 1, 3):
-            a = S[k][j]
-            for i in range(k):
-                a = a - L[j][i] * L[k][i]
-            L[j][k] = a / x
-    y = list(rhs)
-    for k in range(3):
-        y[k] = y[k] / L[k][k]
-        for j in range(k + 1, 3):
-            y[j] = y[j] - L[j][k] * y[k]
-    for k in (2, 1, 0):
-        y[k] = y[k] / L[k][k]
-        for j in range(k):
-            y[j] = y[j] - L[k][j] * y[k]
-    return y
-
-
-def _norm4(v):
-    return math.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3])
-
-
-def _sqrt(v):
-    return math.sqrt(v) if v >= 0.0 else float("nan")
-
-
 def lm_moments(S, start=START_GLOBAL):
-    """Ceres 1.13 trust-region LM (DENSE_SCHUR, default options) on the 15 sums from `start`.
+    """Ceres 1.13 trust-region LM (lm_ref.solve) on the 15 sums from `start`.
     Returns (coef64[4], summary dict)."""
     S = [float(v) for v in S]
     M = [[S[_IDX[i][j]] for j in range(4)] for i in range(4)]
     Jy = [S[10 + i] for i in range(4)]
     yy = S[14]
-    x = [float(v) for v in start]
-    best = list(x)
-    sc = [1.0 / (1.0 + _sqrt(M[k][k])) for k in range(4)]
-    Ms = [[(M[i][j] * sc[i]) * sc[j] for j in range(4)] for i in range(4)]
-    radius, decrease, x_norm = INIT_RADIUS, 2.0, -1.0
-    reuse_diag, successful = False, True
-    invalid_run, iteration, term = 0, 0, 0
-    diag = [0.0] * 4
-    x_cost = _mom_cost(M, Jy, yy, x)
-    g = _mom_gradient(M, Jy, x)
-    initial_cost = x_cost
-    min_cost = DBL_MAX
-    while True:
-        if successful and x_cost < min_cost:
-            min_cost = x_cost
-            best = list(x)
-        if iteration >= MAX_ITER:
-            term = 0
-            break
-        if successful:
-            gmax = 0.0
-            for k in range(4):
-                d = abs(x[k] - (x[k] + -g[k]))
-                if d > gmax:
-                    gmax = d
-            if gmax <= GRAD_TOL:
-                term = 3
-                break
-        if radius <= MIN_RADIUS:
-            term = 4
-            break
-        iteration += 1
-        if not reuse_diag:
-            for k in range(4):
-                d = Ms[k][k] if Ms[k][k] > MIN_DIAG else MIN_DIAG
-                diag[k] = d if d < MAX_DIAG else MAX_DIAG
-        D = [math.sqrt(diag[k] / radius) for k in range(4)]
-        gs = [sc[k] * g[k] for k in range(4)]
-        ete = D[0] * D[0] + Ms[0][0]
-        R = [[0.0] * 3 for _ in range(3)]
-        for a in range(3):
-            for b in range(a, 3):
-                R[a][b] = Ms[1 + a][1 + b] + (D[1 + a] * D[1 + a] if a == b else 0.0)
-        inv = _inv_psd1(ete)
-        inv_g = inv * gs[0]
-        rhs = [gs[1 + a] - Ms[0][1 + a] * inv_g for a in range(3)]
-        for a in range(3):
-            bt = Ms[0][1 + a] * inv
-            for b in range(a, 3):
-                R[a][b] = R[a][b] - bt * Ms[0][1 + b]
-        z = _llt3_solve(R, rhs)
-        ok = z is not None
-        step = [0.0] * 4
-        if ok:
-            ya = gs[0]
-            for a in range(3):
-                ya = ya - Ms[0][1 + a] * z[a]
-            step = [inv * ya, z[0], z[1], z[2]]
-            ok = all(math.isfinite(v) for v in step)
-        reuse_diag = True
-        mcc, valid = 0.0, False
-        if ok:
-            step = [v * -1.0 for v in step]
-            sJr, sMs = 0.0, 0.0
-            for i in range(4):
-                q = 0.0
-                for j in range(4):
-                    q = q + Ms[i][j] * step[j]
-                sMs = sMs + step[i] * q
-                sJr = sJr + step[i] * gs[i]
-            mcc = -(sJr + sMs / 2.0)
-            valid = mcc > 0.0
-        if not valid:
-            invalid_run += 1
-            if invalid_run >= MAX_INVALID:
-                term = 5
-                break
-            radius = radius / decrease
-            decrease *= 2.0
-            successful = False
-            continue
-        invalid_run = 0
-        cand = [x[k] + step[k] * sc[k] for k in range(4)]
-        cand_cost = _mom_cost(M, Jy, yy, cand)
-        if not math.isfinite(cand_cost):
-            cand_cost = DBL_MAX
-        dx = [x[k] - cand[k] for k in range(4)]
-        if _norm4(dx) <= PARAM_TOL * (x_norm + PARAM_TOL):
-            term = 2
-            break
-        if abs(x_cost - cand_cost) <= FUNC_TOL * x_cost:
-            term = 1
-            break
-        rel = (x_cost - cand_cost) / mcc
-        if rel > MIN_REL_DECREASE:
-            x = list(cand)
-            x_norm = _norm4(x)
-            x_cost = _mom_cost(M, Jy, yy, x)
-            g = _mom_gradient(M, Jy, x)
-            q = 2.0 * rel - 1.0
-            f = 1.0 - q * q * q
-            radius = radius / (f if f > 1.0 / 3.0 else 1.0 / 3.0)
-            radius = radius if radius < MAX_RADIUS else MAX_RADIUS
-            decrease = 2.0
-            reuse_diag = False
-            successful = True
-        else:
-            radius = radius / decrease
-            decrease *= 2.0
-            successful = False
-    summary = {"initial_cost": initial_cost, "final_cost": min_cost, "iterations": iteration,
-               "termination": TERMINATION[term], "termination_code": term}
+    best, summary = lm_ref.solve(
+        start, lambda p: (_mom_cost(M, Jy, yy, p), _mom_gradient(M, Jy, p), M),
+        lambda p: _mom_cost(M, Jy, yy, p), False)
     return np.array(best, np.float64), summary
 
 

@@ -4,7 +4,8 @@ y = a x^3 + b x^2 + c x + d, or of y = 1/(a x + b) + d, under HuberLoss or SoftL
 
 TEST INFRASTRUCTURE ONLY.  The fit follows the kernels operation for operation: every sum is taken
 by disp_ref.ordered_sum (lane l of 256 adds samples l, l + 256, ... in order from 0.0, then the
-halving tree) over elementwise numpy fp64 terms, and the scalar LM algebra runs on Python floats.
+halving tree) over elementwise numpy fp64 terms, and the scalar LM algebra (lm_ref.solve) runs on
+Python floats.
 Every operation is an IEEE-754 fp64 + - * / or sqrt, correctly rounded on both sides, so the two
 agree bit for bit.
 
@@ -25,8 +26,8 @@ import math
 import numpy as np
 
 import disp_ref as DR
-from disp_ref import (DBL_MAX, FUNC_TOL, GRAD_TOL, INIT_RADIUS, MAX_DIAG, MAX_INVALID, MAX_ITER,
-                      MAX_RADIUS, MIN_DIAG, MIN_RADIUS, MIN_REL_DECREASE, PARAM_TOL, TERMINATION)
+import lm_ref
+from lm_ref import TERMINATION
 
 DBL_MIN = float(np.finfo(np.float64).tiny)
 LOSS_KINDS = (None, "huber", "softl1")
@@ -101,56 +102,11 @@ def cost(xs, ys, p, kind, a, model, valid=None, ordered_sum=None):
         return ordered_sum(_masked(0.5 * rho0, valid))
 
 
-def _inv_psd1(v):
-    l = math.sqrt(v)
-    return (1.0 / l) / l
-
-
-def _llt_solve(S, rhs):
-    """Eigen LLT<Upper> of the reduced Schur system and its two triangular solves: llt3_solve's
-    loops for any size (llt2_solve is the same operations for n = 2)."""
-    n = len(rhs)
-    L = [[0.0] * n for _ in range(n)]
-    for k in range(n):
-        x = S[k][k]
-        if k > 0:
-            sq = 0.0
-            for i in range(k):
-                sq = sq + L[k][i] * L[k][i]
-            x = x - sq
-        if not x > 0.0:
-            return None
-        x = math.sqrt(x)
-        L[k][k] = x
-        for j in range(k + 1, n):
-            v = S[k][j]
-            for i in range(k):
-                v = v - L[j][i] * L[k][i]
-            L[j][k] = v / x
-    y = list(rhs)
-    for k in range(n):
-        y[k] = y[k] / L[k][k]
-        for j in range(k + 1, n):
-            y[j] = y[j] - L[j][k] * y[k]
-    for k in range(n - 1, -1, -1):
-        y[k] = y[k] / L[k][k]
-        for j in range(k):
-            y[j] = y[j] - L[k][j] * y[k]
-    return y
-
-
-def _norm(v):
-    s = v[0] * v[0]
-    for k in range(1, len(v)):
-        s = s + v[k] * v[k]
-    return math.sqrt(s)
-
-
 def fit(xs, ys, kind, a=0.0, model="cubic", valid=None, trace=None, ordered_sum=None):
     """The LM fit on already clamped samples under the loss (kind None: plain least squares in the
     same sample-wise form).  valid: bool [ns] or None, the samples the validity rule keeps.
     Returns (coef64[4], summary dict); the disparity model's coefficients are (a, b, 1, d).
-    trace (optional list) receives (iteration, cost at its start, outcome) per iteration."""
+    trace (optional list) receives lm_ref.solve's record of every iteration."""
     xs = np.ascontiguousarray(xs, np.float64)
     ys = np.ascontiguousarray(ys, np.float64)
     n = MODELS[model]
@@ -165,142 +121,10 @@ def fit(xs, ys, kind, a=0.0, model="cubic", valid=None, trace=None, ordered_sum=
         return nan4, {"initial_cost": math.nan, "final_cost": math.nan, "iterations": 0,
                       "termination_code": 5, "termination": TERMINATION[5], "used": used,
                       "inliers": 0}
-    diag_at = []  # index of M[k][k] among the sums
-    at = 1 + n
-    for i in range(n):
-        diag_at.append(at)
-        at += n - i
-
-    def take(S):
-        M = [[0.0] * n for _ in range(n)]
-        at = 1 + n
-        for i in range(n):
-            for j in range(i, n):
-                M[i][j] = M[j][i] = S[at]
-                at += 1
-        g = [S[1 + i] for i in range(n)]
-        Ms = [[(M[i][j] * sc[i]) * sc[j] for j in range(n)] for i in range(n)]
-        return g, Ms
-
-    x = [1.0] * n
-    best = [1.0] * n
-    S = sums(xs, ys, x, kind, a, model, valid, ordered_sum)
-    sc = [1.0 / (1.0 + math.sqrt(S[k])) for k in diag_at]
-    g, Ms = take(S)
-    x_cost = S[0]
-    initial_cost = x_cost
-    radius, decrease, x_norm, min_cost = INIT_RADIUS, 2.0, -1.0, DBL_MAX
-    reuse_diag, successful = False, True
-    invalid_run, iteration, term = 0, 0, 0
-    diag = [0.0] * n
-    m = n - 1
-    while True:
-        if successful and x_cost < min_cost:
-            min_cost = x_cost
-            best = list(x)
-        if iteration >= MAX_ITER:
-            term = 0
-            break
-        if successful:
-            gmax = 0.0
-            for k in range(n):
-                d = abs(x[k] - (x[k] + -g[k]))
-                if d > gmax:
-                    gmax = d
-            if gmax <= GRAD_TOL:
-                term = 3
-                break
-        if radius <= MIN_RADIUS:
-            term = 4
-            break
-        iteration += 1
-        rec = [iteration, x_cost, None]
-        if trace is not None:
-            trace.append(rec)
-        if not reuse_diag:
-            for k in range(n):
-                d = Ms[k][k] if Ms[k][k] > MIN_DIAG else MIN_DIAG
-                diag[k] = d if d < MAX_DIAG else MAX_DIAG
-        D = [math.sqrt(diag[k] / radius) for k in range(n)]
-        gs = [sc[k] * g[k] for k in range(n)]
-        ete = D[0] * D[0] + Ms[0][0]
-        R = [[0.0] * m for _ in range(m)]
-        for i in range(m):
-            for c in range(i, m):
-                R[i][c] = Ms[1 + i][1 + c] + (D[1 + i] * D[1 + i] if i == c else 0.0)
-        inv = _inv_psd1(ete)
-        inv_g = inv * gs[0]
-        rhs = [gs[1 + i] - Ms[0][1 + i] * inv_g for i in range(m)]
-        for i in range(m):
-            bt = Ms[0][1 + i] * inv
-            for c in range(i, m):
-                R[i][c] = R[i][c] - bt * Ms[0][1 + c]
-        z = _llt_solve(R, rhs)
-        ok = z is not None
-        step = [0.0] * n
-        if ok:
-            ya = gs[0]
-            for i in range(m):
-                ya = ya - Ms[0][1 + i] * z[i]
-            step = [inv * ya] + list(z)
-            ok = all(math.isfinite(v) for v in step)
-        reuse_diag = True
-        mcc, cand_cost, ok_step = 0.0, 0.0, False
-        if ok:
-            step = [v * -1.0 for v in step]
-            sJr, sMs = 0.0, 0.0
-            for i in range(n):
-                q = 0.0
-                for j in range(n):
-                    q = q + Ms[i][j] * step[j]
-                sMs = sMs + step[i] * q
-                sJr = sJr + step[i] * gs[i]
-            mcc = -(sJr + sMs / 2.0)
-            ok_step = mcc > 0.0
-        if ok_step:
-            cand = [x[k] + step[k] * sc[k] for k in range(n)]
-            cand_cost = cost(xs, ys, cand, kind, a, model, valid, ordered_sum)
-            ok_step = math.isfinite(cand_cost)  # a failed evaluation: an invalid step
-        if not ok_step:
-            rec[2] = "invalid"
-            invalid_run += 1
-            if invalid_run >= MAX_INVALID:
-                term = 5
-                break
-            radius = radius / decrease
-            decrease *= 2.0
-            successful = False
-            continue
-        invalid_run = 0
-        dx = [x[k] - cand[k] for k in range(n)]
-        if _norm(dx) <= PARAM_TOL * (x_norm + PARAM_TOL):
-            rec[2] = "parameter_tolerance"
-            term = 2
-            break
-        if abs(x_cost - cand_cost) <= FUNC_TOL * x_cost:
-            rec[2] = "function_tolerance"
-            term = 1
-            break
-        rel = (x_cost - cand_cost) / mcc
-        if rel > MIN_REL_DECREASE:
-            rec[2] = "accepted"
-            x = list(cand)
-            x_norm = _norm(x)
-            S = sums(xs, ys, x, kind, a, model, valid, ordered_sum)
-            g, Ms = take(S)
-            x_cost = S[0]
-            q = 2.0 * rel - 1.0
-            f = 1.0 - q * q * q
-            radius = radius / (f if f > 1.0 / 3.0 else 1.0 / 3.0)
-            radius = radius if radius < MAX_RADIUS else MAX_RADIUS
-            decrease = 2.0
-            reuse_diag = False
-            successful = True
-        else:
-            rec[2] = "rejected"
-            radius = radius / decrease
-            decrease *= 2.0
-            successful = False
+    best, summary = lm_ref.solve(
+        [1.0] * n,
+        lambda p: lm_ref.unpack_sums(sums(xs, ys, p, kind, a, model, valid, ordered_sum), n),
+        lambda p: cost(xs, ys, p, kind, a, model, valid, ordered_sum), True, trace)
     with np.errstate(all="ignore"):
         r, _ = residual_and_rows(xs, ys, best, model)
         inl = (r * r) <= a * a
@@ -309,12 +133,11 @@ def fit(xs, ys, kind, a=0.0, model="cubic", valid=None, trace=None, ordered_sum=
     if model == "cubic":
         coef = np.array(best, np.float64)
         if not all(math.isfinite(v) for v in best):  # k_register_robust's guard
-            coef, term = nan4, 5
+            coef = nan4
+            summary.update(termination_code=5, termination=TERMINATION[5])
     else:
         coef = np.array([best[0], best[1], 1.0, best[2]], np.float64)
-    summary = {"initial_cost": initial_cost, "final_cost": min_cost, "iterations": iteration,
-               "termination": TERMINATION[term], "termination_code": term, "used": used,
-               "inliers": int(np.count_nonzero(inl))}
+    summary.update(used=used, inliers=int(np.count_nonzero(inl)))
     return coef, summary
 
 

@@ -142,6 +142,53 @@ def test_grid_above_resident_capacity(fuser):
     assert np.array_equal(_bits(sm[0, 0]), _bits(rsum))
 
 
+STEP_TILE = 2
+
+
+def _step_inputs():
+    """C1's 6 tiles at 64^2 with the baseline under tile STEP_TILE's samples made a step of the
+    tile's own values, y = (x > 0.5): a fit the model cannot follow, so the LM rejects steps.  The
+    baseline element of each sample is read back from a baseline that holds its own element
+    numbers ((i + 1) / (n + 2): exact in fp32 and inside the sample clamp)."""
+    lay = PL.band_layout(3, 2, 64, 64, 10, 24, "C1:3x2@64")
+    tiles, emap, disp = _inputs(lay, 5)
+    n = emap.size
+    probe = ((np.arange(n, dtype=np.float64) + 1.0) / (n + 2)).astype(np.float32)
+    assert n + 2 < 2 ** 23 and probe[0] > 1e-4 and probe[-1] < 1 - 1e-4
+    xs, ys, _, _ = O.reg_samples(tiles[STEP_TILE], disp, probe.reshape(emap.shape), ZR)
+    at = np.rint(ys * (n + 2)).astype(np.int64) - 1
+    assert np.array_equal(probe[at].astype(np.float64), ys)
+    emap = emap.copy()
+    emap.reshape(-1)[at] = (xs > 0.5).astype(np.float32)  # samples that share an element: the last
+    return lay, tiles, emap, disp
+
+
+def test_rejected_steps_and_iteration_cap_bit_exact(fuser):
+    """A fit that runs through rejected steps to the iteration cap, which the C1 cases above do not
+    reach.  The restatement's own trace has to show both before the GPU is compared with it."""
+    lay, tiles, emap, disp = _step_inputs()
+    ref = []
+    for p, t in enumerate(tiles):
+        xs, ys, _, _ = O.reg_samples(t, disp, emap, ZR)
+        trace = []
+        c64, s = R.fit(xs, ys, trace=trace)
+        ref.append((c64, R.summary_row(s)))
+        outcomes = [r["outcome"] for r in trace]
+        print(f"tile {p}: {xs.size} samples, {s['termination']} after {s['iterations']}, "
+              f"{outcomes.count('rejected')} rejected, {outcomes.count('invalid')} invalid")
+        if p == STEP_TILE:
+            assert outcomes.count("rejected") >= 1
+            assert s["termination"] == "no_convergence" and s["iterations"] == R.MAX_ITER
+    cf, c64, sm, _ = _register(fuser, lay, [emap], [disp])
+    for p, (r64, rsum) in enumerate(ref):
+        print(f"tile {p}: gpu {c64[0, p]} ref {r64} summary {sm[0, p]} ref {rsum}")
+        assert np.array_equal(_bits(c64[0, p]), _bits(r64)), p
+        assert np.array_equal(_bits(cf[0, p]), _bits(r64.astype(np.float32))), p
+        assert np.array_equal(_bits(sm[0, p, :2]), _bits(rsum[:2])), p
+        assert sm[0, p, 2] == rsum[2] and sm[0, p, 3] == rsum[3], p
+        assert c64[0, p, 2] == 1.0
+
+
 def _same_with_nan(got, want):
     nan = np.isnan(want)
     return np.array_equal(np.isnan(got), nan) and np.array_equal(got[~nan], want[~nan])

@@ -124,8 +124,8 @@ def test_every_sum_goes_through_ordered_sum(model):
     calls.clear()
     trace = []
     _, s = R.fit(xs, ys, "huber", 0.02, model, trace=trace, ordered_sum=spy)
-    accepted = sum(t[2] == "accepted" for t in trace)
-    trials = sum(t[2] != "invalid" for t in trace)
+    accepted = sum(t["outcome"] == "accepted" for t in trace)
+    trials = sum(t["outcome"] != "invalid" for t in trace)
     assert len(calls) == nsums * (1 + accepted) + trials
 
 

@@ -1,6 +1,6 @@
 // pf_disp.hip -- disparity-tile registration: the per-tile fit of y = 1/(a x + b) + d
 // (FunctorDisparity2Depth, Depth.cpp:1044-1073) by the reference's Ceres 1.13 trust-region
-// Levenberg-Marquardt, and PerspectiveMap::D2DTransform (Depth.cpp:214-243).
+// Levenberg-Marquardt (lm_solve, pf_lm.hpp), and PerspectiveMap::D2DTransform (Depth.cpp:214-243).
 //
 // The cubic of k_register is linear in its coefficients, so its LM runs on 15 moment sums.  This
 // model is not: every LM evaluation is a pass over the tile's samples.  One 256-lane workgroup
@@ -74,30 +74,6 @@ __device__ __forceinline__ void disp_cost_term(double X, double Y, const double 
     }
     acc = acc + 0.5 * (r * r);
 }
-
-__device__ __forceinline__ bool llt2_solve(const double S[2][2], const double rhs[2], double z[2])
-{  // Eigen LLT<Upper> of the 2x2 reduced Schur system, llt3_solve's loops for n = 2
-    if (!(S[0][0] > 0.0)) return false;
-    const double l00 = sqrt(S[0][0]);
-    const double l10 = S[0][1] / l00;
-    const double x = S[1][1] - l10 * l10;
-    if (!(x > 0.0)) return false;
-    const double l11 = sqrt(x);
-    double y0 = rhs[0] / l00;
-    double y1 = rhs[1] - l10 * y0;
-    y1 = y1 / l11;
-    y1 = y1 / l11;
-    y0 = y0 - l10 * y1;
-    y0 = y0 / l00;
-    z[0] = y0;
-    z[1] = y1;
-    return true;
-}
-
-__device__ __forceinline__ double norm3(const double v[3])
-{
-    return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-}
 }  // namespace
 
 // One block's fit of tile p of panorama b.  LOSS: under the robust loss L, with the 6-entry
@@ -133,7 +109,8 @@ __device__ __forceinline__ void register_disp_tile(
         }
     }
 
-    auto eval_full = [&](const double* q, double* S) {
+    auto eval_full = [&](const double (&q)[3], double& cost, double (&g)[3], double (&M)[3][3]) {
+        double S[kDispSums];
 #pragma unroll
         for (int k = 0; k < kDispSums; k++) S[k] = 0.0;
 #pragma unroll
@@ -147,8 +124,16 @@ __device__ __forceinline__ void register_disp_tile(
                              S, L);
         }
         disp_reduce<kDispSums>(S, part, tot, l);
+        cost = S[0];
+        for (int i = 0; i < 3; i++) g[i] = S[1 + i];
+        M[0][0] = S[4];
+        M[0][1] = M[1][0] = S[5];
+        M[0][2] = M[2][0] = S[6];
+        M[1][1] = S[7];
+        M[1][2] = M[2][1] = S[8];
+        M[2][2] = S[9];
     };
-    auto eval_cost = [&](const double* q) {
+    auto eval_cost = [&](const double (&q)[3]) {
         double c = 0.0;
 #pragma unroll
         for (int u = 0; u < kDispPerLane; u++)
@@ -164,125 +149,12 @@ __device__ __forceinline__ void register_disp_tile(
         return c;
     };
 
-    // Ceres 1.13 trust-region LM, the control flow of lm_moments (pf_kernels.hip) for three
-    // parameter blocks: DENSE_SCHUR eliminates a, the reduced system is 2x2 in (b, d).  Every lane
-    // holds the same sums, hence the same state: all exits below are block-uniform.
-    double x[3] = {1.0, 1.0, 1.0}, best[3] = {1.0, 1.0, 1.0};  // Depth.cpp:1270-1274
-    double S[kDispSums], sc[3], Ms[3][3], g[3], gs[3], diag[3] = {0, 0, 0}, D[3], step[3], cand[3];
-    auto take = [&]() {  // g and the scaled J'J from the sums of a Jacobian evaluation
-        const double M[3][3] = {{S[4], S[5], S[6]}, {S[5], S[7], S[8]}, {S[6], S[8], S[9]}};
-        for (int i = 0; i < 3; i++) {
-            g[i] = S[1 + i];
-            for (int j = 0; j < 3; j++) Ms[i][j] = (M[i][j] * sc[i]) * sc[j];
-        }
-    };
-    eval_full(x, S);
-    sc[0] = 1.0 / (1.0 + sqrt(S[4]));  // Jacobi scaling, fixed at iteration 0
-    sc[1] = 1.0 / (1.0 + sqrt(S[7]));
-    sc[2] = 1.0 / (1.0 + sqrt(S[9]));
-    take();
-    double x_cost = S[0];
-    const double initial_cost = x_cost;
-    double radius = kLmInitRadius, decrease = 2.0, x_norm = -1.0, min_cost = DBL_MAX;
-    bool reuse_diag = false, successful = true;
-    int invalid_run = 0, iteration = 0, term = kTermNoConvergence;
-    for (;;) {
-        if (successful && x_cost < min_cost) {
-            min_cost = x_cost;
-            for (int k = 0; k < 3; k++) best[k] = x[k];
-        }
-        if (iteration >= kLmMaxIter) { term = kTermNoConvergence; break; }
-        if (successful) {
-            double gmax = 0.0;
-            for (int k = 0; k < 3; k++) {
-                const double d = fabs(x[k] - (x[k] + -g[k]));
-                if (d > gmax) gmax = d;
-            }
-            if (gmax <= kLmGradTol) { term = kTermGradientTol; break; }
-        }
-        if (radius <= kLmMinRadius) { term = kTermMinRadius; break; }
-        iteration++;
-        if (!reuse_diag)
-            for (int k = 0; k < 3; k++) {
-                const double d = Ms[k][k] > kLmMinDiag ? Ms[k][k] : kLmMinDiag;
-                diag[k] = d < kLmMaxDiag ? d : kLmMaxDiag;
-            }
-        for (int k = 0; k < 3; k++) D[k] = sqrt(diag[k] / radius);
-        for (int k = 0; k < 3; k++) gs[k] = sc[k] * g[k];
-        const double ete = D[0] * D[0] + Ms[0][0];
-        double R[2][2], rhs[2], z[2];
-        for (int a = 0; a < 2; a++)
-            for (int c = a; c < 2; c++)
-                R[a][c] = Ms[1 + a][1 + c] + (a == c ? D[1 + a] * D[1 + a] : 0.0);
-        const double inv = inv_psd1(ete);
-        const double inv_g = inv * gs[0];
-        for (int a = 0; a < 2; a++) rhs[a] = gs[1 + a] - Ms[0][1 + a] * inv_g;
-        for (int a = 0; a < 2; a++) {
-            const double bt = Ms[0][1 + a] * inv;
-            for (int c = a; c < 2; c++) R[a][c] = R[a][c] - bt * Ms[0][1 + c];
-        }
-        bool ok = llt2_solve(R, rhs, z);
-        if (ok) {
-            double ya = gs[0];
-            for (int a = 0; a < 2; a++) ya = ya - Ms[0][1 + a] * z[a];
-            step[0] = inv * ya;
-            step[1] = z[0];
-            step[2] = z[1];
-            for (int k = 0; ok && k < 3; k++) ok = isfinite(step[k]);
-        }
-        reuse_diag = true;
-        double mcc = 0.0, cand_cost = 0.0;
-        bool valid = false;
-        if (ok) {
-            for (int k = 0; k < 3; k++) step[k] = step[k] * -1.0;
-            double sJr = 0.0, sMs = 0.0;
-            for (int i = 0; i < 3; i++) {
-                double q = 0.0;
-                for (int j = 0; j < 3; j++) q = q + Ms[i][j] * step[j];
-                sMs = sMs + step[i] * q;
-                sJr = sJr + step[i] * gs[i];
-            }
-            mcc = -(sJr + sMs / 2.0);
-            valid = mcc > 0.0;
-        }
-        if (valid) {
-            for (int k = 0; k < 3; k++) cand[k] = x[k] + step[k] * sc[k];
-            cand_cost = eval_cost(cand);
-            // a trial whose cost is not finite is a failed evaluation: an invalid step
-            valid = isfinite(cand_cost);
-        }
-        if (!valid) {
-            if (++invalid_run >= kLmMaxInvalid) { term = kTermFailure; break; }
-            radius = radius / decrease;
-            decrease *= 2.0;
-            successful = false;
-            continue;
-        }
-        invalid_run = 0;
-        double dx[3];
-        for (int k = 0; k < 3; k++) dx[k] = x[k] - cand[k];
-        if (norm3(dx) <= kLmParamTol * (x_norm + kLmParamTol)) { term = kTermParameterTol; break; }
-        if (fabs(x_cost - cand_cost) <= kLmFuncTol * x_cost) { term = kTermFunctionTol; break; }
-        const double rel = (x_cost - cand_cost) / mcc;
-        if (rel > kLmMinRelDecrease) {
-            for (int k = 0; k < 3; k++) x[k] = cand[k];
-            x_norm = norm3(x);
-            eval_full(x, S);
-            take();
-            x_cost = S[0];
-            const double q = 2.0 * rel - 1.0;
-            const double f = 1.0 - q * q * q;
-            radius = radius / (f > 1.0 / 3.0 ? f : 1.0 / 3.0);
-            radius = radius < kLmMaxRadius ? radius : kLmMaxRadius;
-            decrease = 2.0;
-            reuse_diag = false;
-            successful = true;
-        } else {
-            radius = radius / decrease;
-            decrease *= 2.0;
-            successful = false;
-        }
-    }
+    // lm_solve (pf_lm.hpp) for three parameter blocks: DENSE_SCHUR eliminates a, the reduced
+    // system is 2x2 in (b, d).  Every lane holds the same sums, hence the same state.
+    const double start[3] = {1.0, 1.0, 1.0};  // Depth.cpp:1270-1274
+    double best[3];
+    LmSummary sm;
+    lm_solve<3, true>(start, eval_full, eval_cost, best, sm);
     double inliers = 0.0;
     if constexpr (LOSS) {
         if (summary) {  // the samples with r r <= a a at the returned parameters (exact counts)
@@ -311,10 +183,10 @@ __device__ __forceinline__ void register_disp_tile(
         }
         if (summary) {
             constexpr int kN = LOSS ? 6 : 4;
-            summary[o * kN + 0] = initial_cost;
-            summary[o * kN + 1] = min_cost;
-            summary[o * kN + 2] = (double)iteration;
-            summary[o * kN + 3] = (double)term;
+            summary[o * kN + 0] = sm.initial_cost;
+            summary[o * kN + 1] = sm.final_cost;
+            summary[o * kN + 2] = (double)sm.iterations;
+            summary[o * kN + 3] = (double)sm.termination;
             if constexpr (LOSS) {
                 summary[o * kN + 4] = (double)ns;
                 summary[o * kN + 5] = inliers;

@@ -10,11 +10,11 @@ namespace pf {
 static constexpr int kBlock = 256;
 
 // ---------------------------------------------------------------------------------------------
-// Global cubic fit: the 15 fp64 moment sums of k_register (pf_kernels.hip: same products, same
+// Global cubic fit: the 15 fp64 moment sums of k_register (pf_register.hip: same products, same
 // order per sample) over the samples s = (Y - h0) * W + X of rows h0..h1.  The order is fixed
 // and independent of the grid: chunks of kGlobalChunk consecutive samples, one 256-lane block per
 // (panorama, chunk); lane l adds its samples l, l + 256, ... of the chunk in order from 0.0; the
-// halving tree of k_register reduces the chunk; k_global_solve (pf_kernels.hip) adds the chunk
+// halving tree of k_register reduces the chunk; k_global_solve (pf_register.hip) adds the chunk
 // partials in chunk order.  No atomics.
 static constexpr int kGlobalSums = 15;
 

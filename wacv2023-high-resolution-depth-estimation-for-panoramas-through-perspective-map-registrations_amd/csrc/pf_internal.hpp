@@ -265,7 +265,7 @@ int jres_blocks_per_cu(int w, bool half);
 void launch_jres(hipStream_t s, const JresArgs& A);
 
 // ------------------------------------------------------------------------------------------
-// Kernel launchers (pf_kernels.hip, pf_jacobi.hip).  All are asynchronous on `stream`.
+// Kernel launchers (pf_kernels.hip, pf_register.hip, pf_jacobi.hip).  All are asynchronous on `stream`.
 void launch_tapmap(hipStream_t s, const TileGeom* geom, const TapBox* tb, int ntiles,
                    long long max_points, const GridCol* cols, const GridRow* rows, int32_t* map);
 // pf_layout_audit's counters, ctr[kAuditWords] (zeroed on the stream before the launch): taps
@@ -394,7 +394,7 @@ void launch_disp_map(hipStream_t s, float* data, long long npx, int c, const flo
 // kGlobalChunk consecutive band samples) the 15 moment sums to partials [batch][nchunks][15];
 // ecol / erow: ValueAtCoord's column term per X and row term per Y (element offsets).  Then the
 // chunk partials added in chunk order and the LM from (0, 0, 1, 0) (k_global_solve,
-// pf_kernels.hip); summary as launch_register_disp's, [batch][4].
+// pf_register.hip); summary as launch_register_disp's, [batch][4].
 static constexpr int kGlobalChunk = 16384;
 void launch_global_sums(hipStream_t s, const uint16_t* data, long long dstride, const float* emap,
                         long long estride, const int* ecol, const int* erow, int w, int h0,

@@ -1,6 +1,6 @@
 // pf_robust.hip -- robust cubic tile registration (pf_set_register_loss): the per-tile fit of
 // y = a x^3 + b x^2 + c x + d under Ceres 1.13's HuberLoss or SoftLOneLoss, by the reference's
-// trust-region Levenberg-Marquardt.
+// trust-region Levenberg-Marquardt (lm_solve, pf_lm.hpp).
 //
 // k_register solves the cubic from 15 moment sums; a loss weights every sample by a function of
 // its own residual, which moments cannot carry, so this kernel is sample-wise, in the form of
@@ -63,43 +63,6 @@ __device__ __forceinline__ void rob_cost_term(double X, double Y, const double p
     loss_eval(L, r * r, rho0, rho1);
     acc = acc + 0.5 * rho0;
 }
-
-__device__ bool llt3_solve(double S[3][3], const double rhs[3], double z[3])
-{  // Eigen LLT<Upper> of the 3x3 reduced Schur system (schur_complement_solver.cc:197-213), as
-   // lm_moments' (pf_kernels.hip)
-    double Lo[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-    for (int k = 0; k < 3; k++) {
-        double x = S[k][k];
-        if (k > 0) {
-            double sq = 0.0;
-            for (int i = 0; i < k; i++) sq = sq + Lo[k][i] * Lo[k][i];
-            x = x - sq;
-        }
-        if (!(x > 0.0)) return false;
-        Lo[k][k] = x = sqrt(x);
-        for (int j = k + 1; j < 3; j++) {
-            double a = S[k][j];
-            for (int i = 0; i < k; i++) a = a - Lo[j][i] * Lo[k][i];
-            Lo[j][k] = a / x;
-        }
-    }
-    double y[3] = {rhs[0], rhs[1], rhs[2]};
-    for (int k = 0; k < 3; k++) {
-        y[k] = y[k] / Lo[k][k];
-        for (int j = k + 1; j < 3; j++) y[j] = y[j] - Lo[j][k] * y[k];
-    }
-    for (int k = 2; k >= 0; k--) {
-        y[k] = y[k] / Lo[k][k];
-        for (int j = 0; j < k; j++) y[j] = y[j] - Lo[k][j] * y[k];
-    }
-    z[0] = y[0]; z[1] = y[1]; z[2] = y[2];
-    return true;
-}
-
-__device__ __forceinline__ double norm4(const double v[4])
-{
-    return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
-}
 }  // namespace
 
 // MASK: under the validity rule (k_register_valid's: a sample whose raw tile value fails the rule,
@@ -160,13 +123,20 @@ __global__ void __launch_bounds__(kDispLanes) k_register_robust(
             if (kept(tv, ev)) f(clamp_sample((double)tv), clamp_sample((double)ev));
         }
     };
-    auto eval_full = [&](const double* q, double* S) {
+    auto eval_full = [&](const double (&q)[4], double& cost, double (&g)[4], double (&M)[4][4]) {
+        double S[kRobSums];
 #pragma unroll
         for (int k = 0; k < kRobSums; k++) S[k] = 0.0;
         each([&](double X, double Y) { rob_terms(X, Y, q, S, L); });
         disp_reduce<kRobSums>(S, part, tot, l);
+        cost = S[0];
+        int at = 5;  // upper J'J, row-major
+        for (int i = 0; i < 4; i++) {
+            g[i] = S[1 + i];
+            for (int j = i; j < 4; j++) M[i][j] = M[j][i] = S[at++];
+        }
     };
-    auto eval_cost = [&](const double* q) {
+    auto eval_cost = [&](const double (&q)[4]) {
         double c = 0.0;
         each([&](double X, double Y) { rob_cost_term(X, Y, q, c, L); });
         disp_reduce<1>(&c, part, tot, l);
@@ -199,129 +169,12 @@ __global__ void __launch_bounds__(kDispLanes) k_register_robust(
         }
     }
 
-    // Ceres 1.13 trust-region LM, the control flow of k_register_disp for four parameter blocks:
-    // DENSE_SCHUR eliminates a, the reduced system is the 3x3 one of lm_moments in (b, c, d).
-    // Every lane holds the same sums, hence the same state: all exits below are block-uniform.
-    double x[4] = {1.0, 1.0, 1.0, 1.0}, best[4] = {1.0, 1.0, 1.0, 1.0};  // Depth.cpp:1270-1274
-    double S[kRobSums], sc[4], Ms[4][4], g[4], gs[4], diag[4] = {0, 0, 0, 0}, D[4], step[4],
-        cand[4];
-    auto take = [&]() {  // g and the scaled J'J from the sums of a Jacobian evaluation
-        const double M[4][4] = {{S[5], S[6], S[7], S[8]}, {S[6], S[9], S[10], S[11]},
-                                {S[7], S[10], S[12], S[13]}, {S[8], S[11], S[13], S[14]}};
-        for (int i = 0; i < 4; i++) {
-            g[i] = S[1 + i];
-            for (int j = 0; j < 4; j++) Ms[i][j] = (M[i][j] * sc[i]) * sc[j];
-        }
-    };
-    eval_full(x, S);
-    sc[0] = 1.0 / (1.0 + sqrt(S[5]));  // Jacobi scaling, fixed at iteration 0
-    sc[1] = 1.0 / (1.0 + sqrt(S[9]));
-    sc[2] = 1.0 / (1.0 + sqrt(S[12]));
-    sc[3] = 1.0 / (1.0 + sqrt(S[14]));
-    take();
-    double x_cost = S[0];
-    const double initial_cost = x_cost;
-    double radius = kLmInitRadius, decrease = 2.0, x_norm = -1.0, min_cost = DBL_MAX;
-    bool reuse_diag = false, successful = true;
-    int invalid_run = 0, iteration = 0, term = kTermNoConvergence;
-    for (;;) {
-        if (successful && x_cost < min_cost) {
-            min_cost = x_cost;
-            for (int k = 0; k < 4; k++) best[k] = x[k];
-        }
-        if (iteration >= kLmMaxIter) { term = kTermNoConvergence; break; }
-        if (successful) {
-            double gmax = 0.0;
-            for (int k = 0; k < 4; k++) {
-                const double d = fabs(x[k] - (x[k] + -g[k]));
-                if (d > gmax) gmax = d;
-            }
-            if (gmax <= kLmGradTol) { term = kTermGradientTol; break; }
-        }
-        if (radius <= kLmMinRadius) { term = kTermMinRadius; break; }
-        iteration++;
-        if (!reuse_diag)
-            for (int k = 0; k < 4; k++) {
-                const double d = Ms[k][k] > kLmMinDiag ? Ms[k][k] : kLmMinDiag;
-                diag[k] = d < kLmMaxDiag ? d : kLmMaxDiag;
-            }
-        for (int k = 0; k < 4; k++) D[k] = sqrt(diag[k] / radius);
-        for (int k = 0; k < 4; k++) gs[k] = sc[k] * g[k];
-        const double ete = D[0] * D[0] + Ms[0][0];
-        double R[3][3], rhs[3], z[3];
-        for (int a = 0; a < 3; a++)
-            for (int c = a; c < 3; c++)
-                R[a][c] = Ms[1 + a][1 + c] + (a == c ? D[1 + a] * D[1 + a] : 0.0);
-        const double inv = inv_psd1(ete);
-        const double inv_g = inv * gs[0];
-        for (int a = 0; a < 3; a++) rhs[a] = gs[1 + a] - Ms[0][1 + a] * inv_g;
-        for (int a = 0; a < 3; a++) {
-            const double bt = Ms[0][1 + a] * inv;
-            for (int c = a; c < 3; c++) R[a][c] = R[a][c] - bt * Ms[0][1 + c];
-        }
-        bool ok = llt3_solve(R, rhs, z);
-        if (ok) {
-            double ya = gs[0];
-            for (int a = 0; a < 3; a++) ya = ya - Ms[0][1 + a] * z[a];
-            step[0] = inv * ya;
-            step[1] = z[0];
-            step[2] = z[1];
-            step[3] = z[2];
-            for (int k = 0; ok && k < 4; k++) ok = isfinite(step[k]);
-        }
-        reuse_diag = true;
-        double mcc = 0.0, cand_cost = 0.0;
-        bool valid = false;
-        if (ok) {
-            for (int k = 0; k < 4; k++) step[k] = step[k] * -1.0;
-            double sJr = 0.0, sMs = 0.0;
-            for (int i = 0; i < 4; i++) {
-                double q = 0.0;
-                for (int j = 0; j < 4; j++) q = q + Ms[i][j] * step[j];
-                sMs = sMs + step[i] * q;
-                sJr = sJr + step[i] * gs[i];
-            }
-            mcc = -(sJr + sMs / 2.0);
-            valid = mcc > 0.0;
-        }
-        if (valid) {
-            for (int k = 0; k < 4; k++) cand[k] = x[k] + step[k] * sc[k];
-            cand_cost = eval_cost(cand);
-            // a trial whose cost is not finite is a failed evaluation: an invalid step
-            valid = isfinite(cand_cost);
-        }
-        if (!valid) {
-            if (++invalid_run >= kLmMaxInvalid) { term = kTermFailure; break; }
-            radius = radius / decrease;
-            decrease *= 2.0;
-            successful = false;
-            continue;
-        }
-        invalid_run = 0;
-        double dx[4];
-        for (int k = 0; k < 4; k++) dx[k] = x[k] - cand[k];
-        if (norm4(dx) <= kLmParamTol * (x_norm + kLmParamTol)) { term = kTermParameterTol; break; }
-        if (fabs(x_cost - cand_cost) <= kLmFuncTol * x_cost) { term = kTermFunctionTol; break; }
-        const double rel = (x_cost - cand_cost) / mcc;
-        if (rel > kLmMinRelDecrease) {
-            for (int k = 0; k < 4; k++) x[k] = cand[k];
-            x_norm = norm4(x);
-            eval_full(x, S);
-            take();
-            x_cost = S[0];
-            const double q = 2.0 * rel - 1.0;
-            const double f = 1.0 - q * q * q;
-            radius = radius / (f > 1.0 / 3.0 ? f : 1.0 / 3.0);
-            radius = radius < kLmMaxRadius ? radius : kLmMaxRadius;
-            decrease = 2.0;
-            reuse_diag = false;
-            successful = true;
-        } else {
-            radius = radius / decrease;
-            decrease *= 2.0;
-            successful = false;
-        }
-    }
+    // lm_solve (pf_lm.hpp) for four parameter blocks: DENSE_SCHUR eliminates a, the reduced system
+    // is 3x3 in (b, c, d).  Every lane holds the same sums, hence the same state.
+    const double start[4] = {1.0, 1.0, 1.0, 1.0};  // Depth.cpp:1270-1274
+    double best[4];
+    LmSummary sm;
+    lm_solve<4, true>(start, eval_full, eval_cost, best, sm);
 
     // one more pass at the returned parameters: the samples with r r <= a a (exact counts)
     double inliers = 0.0;
@@ -334,17 +187,17 @@ __global__ void __launch_bounds__(kDispLanes) k_register_robust(
     if (l == 0) {
         bool finite = true;
         for (int i = 0; i < 4; i++) finite = finite && isfinite(best[i]);
-        if (!finite) term = kTermFailure;
+        if (!finite) sm.termination = kTermFailure;
         for (int i = 0; i < 4; i++) {
             if (coeffs)  // Vec4f(vars), Depth.cpp:1408
                 coeffs[o * 4 + i] = finite ? (float)best[i] : __uint_as_float(0x7FC00000u);
             if (coeffs64) coeffs64[o * 4 + i] = finite ? best[i] : qnan;
         }
         if (summary) {
-            summary[o * 6 + 0] = initial_cost;
-            summary[o * 6 + 1] = min_cost;
-            summary[o * 6 + 2] = (double)iteration;
-            summary[o * 6 + 3] = (double)term;
+            summary[o * 6 + 0] = sm.initial_cost;
+            summary[o * 6 + 1] = sm.final_cost;
+            summary[o * 6 + 2] = (double)sm.iterations;
+            summary[o * 6 + 3] = (double)sm.termination;
             summary[o * 6 + 4] = used;
             summary[o * 6 + 5] = inliers;
         }
