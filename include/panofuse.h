@@ -221,6 +221,46 @@ int pf_register_ex(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, float
                    int batch, float zr0, float zr1, int degree, int apply, float* coeffs,
                    double* coeffs64, double* summary);
 
+/* ---- planar-depth tiles (an extension: the reference reads every tile value as ray distance) ----
+ *
+ * Perspective depth networks (LeReS, MiDaS / DPT, ZoeDepth, ...) predict planar depth: distance
+ * along the optical axis.  The baseline panorama and the fused result hold ray distance: distance
+ * from the camera centre.  On SetWindow's plane at unit distance (Depth.cpp:120-155) tile pixel
+ * (x, y) sits at pos = corner0 + x hedge + y vedge, and the two differ by the factor
+ *   k = |pos| = sqrt(1 + (tx (1 - 2x))^2 + (ty (2y - 1))^2),  tx = tan(daz / 2), ty = tan(dzen / 2),
+ * which depends on the pixel's position, so no per-tile function of the value can carry it.
+ *
+ * pf_set_tiles builds, per tile, cu[i] = (tx (1 - 2 i / (w-1)))^2 and rv[j] = (ty (2 j / (h-1) - 1))^2
+ * in fp64 from the fp32 window (pixel i is x = i / (w-1), the inverse of Value()'s truncating
+ * index).  The factor has one definition: kf(i, j) = (float)sqrt(1.0 + cu[i] + rv[j]), the adds and
+ * the sqrt in fp64, rounded once to fp32; the registrations use K = (double)kf.
+ *
+ * Under PF_TILE_DEPTH_PLANAR:
+ *   pf_register, pf_register_ex, pf_register_disparity   fit K T(x) to the baseline, T the per-tile
+ *     cubic or 1/(a x + b) + d: the residual is K m - y and the Jacobian row is K times the plain
+ *     one, in the plain fits' summation order, for every combination of solver, degree, validity
+ *     rule and loss that runs in ray mode.  apply != 0 writes clamp01(kf * T32(x)): T32 is the fp32
+ *     value of Depth2DepthTransform / D2DTransform before its final clamp, then one fp32 multiply,
+ *     then the clamp; NaN stays NaN and, under the validity rule, an invalid pixel becomes NaN.
+ *   pf_merge, pf_merge_disparity   register, apply into a context-owned copy of the tiles and fuse
+ *     that copy without coefficients; the caller's tiles are untouched and coeffs receives the
+ *     planar fit.  Under the validity rule the copy is fused under (-inf, +inf): its invalid
+ *     pixels are the NaNs apply wrote, and a value clamped to 0 or 1 is valid.
+ *   The fused-transform gathers have no factor: pf_fuse, pf_fuse_targets, pf_fuse_check, pf_stitch,
+ *     pf_solve_smoothing, pf_fuse_partial, pf_fuse_partial_rows and pf_fuse_multicover return
+ *     PF_ESTATE when coeffs != NULL, and run as ever with coeffs == NULL (the tiles are then ray
+ *     distance already).  pf_register_joint returns PF_ESTATE.  Everything else is unaffected.
+ * With PF_TILE_DEPTH_RAY (the default, also after PLANAR was set and unset) every entry point
+ * launches the kernels and returns the bits it always did. */
+#define PF_TILE_DEPTH_RAY 0     /* default: tiles hold ray distance, as the reference assumes */
+#define PF_TILE_DEPTH_PLANAR 1  /* tiles hold depth along the optical axis */
+int pf_set_tile_depth(pf_ctx* ctx, int kind);          /* unknown kind: PF_EINVAL */
+/* The tables of one tile of the stored layout: HOST out, cu[tile_w], rv[tile_h]. */
+int pf_tile_ray_tables(pf_ctx* ctx, int tile, double* cu, double* rv);
+/* kf of every tile pixel: DEVICE out, one float per tile pixel (no channels), tiles in layout
+ * order, rows top-first.  Works in either mode.  Stream-ordered. */
+int pf_tile_ray_factor(pf_ctx* ctx, float* k);
+
 /* ---- post-fusion calibration (no tile layout needed; all pointers are device pointers) ----
  *
  * SolveDepthToDepth2 (Depth.cpp:1158-1259): one cubic per panorama from the fused u16 result

@@ -328,6 +328,18 @@ bool SetTileValidity(bool on, float lo, float hi);
  * of <n> samples beyond a=<A>, cost <c0> -> <c1>, <it> iterations, <termination>".  false (and a
  * message) for an unknown kind or a bad scale. */
 bool SetRegistrationLoss(int kind, double a);
+/* EXTENSION (the reference reads every tile value as ray distance): what the tiles of every later
+ * call of this facade hold, process-wide (pf_set_tile_depth, include/panofuse.h): kind 0 ray
+ * distance (the default), 1 planar depth, i.e. depth along the optical axis as perspective depth
+ * networks predict it.  Under planar depth MergeDepthMaps / MergeDisparityMaps register with the
+ * per-pixel ray factor, transform the uploaded tiles and fuse, stitch or smooth those, and print
+ * "[tile-depth] planar: ray factor up to <max> over <n> tiles"; SolveDepthToDepth with one active
+ * map and SolveDisparityToDepth fit with the factor; the calls that hand the library a transform to
+ * fuse into its gather, and SolveDepthToDepth with several active maps, print the library's message
+ * and return false.  MergeDepthMaps / MergeDisparityMaps also read PF_TILE_DEPTH=planar|ray
+ * (panofuse_main --tile-depth), which holds for that call.  false (and a message) for another
+ * kind. */
+bool SetTileDepth(int kind);
 /* EXTENSION (in the reference an `if (false)` block of MergeDepthMaps, Depth.cpp:817-865): the
  * direct stitch of the tiles as they are into data (width * height u16) -- every pixel takes the
  * first map whose range box contains it, no fusion -- on the GPU (pf_stitch), bit-exact. */

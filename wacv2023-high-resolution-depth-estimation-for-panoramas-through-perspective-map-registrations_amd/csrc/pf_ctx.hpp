@@ -69,6 +69,9 @@ struct pf_ctx {
     // robust loss of the tile registrations (pf_set_register_loss); PF_LOSS_NONE: least squares
     int loss_kind = PF_LOSS_NONE;
     double loss_a = 0.0;
+    // what the tiles hold (pf_set_tile_depth); PF_TILE_DEPTH_RAY: ray distance, as the reference
+    // assumes, and every entry point launches what it always did
+    int tile_depth = PF_TILE_DEPTH_RAY;
     std::vector<pf_window> fov, rng;
     std::vector<int> tw_h, th_h;
     bool layout_ok = false;  // the stored layout was set completely
@@ -78,6 +81,13 @@ struct pf_ctx {
     pf::DevBuf geom, reg, rcols, rrows, rgb_off;
     pf::DevBuf reg_sidx;                   // registration sample indices (k_regidx), for the
     int reg_sidx_key[3] = {-1, -1, -1};    // (ew, eh, ec) of the baseline they were built for
+    // the ray factor of planar-depth tiles: the layout's fp64 column / row tables (pf_ray.hpp; host
+    // copy and device copy, uploaded by pf_set_tiles), where each tile's start, and the factor of
+    // every registration sample (k_reg_kf), built on first planar use for the key of reg_sidx
+    std::vector<double> ray_tab_h;
+    std::vector<pf::RayTile> ray_h;
+    pf::DevBuf ray_tab, ray, reg_kf;
+    int reg_kf_key[3] = {-1, -1, -1};
     std::vector<pf::RgbCam> cams_h;  // GL cameras of the RGB warp (SaveCubeMap), host only
     // RGB warp taps for one panorama size (rgb_taps_host), built on first use
     int rgb_pw = 0, rgb_ph = 0;
@@ -98,7 +108,9 @@ struct pf_ctx {
     // workspace
     pf::DevBuf buf[3], lnorm, coeffs, lsum_ws, metrics_ws, reg_sums, reg_active;
     pf::DevBuf audit_ws;    // pf_layout_audit: the counter words
-    pf::DevBuf disp_tiles;  // pf_merge_disparity: the transformed copy of the caller's tiles
+    // pf_merge_disparity, pf_merge under PF_TILE_DEPTH_PLANAR: the transformed copy of the
+    // caller's tiles
+    pf::DevBuf disp_tiles;
     // pf_register_global: ValueAtCoord's column / row terms for one (result size, baseline size)
     // key, the chunk partials with the coefficients after them; pf_median_scale: bins and states
     pf::DevBuf glob_ecol, glob_erow, glob_ws, med_ws;
@@ -282,6 +294,19 @@ inline int check_no_loss(pf_ctx* c, const char* entry)
     return PF_OK;
 }
 
+// The entry points whose fused-transform gathers have no ray factor refuse coefficients while the
+// tiles are planar depth (without coefficients the tiles are read as they are: ray distance).
+inline int check_ray_coeffs(pf_ctx* c, const char* entry, const void* coeffs)
+{
+    if (c && c->tile_depth != PF_TILE_DEPTH_RAY && coeffs)
+        return fail(c, PF_ESTATE,
+                    "%s has no ray factor in its fused transform: register with apply (or pf_merge) "
+                    "and pass coeffs = NULL, or call pf_set_tile_depth(ctx, PF_TILE_DEPTH_RAY) "
+                    "first",
+                    entry);
+    return PF_OK;
+}
+
 // Whether level l may take the coverage shortcuts (the packed Jacobi form, the resident kernel):
 // it holds the separable-coverage certificate and coverage does not depend on the data.
 inline bool level_full(const pf_ctx* c, int l) { return c->lc.full[l] && !c->valid.on; }
@@ -299,6 +324,8 @@ int prepare_levels(pf_ctx* c, int out_w, int out_h, float zr0, float zr1);
 // The registration grids for this zenith range, and the checks / tables that follow them.
 int prepare_registration(pf_ctx* c, float zr0, float zr1);
 const int2* reg_sample_index(pf_ctx* c, int ew, int eh, int ec);
+// The ray factor of the samples of reg_sample_index(c, ew, eh, ec) (nullptr: no table).
+const float* reg_sample_kf(pf_ctx* c, int ew, int eh, int ec);
 int check_reg_grids(pf_ctx* c, const int* active);
 void grid_tables(const LevelDims& L, std::vector<GridCol>& cols, std::vector<GridRow>& rows);
 

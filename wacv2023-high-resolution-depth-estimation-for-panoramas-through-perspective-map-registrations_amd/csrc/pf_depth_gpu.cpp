@@ -29,6 +29,14 @@ RegLossRule reg_loss()
     return g_loss;
 }
 
+static int g_tile_depth = PF_TILE_DEPTH_RAY;
+
+int tile_depth()
+{
+    std::lock_guard<std::mutex> lk(g_rule_mu);
+    return g_tile_depth;
+}
+
 static pf_ctx* device_ctx();
 
 pf_ctx* facade_ctx()
@@ -37,6 +45,7 @@ pf_ctx* facade_ctx()
     if (c) {
         apply_rule(c, tile_rule());  // a checked rule (SetTileValidity): cannot fail
         apply_loss(c, reg_loss());   // a checked loss (SetRegistrationLoss): neither
+        pf_set_tile_depth(c, tile_depth());  // a checked kind (SetTileDepth): neither
     }
     return c;
 }
@@ -235,6 +244,18 @@ bool SetRegistrationLoss(int kind, double a)
     return true;
 }
 
+bool SetTileDepth(int kind)
+{  // EXTENSION: pf_set_tile_depth for every later facade call
+    if (kind != PF_TILE_DEPTH_RAY && kind != PF_TILE_DEPTH_PLANAR) {
+        std::cout << "[SetTileDepth] needs PF_TILE_DEPTH_RAY or PF_TILE_DEPTH_PLANAR (got " << kind
+                  << ")" << std::endl;
+        return false;
+    }
+    std::lock_guard<std::mutex> lk(pff::g_rule_mu);
+    pff::g_tile_depth = kind;
+    return true;
+}
+
 // ---- the four map members that run on the GPU ----
 void EquirectangularMap::CopyInvalidPixels(EquirectangularMap& ref)  // Depth.cpp:703-725
 {
@@ -284,8 +305,11 @@ bool SolveDepthToDepth(EquirectangularMap& emap, std::vector<PerspectiveMap>& pm
     }
     const std::vector<int> all(pm.size(), 1);
     // under a loss (SetRegistrationLoss) one active map is the robust per-tile fit; several go to
-    // the joint solve, which has no robust form and answers with the library's message
-    if (pm.size() == 1 && reg_loss().kind != PF_LOSS_NONE)
+    // the joint solve, which has no robust form and answers with the library's message.  The same
+    // for planar-depth tiles (SetTileDepth): the per-tile fit carries the ray factor, the joint
+    // solve does not.
+    if (pm.size() == 1 &&
+        (reg_loss().kind != PF_LOSS_NONE || tile_depth() != PF_TILE_DEPTH_RAY))
         return solve(emap, pm, "pf_register", abcd,
                      [&](pf_ctx* c, const float* de, float* dt, float* dc) {
                          return pf_register(c, de, emap.width, emap.height, emap.channels, dt, 1,

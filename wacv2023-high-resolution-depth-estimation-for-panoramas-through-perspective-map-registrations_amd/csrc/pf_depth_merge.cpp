@@ -6,10 +6,12 @@
 // file writes stay on the host (they are file formats), every per-pixel computation of the path
 // (registration, transform, fusion, quantisation, metrics) is a libpanofuse HIP kernel.
 #include "pf_facade.hpp"
+#include "pf_ray.hpp"
 #include "pf_valid.hpp"
 
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <future>
@@ -33,6 +35,9 @@ struct MergeSwitches {
     // PF_REG_LOSS=huber:A|softl1:A (panofuse_main --reg-loss): the registration loss of this
     // call; without it the loss is SetRegistrationLoss's
     RegLossRule loss{PF_LOSS_NONE, 0.0};
+    // PF_TILE_DEPTH=planar|ray (panofuse_main --tile-depth): what the tiles of this call hold;
+    // without it SetTileDepth's
+    int tile_depth = PF_TILE_DEPTH_RAY;
 };
 
 bool read_merge_switches(MergeSwitches& s)
@@ -64,6 +69,15 @@ bool read_merge_switches(MergeSwitches& s)
         if (!parse_reg_loss(rl, s.loss)) {
             std::cout << "[MergeDepthMaps] bad PF_REG_LOSS " << rl
                       << " (want huber:A or softl1:A, A > 0)" << std::endl;
+            return false;
+        }
+    }
+    s.tile_depth = tile_depth();
+    if (const char* td = std::getenv("PF_TILE_DEPTH")) {
+        s.tile_depth = pf::parse_tile_depth(td);
+        if (s.tile_depth < 0) {
+            std::cout << "[MergeDepthMaps] bad PF_TILE_DEPTH " << td << " (want planar or ray)"
+                      << std::endl;
             return false;
         }
     }
@@ -138,9 +152,12 @@ struct Job {
 // Registration (Depth.cpp:789-808): every tile alone; depth tiles: cubic, the transform fused
 // into the fusion; disparity tiles: y = 1/(a x + b) + d, D2DTransform on the uploaded copy.
 bool register_tiles(const Job& j, float* d_coeffs, bool disparity_tiles, int ntiles,
-                    const RegLossRule& loss)
+                    const RegLossRule& loss, bool planar)
 {
     const EquirectangularMap& e = j.emap;
+    // planar-depth tiles: the cubic is applied to the uploaded tiles too (with the ray factor),
+    // and the fusion then runs without coefficients
+    const int apply = planar ? 1 : 0;
     if (loss.kind != PF_LOSS_NONE) {  // the same calls with the solver summary, one line per tile
         static const char* const kTerm[] = {"no convergence", "function tolerance",
                                             "parameter tolerance", "gradient tolerance",
@@ -154,7 +171,7 @@ bool register_tiles(const Job& j, float* d_coeffs, bool disparity_tiles, int nti
                                                    j.d_tiles, 1, j.zr[0], j.zr[1], 1, d_coeffs,
                                                    nullptr, ds.as<double>())
                            : pf_register_ex(j.c, j.d_emap, e.width, e.height, e.channels,
-                                            j.d_tiles, 1, j.zr[0], j.zr[1], 3, 0, d_coeffs,
+                                            j.d_tiles, 1, j.zr[0], j.zr[1], 3, apply, d_coeffs,
                                             nullptr, ds.as<double>()),
                        disparity_tiles ? "pf_register_disparity" : "pf_register_ex") ||
             !download(sm.data(), ds, sm.size()))
@@ -175,7 +192,7 @@ bool register_tiles(const Job& j, float* d_coeffs, bool disparity_tiles, int nti
                                                  j.d_tiles, 1, j.zr[0], j.zr[1], 1, d_coeffs,
                                                  nullptr, nullptr)
                          : pf_register(j.c, j.d_emap, e.width, e.height, e.channels, j.d_tiles, 1,
-                                       j.zr[0], j.zr[1], 3, 0, d_coeffs, nullptr),
+                                       j.zr[0], j.zr[1], 3, apply, d_coeffs, nullptr),
                      disparity_tiles ? "pf_register_disparity" : "pf_register");
 }
 
@@ -224,6 +241,27 @@ bool print_mask_lines(const Job& j, int ntiles, const TileRule& rule)
         return false;
     }
     for (const std::string& ln : lines) std::cout << ln << std::endl;
+    return true;
+}
+
+// "[tile-depth] planar: ray factor up to <max kf> over <n> tiles", from the layout's tables.
+bool print_tile_depth_line(pf_ctx* c, const std::vector<PerspectiveMap>& pmaps)
+{
+    float top = 1.0f;
+    for (size_t p = 0; p < pmaps.size(); p++) {
+        std::vector<double> cu((size_t)pmaps[p].width), rv((size_t)pmaps[p].height);
+        if (!pf_ok(c, pf_tile_ray_tables(c, (int)p, cu.data(), rv.data()), "pf_tile_ray_tables"))
+            return false;
+        double mu = 0.0, mv = 0.0;
+        for (double v : cu) mu = v > mu ? v : mu;
+        for (double v : rv) mv = v > mv ? v : mv;
+        const float k = pf::ray_factor(mu, mv);
+        top = k > top ? k : top;
+    }
+    char line[128];
+    std::snprintf(line, sizeof(line), "[tile-depth] planar: ray factor up to %.3f over %zu tiles",
+                  (double)top, pmaps.size());
+    std::cout << line << std::endl;
     return true;
 }
 
@@ -367,21 +405,30 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
         {
             apply_rule(c, tile_rule());
             apply_loss(c, reg_loss());
+            pf_set_tile_depth(c, tile_depth());
         }
     } rule_scope{c};
     if (!pf_ok(c, apply_rule(c, sw.rule), "pf_set_tile_validity")) return false;
     if (!pf_ok(c, apply_loss(c, sw.loss), "pf_set_register_loss")) return false;
+    if (!pf_ok(c, pf_set_tile_depth(c, sw.tile_depth), "pf_set_tile_depth")) return false;
+    const bool planar = sw.tile_depth == PF_TILE_DEPTH_PLANAR;
     DevMem dt = tiles_on_device(c, pmaps);
     if (!dt.ok) return false;
     DevMem de = on_device(emap), dc(sizeof(float) * 4 * pmaps.size()), dout(no * 2);
     if (!de.ok || !dc.ok || !dout.ok) return false;
     const Job j{c, emap, de.as<float>(), dt.as<float>(),
-                disparity_tiles ? nullptr : dc.as<float>(), dout.as<uint16_t>(), out_width,
-                out_height, zr};
+                disparity_tiles || planar ? nullptr : dc.as<float>(), dout.as<uint16_t>(),
+                out_width, out_height, zr};
+    if (planar && !print_tile_depth_line(c, pmaps)) return false;
 
     if (sw.rule.on && !print_mask_lines(j, (int)pmaps.size(), sw.rule)) return false;
     auto t = std::chrono::steady_clock::now();
-    if (!register_tiles(j, dc.as<float>(), disparity_tiles, (int)pmaps.size(), sw.loss))
+    if (!register_tiles(j, dc.as<float>(), disparity_tiles, (int)pmaps.size(), sw.loss, planar))
+        return false;
+    // the transformed planar tiles carry NaN at their invalid pixels: what follows reads them
+    // under (-inf, +inf), not under the caller's lo / hi (a value clamped to exactly 0 is valid)
+    if (planar && sw.rule.on &&
+        !pf_ok(c, apply_rule(c, TileRule{true, -INFINITY, INFINITY}), "pf_set_tile_validity"))
         return false;
     if (time_Reg) *time_Reg = elapsed_ms(t);
     t = std::chrono::steady_clock::now();

@@ -23,13 +23,40 @@ constexpr int kDispSums = 10;  // cost, J'r (3), upper J'J (6)
 // (-(X q q), -(q q), 1).
 // With LOSS (pf_set_register_loss) the cost term is 0.5 rho(r r) and the residual and the row
 // are scaled by sqrt(rho'(r r)) first (pf_lm.hpp); without, this is the code it always was.
-template <bool LOSS>
+// PLANAR (pf_set_tile_depth): the model is K (q + d) with the sample's ray factor K, so
+// r = K (q + d) - Y and the row is (K j0, K j1, K), one multiply per entry, before any loss.
+template <bool LOSS, bool PLANAR = false>
 __device__ __forceinline__ void disp_terms(double X, double Y, const double p[3],
-                                           double acc[kDispSums], const RegLoss& L)
+                                           double acc[kDispSums], const RegLoss& L, double K = 1.0)
 {
     const double q = 1.0 / (p[0] * X + p[1]);
-    const double r = (q + p[2]) - Y;
     const double qq = q * q;
+    if constexpr (PLANAR) {
+        const double r = K * (q + p[2]) - Y;
+        double k0 = K * -(X * qq), k1 = K * -qq, k2 = K, rc = r, c0 = 0.5 * (r * r);
+        if constexpr (LOSS) {
+            double rho0, rho1;
+            loss_eval(L, r * r, rho0, rho1);
+            const double w = sqrt(rho1);
+            rc = w * r;
+            k0 = w * k0;
+            k1 = w * k1;
+            k2 = w * k2;
+            c0 = 0.5 * rho0;
+        }
+        acc[0] = acc[0] + c0;
+        acc[1] = acc[1] + k0 * rc;
+        acc[2] = acc[2] + k1 * rc;
+        acc[3] = acc[3] + k2 * rc;
+        acc[4] = acc[4] + k0 * k0;
+        acc[5] = acc[5] + k0 * k1;
+        acc[6] = acc[6] + k0 * k2;
+        acc[7] = acc[7] + k1 * k1;
+        acc[8] = acc[8] + k1 * k2;
+        acc[9] = acc[9] + k2 * k2;
+        return;
+    }
+    const double r = (q + p[2]) - Y;
     const double j0 = -(X * qq), j1 = -qq;
     if constexpr (LOSS) {
         double rho0, rho1;
@@ -60,12 +87,12 @@ __device__ __forceinline__ void disp_terms(double X, double Y, const double p[3]
     acc[9] = acc[9] + 1.0;
 }
 
-template <bool LOSS>
+template <bool LOSS, bool PLANAR = false>
 __device__ __forceinline__ void disp_cost_term(double X, double Y, const double p[3], double& acc,
-                                               const RegLoss& L)
+                                               const RegLoss& L, double K = 1.0)
 {
     const double q = 1.0 / (p[0] * X + p[1]);
-    const double r = (q + p[2]) - Y;
+    const double r = PLANAR ? K * (q + p[2]) - Y : (q + p[2]) - Y;
     if constexpr (LOSS) {
         double rho0, rho1;
         loss_eval(L, r * r, rho0, rho1);
@@ -77,14 +104,18 @@ __device__ __forceinline__ void disp_cost_term(double X, double Y, const double 
 }  // namespace
 
 // One block's fit of tile p of panorama b.  LOSS: under the robust loss L, with the 6-entry
-// summary of pf_register_ex; without, k_register_disp as it was.
-template <bool LOSS>
+// summary of pf_register_ex; without, k_register_disp as it was.  PLANAR: with the samples' ray
+// factor kfs (k_reg_kf).  The resident registers hold (x, y) as before; K is a float load from the
+// cached table in every pass (coalesced: lane l reads kfs[l + 256 u]), widened to fp64 -- a third
+// resident value per sample does not fit the register file, and the load replaces nothing that
+// was in registers.  The lane-to-sample order is unchanged.
+template <bool LOSS, bool PLANAR = false>
 __device__ __forceinline__ void register_disp_tile(
     const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
     const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
     long long tstride, const int2* __restrict__ sidx, float* __restrict__ coeffs,
     double* __restrict__ coeffs64, double* __restrict__ summary, const RegLoss L,
-    double (*part)[kDispLanes], double* tot)
+    double (*part)[kDispLanes], double* tot, const float* __restrict__ kfs = nullptr)
 {
     // k_register's block order: the tiles of one panorama on one XCD
     const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
@@ -94,6 +125,8 @@ __device__ __forceinline__ void register_disp_tile(
     const float* em = emap + b * estride;
     const int2* ix = sidx + rg.soff;
     const int ns = (rg.cols + 1) * (rg.rows + 1);
+    const float* kf = PLANAR ? kfs + rg.soff : nullptr;
+    auto Kof = [&](int s) { return PLANAR ? (double)kf[s] : 1.0; };
 
     // the lane's resident samples l, l + 256, ...: gathered once (independent loads)
     float xs[kDispPerLane], ys[kDispPerLane];
@@ -116,12 +149,12 @@ __device__ __forceinline__ void register_disp_tile(
 #pragma unroll
         for (int u = 0; u < kDispPerLane; u++)
             if (l + u * kDispLanes < ns)
-                disp_terms<LOSS>(clamp_sample((double)xs[u]), clamp_sample((double)ys[u]), q, S,
-                                 L);
+                disp_terms<LOSS, PLANAR>(clamp_sample((double)xs[u]), clamp_sample((double)ys[u]),
+                                         q, S, L, Kof(l + u * kDispLanes));
         for (int s = l + kDispResident; s < ns; s += kDispLanes) {  // past the capacity
             const int2 i2 = ix[s];
-            disp_terms<LOSS>(clamp_sample((double)tile[i2.x]), clamp_sample((double)em[i2.y]), q,
-                             S, L);
+            disp_terms<LOSS, PLANAR>(clamp_sample((double)tile[i2.x]),
+                                     clamp_sample((double)em[i2.y]), q, S, L, Kof(s));
         }
         disp_reduce<kDispSums>(S, part, tot, l);
         cost = S[0];
@@ -138,12 +171,13 @@ __device__ __forceinline__ void register_disp_tile(
 #pragma unroll
         for (int u = 0; u < kDispPerLane; u++)
             if (l + u * kDispLanes < ns)
-                disp_cost_term<LOSS>(clamp_sample((double)xs[u]), clamp_sample((double)ys[u]), q,
-                                     c, L);
+                disp_cost_term<LOSS, PLANAR>(clamp_sample((double)xs[u]),
+                                             clamp_sample((double)ys[u]), q, c, L,
+                                             Kof(l + u * kDispLanes));
         for (int s = l + kDispResident; s < ns; s += kDispLanes) {
             const int2 i2 = ix[s];
-            disp_cost_term<LOSS>(clamp_sample((double)tile[i2.x]), clamp_sample((double)em[i2.y]),
-                                 q, c, L);
+            disp_cost_term<LOSS, PLANAR>(clamp_sample((double)tile[i2.x]),
+                                         clamp_sample((double)em[i2.y]), q, c, L, Kof(s));
         }
         disp_reduce<1>(&c, part, tot, l);
         return c;
@@ -158,17 +192,19 @@ __device__ __forceinline__ void register_disp_tile(
     double inliers = 0.0;
     if constexpr (LOSS) {
         if (summary) {  // the samples with r r <= a a at the returned parameters (exact counts)
-            auto count = [&](double X, double Y) {
-                const double r = (1.0 / (best[0] * X + best[1]) + best[2]) - Y;
+            auto count = [&](double X, double Y, double K) {
+                const double m = 1.0 / (best[0] * X + best[1]) + best[2];
+                const double r = PLANAR ? K * m - Y : m - Y;
                 if (r * r <= L.b) inliers = inliers + 1.0;
             };
 #pragma unroll
             for (int u = 0; u < kDispPerLane; u++)
                 if (l + u * kDispLanes < ns)
-                    count(clamp_sample((double)xs[u]), clamp_sample((double)ys[u]));
+                    count(clamp_sample((double)xs[u]), clamp_sample((double)ys[u]),
+                          Kof(l + u * kDispLanes));
             for (int s = l + kDispResident; s < ns; s += kDispLanes) {
                 const int2 i2 = ix[s];
-                count(clamp_sample((double)tile[i2.x]), clamp_sample((double)em[i2.y]));
+                count(clamp_sample((double)tile[i2.x]), clamp_sample((double)em[i2.y]), Kof(s));
             }
             disp_reduce<1>(&inliers, part, tot, l);
         }
@@ -219,6 +255,32 @@ __global__ void __launch_bounds__(kDispLanes) k_register_disp_loss(
                              coeffs64, summary, loss, part, tot);
 }
 
+__global__ void __launch_bounds__(kDispLanes) k_register_disp_planar(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, const int2* __restrict__ sidx, const float* __restrict__ kfs,
+    float* __restrict__ coeffs, double* __restrict__ coeffs64, double* __restrict__ summary)
+{
+    __shared__ double part[kDispSums][kDispLanes];
+    __shared__ double tot[kDispSums];
+    register_disp_tile<false, true>(geom, grids, ntiles, emap, estride, tiles, tstride, sidx,
+                                    coeffs, coeffs64, summary,
+                                    RegLoss{PF_LOSS_NONE, 0.0, 0.0, 0.0}, part, tot, kfs);
+}
+
+__global__ void __launch_bounds__(kDispLanes) k_register_disp_planar_loss(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, const int2* __restrict__ sidx, const float* __restrict__ kfs,
+    float* __restrict__ coeffs, double* __restrict__ coeffs64, double* __restrict__ summary,
+    RegLoss loss)
+{
+    __shared__ double part[kDispSums][kDispLanes];
+    __shared__ double tot[kDispSums];
+    register_disp_tile<true, true>(geom, grids, ntiles, emap, estride, tiles, tstride, sidx,
+                                   coeffs, coeffs64, summary, loss, part, tot, kfs);
+}
+
 // D2DTransform's per-pixel map (Depth.cpp:225-240).  The X clamps compare the float against the
 // double constants 1e-4 and 1 - 1e-4 as Depth2DepthTransform's do: cubic_map's float thresholds
 // decide identically (pf_internal.hpp).  A NaN passes every comparison and stays NaN.
@@ -247,6 +309,34 @@ __global__ void __launch_bounds__(256) k_apply_disp(const TileGeom* __restrict__
         t[i * g.c] = disp_map(t[i * g.c], abcd.x, abcd.y, abcd.z, abcd.w);
 }
 
+// D2DTransform composed with the ray factor (pf_set_tile_depth), src -> dst (in place when they
+// are equal): clamp01(kf * T32(X)), T32 = disp_map's fp32 value before its final clamp, in its
+// operation order; one fp32 multiply by kf; NaN stays NaN.
+__global__ void __launch_bounds__(256) k_apply_disp_planar(
+    const TileGeom* __restrict__ geom, const RayTile* __restrict__ ray,
+    const double* __restrict__ tab, int ntiles, const float* src, float* dst, long long tstride,
+    const float* __restrict__ coeffs)
+{
+    const int p = blockIdx.y, b = blockIdx.z;
+    const TileGeom g = geom[p];
+    const RayTile rt = ray[p];
+    const long long npx = (long long)g.w * g.h;
+    const float4 abcd = *reinterpret_cast<const float4*>(coeffs + ((long long)b * ntiles + p) * 4);
+    const float* in = src + b * tstride + g.off;
+    float* t = dst + b * tstride + g.off;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < npx;
+         i += (long long)gridDim.x * 256) {
+        float X = in[i * g.c];
+        if (X <= 9.99999974737875e-05f) X = (float)1e-4;  // disp_map's clamps
+        else if (X > 0.99989998340606689f) X = (float)(1 - 1e-4);
+        float Y = abcd.z / (abcd.x * X + abcd.y) + abcd.w;
+        Y = ray_kf(tab, rt, (int)i % g.w, (int)i / g.w) * Y;
+        if (Y < 0) Y = 0;
+        else if (Y > 1) Y = 1;
+        t[i * g.c] = Y;
+    }
+}
+
 // D2DTransform of one map, channel 0 of every pixel, in place.
 __global__ void __launch_bounds__(256) k_disp_map(float* __restrict__ data, long long npx, int c,
                                                   float a, float b, float cc, float d)
@@ -271,6 +361,35 @@ void launch_register_disp(hipStream_t s, const TileGeom* geom, const RegGrid* gr
     hipLaunchKernelGGL(k_register_disp, dim3((unsigned)(ntiles * batch)), dim3(kDispLanes), 0, s,
                        geom, grids, ntiles, emap, estride, tiles, tstride, sidx, coeffs, coeffs64,
                        summary);
+}
+
+void launch_register_disp_planar(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
+                                 int ntiles, const float* emap, long long estride,
+                                 const float* tiles, long long tstride, const int2* sidx,
+                                 const float* kfs, float* coeffs, double* coeffs64,
+                                 double* summary, int batch, int loss_kind, double loss_a)
+{
+    const dim3 grid((unsigned)(ntiles * batch)), block(kDispLanes);
+    if (loss_kind != PF_LOSS_NONE)
+        hipLaunchKernelGGL(k_register_disp_planar_loss, grid, block, 0, s, geom, grids, ntiles,
+                           emap, estride, tiles, tstride, sidx, kfs, coeffs, coeffs64, summary,
+                           make_loss(loss_kind, loss_a));
+    else
+        hipLaunchKernelGGL(k_register_disp_planar, grid, block, 0, s, geom, grids, ntiles, emap,
+                           estride, tiles, tstride, sidx, kfs, coeffs, coeffs64, summary);
+}
+
+void launch_apply_disp_planar(hipStream_t s, const TileGeom* geom, const RayTile* ray,
+                              const double* tab, int ntiles, long long tile_pixels,
+                              const float* src, float* dst, long long tstride,
+                              const float* coeffs, int batch)
+{
+    const long long per = tile_pixels / (ntiles > 0 ? ntiles : 1);
+    long long gx = (per + 255) / 256;
+    if (gx > 1024) gx = 1024;
+    if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(k_apply_disp_planar, dim3((unsigned)gx, ntiles, batch), dim3(256), 0, s,
+                       geom, ray, tab, ntiles, src, dst, tstride, coeffs);
 }
 
 void launch_apply_disp(hipStream_t s, const TileGeom* geom, int ntiles, long long tile_pixels,

@@ -26,7 +26,22 @@ int pf_register_disparity(pf_ctx* c, const float* emap, int ew, int eh, int ec, 
     for (const RegGrid& g : c->reg_h) nsamp += (double)(g.cols + 1) * (g.rows + 1);
     const int2* sidx = reg_sample_index(c, ew, eh, ec);  // before the stage timer: built once
     if (!sidx) return fail(c, PF_EHIP, "pf_register_disparity: no sample-index table");
-    {
+    if (c->tile_depth == PF_TILE_DEPTH_PLANAR) {  // the fit and D2DTransform with the ray factor
+        const float* kfs = reg_sample_kf(c, ew, eh, ec);
+        if (!kfs) return fail(c, PF_EHIP, "pf_register_disparity: no sample ray-factor table");
+        StageTimer t(c, PF_STAGE_REGISTER,
+                     batch * (12.0 * nsamp + (apply ? 8.0 * (double)c->tile_elems / c->tile_c : 0.0)),
+                     apply ? 2 : 1);
+        launch_register_disp_planar(c->stream, (const TileGeom*)c->geom.p,
+                                    (const RegGrid*)c->reg.p, c->ntiles, emap,
+                                    (long long)ew * eh * ec, tiles, c->tile_elems, sidx, kfs, cf,
+                                    coeffs64, summary, batch, c->loss_kind, c->loss_a);
+        if (apply)
+            launch_apply_disp_planar(c->stream, (const TileGeom*)c->geom.p,
+                                     (const RayTile*)c->ray.p, (const double*)c->ray_tab.p,
+                                     c->ntiles, c->tile_elems / c->tile_c, tiles, tiles,
+                                     c->tile_elems, cf, batch);
+    } else {
         StageTimer t(c, PF_STAGE_REGISTER,
                      batch * (8.0 * nsamp + (apply ? 8.0 * (double)c->tile_elems / c->tile_c : 0.0)),
                      apply ? 2 : 1);

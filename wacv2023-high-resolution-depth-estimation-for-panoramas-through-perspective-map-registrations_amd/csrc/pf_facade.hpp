@@ -48,6 +48,8 @@ inline int apply_loss(pf_ctx* c, const RegLossRule& r)
 {
     return pf_set_register_loss(c, r.kind, r.a);
 }
+// What the tiles hold (SetTileDepth): PF_TILE_DEPTH_*, carried the same way.
+int tile_depth();
 // "huber:A" or "softl1:A" with a finite A > 0 (PF_REG_LOSS / --reg-loss).
 inline bool parse_reg_loss(const char* s, RegLossRule& r)
 {

@@ -332,11 +332,12 @@ static int fuse_impl(pf_ctx* c, const float* emap, int ew, int eh, int ec, const
                       (float*)c->lnorm.p);
 }
 
-// pf_register / pf_register_ex.  The launchers branch on the context's loss: without one this
-// launches what pf_register always did.
+// pf_register / pf_register_ex.  The launchers branch on the context's loss and tile depth:
+// without either this launches what pf_register always did.  apply_dst (planar tiles only, with
+// apply): where the transformed tiles go; nullptr: in place.
 static int register_impl(pf_ctx* c, const float* emap, int ew, int eh, int ec, float* tiles,
                          int batch, float zr0, float zr1, int degree, int apply, float* coeffs,
-                         double* coeffs64, double* summary)
+                         double* coeffs64, double* summary, float* apply_dst = nullptr)
 {
     int rc;
     if ((rc = check_common(c, batch))) return rc;
@@ -364,7 +365,31 @@ static int register_impl(pf_ctx* c, const float* emap, int ew, int eh, int ec, f
     for (const RegGrid& g : c->reg_h) nsamp += (double)(g.cols + 1) * (g.rows + 1);
     const int2* sidx = reg_sample_index(c, ew, eh, ec);  // before the stage timer: built once
     if (robust && !sidx) return fail(c, PF_EHIP, "robust registration: no sample-index table");
-    {
+    const bool planar = c->tile_depth == PF_TILE_DEPTH_PLANAR;
+    const float* kfs = planar ? reg_sample_kf(c, ew, eh, ec) : nullptr;
+    if (planar && !kfs) return fail(c, PF_EHIP, "planar registration: no sample ray-factor table");
+    if (planar) {
+        const TileGeom* geom = (const TileGeom*)c->geom.p;
+        const RegGrid* reg = (const RegGrid*)c->reg.p;
+        const long long estride = (long long)ew * eh * ec;
+        StageTimer t(c, PF_STAGE_REGISTER,
+                     batch * (12.0 * nsamp + (apply ? 8.0 * (double)c->tile_elems / c->tile_c : 0.0)),
+                     apply ? 2 : 1);
+        if (robust)
+            launch_register_robust_planar(c->stream, geom, reg, c->ntiles, emap, estride, tiles,
+                                          c->tile_elems, sidx, kfs, cf, coeffs64, summary, batch,
+                                          c->loss_kind, c->loss_a, c->valid);
+        else
+            launch_register_planar(c->stream, geom, reg, c->ntiles, emap, estride, tiles,
+                                   c->tile_elems, degree, c->solver, cf, coeffs64, batch, sidx, kfs,
+                                   c->valid);
+        if (apply)
+            launch_apply_cubic_planar(c->stream, geom, (const RayTile*)c->ray.p,
+                                      (const double*)c->ray_tab.p, c->ntiles,
+                                      c->tile_elems / c->tile_c, tiles,
+                                      apply_dst ? apply_dst : tiles, c->tile_elems, cf, batch,
+                                      c->valid);
+    } else {
         StageTimer t(c, PF_STAGE_REGISTER,
                      batch * (8.0 * nsamp + (apply ? 8.0 * (double)c->tile_elems / c->tile_c : 0.0)),
                      apply ? 2 : 1);
@@ -425,6 +450,7 @@ int pf_fuse(pf_ctx* c, const float* emap, int ew, int eh, int ec, const float* t
     if ((rc = check_common(c, batch))) return rc;
     if ((rc = check_emap(c, emap, ew, eh, ec))) return rc;
     if (!tiles || !out) return fail(c, PF_EINVAL, "tiles/out is NULL");
+    if ((rc = check_ray_coeffs(c, "pf_fuse", coeffs))) return rc;
     if ((rc = jres_check(c))) return rc;  // an earlier fusion's timeout, once it has landed
     return fuse_impl(c, emap, ew, eh, ec, tiles, coeffs, batch, out_w, out_h, zr0, zr1, out);
 }
@@ -442,6 +468,23 @@ int pf_merge(pf_ctx* c, const float* emap, int ew, int eh, int ec, const float* 
         if ((rc = ensure(c, c->coeffs, sizeof(float) * 4 * c->ntiles * batch))) return rc;
         cf = (float*)c->coeffs.p;
     }
+    if (c->tile_depth == PF_TILE_DEPTH_PLANAR) {
+        // planar-depth tiles: the fused-transform gather has no ray factor, so the planar fit is
+        // applied into a copy of the tiles, which is fused without coefficients.  Its invalid
+        // pixels are the NaNs apply wrote: the copy is fused under (-inf, +inf), not under the
+        // caller's lo / hi (a value clamped to exactly 0 is valid).
+        if ((rc = ensure(c, c->disp_tiles, sizeof(float) * (size_t)c->tile_elems * batch)))
+            return rc;
+        float* copy = (float*)c->disp_tiles.p;
+        if ((rc = register_impl(c, emap, ew, eh, ec, const_cast<float*>(tiles), batch, zr0, zr1, 3,
+                                1, cf, nullptr, nullptr, copy)))
+            return rc;
+        const TileValid rule = c->valid;
+        if (rule.on) c->valid = TileValid{1, -INFINITY, INFINITY};
+        rc = fuse_impl(c, emap, ew, eh, ec, copy, nullptr, batch, out_w, out_w / 2, zr0, zr1, out);
+        c->valid = rule;
+        return rc;
+    }
     if ((rc = pf_register(c, emap, ew, eh, ec, const_cast<float*>(tiles), batch, zr0, zr1, 3, 0,
                           cf, nullptr)))
         return rc;
@@ -455,6 +498,10 @@ int pf_register_joint(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
     int rc;
     if ((rc = check_common(c, batch))) return rc;
     if ((rc = check_no_loss(c, "pf_register_joint"))) return rc;
+    if (c->tile_depth != PF_TILE_DEPTH_RAY)
+        return fail(c, PF_ESTATE,
+                    "pf_register_joint has no planar-depth form: call pf_set_tile_depth(ctx, "
+                    "PF_TILE_DEPTH_RAY) first");
     if ((rc = check_emap(c, emap, ew, eh, ec))) return rc;
     if (!tiles || !active) return fail(c, PF_EINVAL, "tiles/active is NULL");
     if (degree < 0 || degree > 3) return fail(c, PF_EINVAL, "degree %d not in [0,3]", degree);

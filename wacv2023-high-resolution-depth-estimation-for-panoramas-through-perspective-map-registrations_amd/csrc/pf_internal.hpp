@@ -67,6 +67,11 @@ struct RegGrid {
     int soff;                          // first sample of this tile in the sample-index table
 };
 
+// Where a tile's ray-factor tables (pf_ray.hpp: cu[w], rv[h]) start in the layout's fp64 table.
+struct RayTile {
+    int cu, rv;
+};
+
 // GL camera of SaveCubeMap (Main.cpp:246-269) per tile, evaluated on the host in double.
 struct RgbCam {
     double f[3], s[3], u[3];
@@ -386,6 +391,38 @@ void launch_register_robust(hipStream_t s, const TileGeom* geom, const RegGrid* 
                             long long tstride, const int2* sidx, float* coeffs, double* coeffs64,
                             double* summary, int batch, int loss_kind, double loss_a,
                             TileValid tv);
+// Planar-depth tiles (pf_set_tile_depth): the ray factor kf of every tile pixel / of every
+// registration sample (kfs, next to sidx), and the registrations and transforms composed with it.
+// The planar registrations need sidx and kfs; summaries and tv as their plain counterparts'.  The
+// planar transforms write clamp01(kf * T32(x)) from src to dst (equal: in place).
+void launch_ray_factor(hipStream_t s, const TileGeom* geom, const RayTile* ray, const double* tab,
+                       int ntiles, long long tile_pixels, float* out);
+void launch_reg_kf(hipStream_t s, const TileGeom* geom, const RegGrid* grids, const RayTile* ray,
+                   const double* tab, int ntiles, int max_samples, const int2* sidx, float* kfs);
+void launch_register_planar(hipStream_t s, const TileGeom* geom, const RegGrid* grids, int ntiles,
+                            const float* emap, long long estride, const float* tiles,
+                            long long tstride, int degree, int solver, float* coeffs,
+                            double* coeffs64, int batch, const int2* sidx, const float* kfs,
+                            TileValid tv);
+void launch_register_robust_planar(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
+                                   int ntiles, const float* emap, long long estride,
+                                   const float* tiles, long long tstride, const int2* sidx,
+                                   const float* kfs, float* coeffs, double* coeffs64,
+                                   double* summary, int batch, int loss_kind, double loss_a,
+                                   TileValid tv);
+void launch_register_disp_planar(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
+                                 int ntiles, const float* emap, long long estride,
+                                 const float* tiles, long long tstride, const int2* sidx,
+                                 const float* kfs, float* coeffs, double* coeffs64,
+                                 double* summary, int batch, int loss_kind, double loss_a);
+void launch_apply_cubic_planar(hipStream_t s, const TileGeom* geom, const RayTile* ray,
+                               const double* tab, int ntiles, long long tile_pixels,
+                               const float* src, float* dst, long long tstride,
+                               const float* coeffs, int batch, TileValid tv);
+void launch_apply_disp_planar(hipStream_t s, const TileGeom* geom, const RayTile* ray,
+                              const double* tab, int ntiles, long long tile_pixels,
+                              const float* src, float* dst, long long tstride,
+                              const float* coeffs, int batch);
 // D2DTransform (Depth.cpp:214-243) on all tiles / on one map, channel 0, in place
 void launch_apply_disp(hipStream_t s, const TileGeom* geom, int ntiles, long long tile_pixels,
                        float* tiles, long long tstride, const float* coeffs, int batch);

@@ -5,6 +5,7 @@
 // panorama runs on the GPU.
 #include "pf_ctx.hpp"
 #include "pf_geom.hpp"
+#include "pf_ray.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -225,6 +226,17 @@ int pf_set_tiles(pf_ctx* c, const pf_window* fovs, const pf_window* ranges, int 
     c->wmap_pw = c->wmap_ph = 0;
     c->rgb_pw = c->rgb_ph = 0;
     c->cams_h = cams;
+    // the ray-factor tables of planar-depth tiles (pf_set_tile_depth): sum (w + h) doubles
+    c->ray_h.resize(ntiles);
+    c->ray_tab_h.clear();
+    for (int i = 0; i < ntiles; i++) {
+        const size_t at = c->ray_tab_h.size();
+        c->ray_h[i] = RayTile{(int)at, (int)at + tile_w[i]};
+        c->ray_tab_h.resize(at + (size_t)tile_w[i] + (size_t)tile_h[i]);
+        ray_tables(fovs[i].az_left, fovs[i].az_right, fovs[i].zen_top, fovs[i].zen_down, tile_w[i],
+                   tile_h[i], &c->ray_tab_h[at], &c->ray_tab_h[at + tile_w[i]]);
+    }
+    c->reg_kf_key[0] = -1;
     std::vector<WarpPatch> patches;
     const int pe = warp_patch_edge(), peh = warp_patch_height();
     for (int i = 0; i < ntiles; i++)
@@ -236,7 +248,44 @@ int pf_set_tiles(pf_ctx* c, const pf_window* fovs, const pf_window* ranges, int 
     if ((rc = upload(c, c->wpatch, patches))) return rc;
     if ((rc = upload(c, c->geom, c->geom_h))) return rc;
     if ((rc = upload(c, c->rgb_off, rgb_off))) return rc;
+    if ((rc = upload(c, c->ray_tab, c->ray_tab_h))) return rc;
+    if ((rc = upload(c, c->ray, c->ray_h))) return rc;
     c->layout_ok = true;
+    return PF_OK;
+}
+
+int pf_set_tile_depth(pf_ctx* c, int kind)
+{
+    if (!c) return PF_EINVAL;
+    if (kind != PF_TILE_DEPTH_RAY && kind != PF_TILE_DEPTH_PLANAR)
+        return fail(c, PF_EINVAL, "pf_set_tile_depth: unknown kind %d", kind);
+    c->tile_depth = kind;
+    return PF_OK;
+}
+
+int pf_tile_ray_tables(pf_ctx* c, int tile, double* cu, double* rv)
+{
+    if (!c) return PF_EINVAL;
+    if (c->ntiles <= 0 || !c->layout_ok)
+        return fail(c, PF_ESTATE, "no tile layout: call pf_set_tiles first");
+    if (tile < 0 || tile >= c->ntiles || !cu || !rv)
+        return fail(c, PF_EINVAL, "pf_tile_ray_tables: bad arguments (tile %d of %d)", tile,
+                    c->ntiles);
+    const RayTile rt = c->ray_h[tile];
+    memcpy(cu, &c->ray_tab_h[rt.cu], sizeof(double) * c->tw_h[tile]);
+    memcpy(rv, &c->ray_tab_h[rt.rv], sizeof(double) * c->th_h[tile]);
+    return PF_OK;
+}
+
+int pf_tile_ray_factor(pf_ctx* c, float* k)
+{
+    int rc;
+    if ((rc = check_common(c, 1))) return rc;
+    if (!c->layout_ok) return fail(c, PF_ESTATE, "no tile layout: call pf_set_tiles first");
+    if (!k) return fail(c, PF_EINVAL, "pf_tile_ray_factor: k is NULL");
+    launch_ray_factor(c->stream, (const TileGeom*)c->geom.p, (const RayTile*)c->ray.p,
+                      (const double*)c->ray_tab.p, c->ntiles, c->tile_elems / c->tile_c, k);
+    HIPCHK(c, hipGetLastError());
     return PF_OK;
 }
 
@@ -321,6 +370,7 @@ int pf::prepare_registration(pf_ctx* c, float zr0, float zr1)
     if ((rc = upload(c, c->rrows, rrows))) return rc;
     c->reg_valid = true;
     c->reg_sidx_key[0] = -1;  // the sample indices follow the grids
+    c->reg_kf_key[0] = -1;
     c->reg_zr0 = b0;
     c->reg_zr1 = b1;
     return PF_OK;
@@ -348,6 +398,32 @@ const int2* pf::reg_sample_index(pf_ctx* c, int ew, int eh, int ec)
     c->reg_sidx_key[1] = eh;
     c->reg_sidx_key[2] = ec;
     return (const int2*)c->reg_sidx.p;
+}
+
+// The samples' ray factor (k_reg_kf) for the sample indices of this baseline size; rebuilt when
+// they are.  Stream-ordered before the planar registrations that read it.
+const float* pf::reg_sample_kf(pf_ctx* c, int ew, int eh, int ec)
+{
+    const int2* sidx = reg_sample_index(c, ew, eh, ec);
+    if (!sidx) return nullptr;
+    if (c->reg_kf_key[0] == ew && c->reg_kf_key[1] == eh && c->reg_kf_key[2] == ec)
+        return (const float*)c->reg_kf.p;
+    long long n = 0;
+    int maxn = 0;
+    for (const RegGrid& g : c->reg_h) {
+        const int k = (g.cols + 1) * (g.rows + 1);
+        n += k;
+        maxn = k > maxn ? k : maxn;
+    }
+    if (ensure(c, c->reg_kf, sizeof(float) * (size_t)n) != PF_OK) return nullptr;
+    launch_reg_kf(c->stream, (const TileGeom*)c->geom.p, (const RegGrid*)c->reg.p,
+                  (const RayTile*)c->ray.p, (const double*)c->ray_tab.p, c->ntiles, maxn, sidx,
+                  (float*)c->reg_kf.p);
+    if (hipGetLastError() != hipSuccess) return nullptr;
+    c->reg_kf_key[0] = ew;
+    c->reg_kf_key[1] = eh;
+    c->reg_kf_key[2] = ec;
+    return (const float*)c->reg_kf.p;
 }
 
 // The tiles that will be solved must have a non-empty sample grid (Depth.cpp:1334-1335 divides

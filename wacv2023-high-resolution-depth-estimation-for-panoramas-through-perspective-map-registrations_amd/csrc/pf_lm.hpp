@@ -33,6 +33,15 @@ __device__ __forceinline__ double clamp_sample(double v)
     return v;
 }
 
+// The ray factor of pixel (i, j) of a planar-depth tile (pf_set_tile_depth) from the layout's
+// column / row tables (pf_ray.hpp): two fp64 adds and an fp64 sqrt, rounded once to fp32 -- the one
+// definition of kf.
+__device__ __forceinline__ float ray_kf(const double* __restrict__ tab, const RayTile rt, int i,
+                                        int j)
+{
+    return (float)sqrt(1.0 + tab[rt.cu + i] + tab[rt.rv + j]);
+}
+
 // The halving tree over the 256 lanes' partial sums, every lane receiving the totals.  Strides
 // 128 and 64 are wave 0 reading the four waves' values from LDS, strides 32..1 its lane shifts:
 // the same additions in the same association as p[l] = p[l] + p[l + stride].

@@ -4,7 +4,7 @@
 //                 [--metrics-order tree|sequential] [--edge-metrics]
 //                 [--tile-model depth|disparity] [--global-align] [--layout NAME|FILE]
 //                 [--fusion laplacian|smoothing|stitch] [--save-stitch] [--check-laplacian]
-//                 [--tile-valid LO:HI]
+//                 [--tile-valid LO:HI] [--reg-loss huber:A|softl1:A] [--tile-depth planar|ray]
 //   panofuse_main export <rgb_dir> <tile_dir> [--device D] [--layout NAME|FILE]
 //   panofuse_main layout NAME|FILE [--width W] [--tile-size WxH] [--device D]
 //   panofuse_main lap <gt_file> <given_file> [--device D]
@@ -69,7 +69,15 @@
 // SoftLOneLoss(A) (pf_set_register_loss), and the run prints per tile "[robust] tile <i>: <m> of
 // <n> samples beyond a=<A>, cost <c0> -> <c1>, <it> iterations, <termination>".  Not with
 // --global-align.  Carried in PF_REG_LOSS; not in the usage text either.
+// --tile-depth planar|ray (opt-in): what the tiles hold (pf_set_tile_depth).  ray (the default) is
+// distance from the camera centre, as the reference assumes; planar is depth along the optical
+// axis, what perspective depth networks predict.  Under planar the registration fits the tile
+// model times the pixel's ray factor and transforms the uploaded tiles, --fusion, --save-stitch and
+// --check-laplacian run on those without coefficients, and the run prints per panorama
+// "[tile-depth] planar: ray factor up to <max> over <n> tiles".  Works with both --tile-model
+// values.  Carried in PF_TILE_DEPTH; not in the usage text either.
 #include "pf_facade.hpp"  // the inline to_window and load_pair; it includes the two public headers
+#include "pf_ray.hpp"
 #include "pf_valid.hpp"
 
 #include <cstdio>
@@ -351,6 +359,10 @@ static int mode0_command(int argc, char* argv[])
             pff::RegLossRule r;
             if (!pff::parse_reg_loss(v.c_str(), r)) return bad(k, v, "huber:A or softl1:A, A > 0");
             setenv("PF_REG_LOSS", v.c_str(), 1);  // read by MergeDepthMaps / MergeDisparityMaps
+        }
+        else if (k == "--tile-depth") {
+            if (pf::parse_tile_depth(v.c_str()) < 0) return bad(k, v, "planar or ray");
+            setenv("PF_TILE_DEPTH", v.c_str(), 1);  // read by MergeDepthMaps / MergeDisparityMaps
         }
         else if (k == "--shard") {  // R/N: one process per GPU over the sorted folder
             if (std::sscanf(v.c_str(), "%d/%d", &shard, &nshards) != 2 || nshards < 1 ||

@@ -2,7 +2,9 @@
 // (k_register, k_register_valid), their solve by least squares or by the reference's Ceres 1.13
 // trust-region LM (lm_moments over lm_solve, pf_lm.hpp), the joint and global solves on the same
 // sums (k_register_joint, k_global_solve), the cached sample indices (k_regidx) and
-// Depth2DepthTransform (k_apply_cubic, k_d2d_map).
+// Depth2DepthTransform (k_apply_cubic, k_d2d_map); for planar-depth tiles (pf_set_tile_depth) the
+// ray factor (k_ray_factor, k_reg_kf), the moment sums weighted by it (k_register_planar,
+// k_register_planar_valid) and the transform composed with it (k_apply_cubic_planar).
 #include "pf_lm.hpp"
 
 namespace pf {
@@ -139,13 +141,14 @@ __device__ void solve_store(const double* S, int degree, int solver, float* coef
 }
 
 // The masked rule's store (pf_set_tile_validity): four quiet NaNs for a problem with fewer than
-// degree + 1 valid samples (S[9] is their count) or with a non-finite solution.
+// degree + 1 valid samples (count: S[9] for the plain sums, the 16th sum under the ray factor,
+// whose S[9] is the sum of K K) or with a non-finite solution.
 __device__ void solve_store_valid(const double* S, int degree, int solver, float* coeffs,
-                                  double* coeffs64, long long o)
+                                  double* coeffs64, long long o, double count)
 {
     float c32[4];
     double c64[4];
-    bool ok = S[9] >= (double)(degree + 1);
+    bool ok = count >= (double)(degree + 1);
     if (ok) {
         solve_store(S, degree, solver, c32, c64, 0);
         for (int i = 0; i < 4; i++) ok = ok && isfinite(c64[i]);
@@ -156,11 +159,23 @@ __device__ void solve_store_valid(const double* S, int degree, int solver, float
     }
 }
 
+__device__ void solve_store_valid(const double* S, int degree, int solver, float* coeffs,
+                                  double* coeffs64, long long o)
+{
+    solve_store_valid(S, degree, solver, coeffs, coeffs64, o, S[9]);
+}
+
 // One block's registration of tile p of panorama b.  MASK (k_register_valid): a sample whose raw
 // tile value fails the rule, or whose baseline value is not finite, adds nothing to the sums; the
 // lane-to-sample assignment and the halving tree are the unmasked ones, so acc[9] is the count of
 // valid samples.  With MASK false this is k_register as it was.
-template <bool MASK>
+// PLANAR (k_register_planar, k_register_planar_valid; pf_set_tile_depth): the tile holds depth along
+// the optical axis, so the model is K (a X^3 + b X^2 + c X + d) with K = (double)kfs[sample], the
+// sample's ray factor (k_reg_kf).  The Jacobian row is e = (K X^3, K X^2, K X, K) and the 15 sums
+// keep their positions with e in place of (X^3, X^2, X, 1): they are J'J, J'y and y'y of the
+// weighted problem, which solve_normal and lm_moments take unchanged.  acc[9] is then the sum of
+// K K, so under MASK the count of valid samples travels in a 16th sum.  Needs sidx.
+template <bool MASK, bool PLANAR = false>
 __device__ __forceinline__ void register_tile(
     const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids,
     const GridCol* __restrict__ rcols, const GridRow* __restrict__ rrows, int ntiles,
@@ -168,8 +183,9 @@ __device__ __forceinline__ void register_tile(
     const float* __restrict__ tiles, long long tstride, int degree, int solver,
     float* __restrict__ coeffs, double* __restrict__ coeffs64, double* __restrict__ sums,
     const int* __restrict__ active, const int2* __restrict__ sidx, float vlo, float vhi,
-    double (*part)[kRegLanes])
+    double (*part)[kRegLanes], const float* __restrict__ kfs = nullptr)
 {
+    constexpr int kNS = PLANAR && MASK ? kRegSums + 1 : kRegSums;
     // one linear grid, XCD-contiguous: the tiles of one panorama run on one XCD, so its emap is
     // fetched into one L2 (the samples of neighbouring tiles overlap in the emap)
     const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
@@ -181,25 +197,28 @@ __device__ __forceinline__ void register_tile(
     const float* em = emap + b * estride;
     const int ncol = rg.cols + 1;
     const int ns = ncol * (rg.rows + 1);
-    double acc[kRegSums];
+    double acc[kNS];
 #pragma unroll
-    for (int k = 0; k < kRegSums; k++) acc[k] = 0.0;
+    for (int k = 0; k < kNS; k++) acc[k] = 0.0;
     // The lane's samples l, l + 256, ... in groups of kRegU: the gathers of a group are issued
     // together (they are independent), then added in sample order -- the same per-lane order as
     // one sample per iteration, so the sums are unchanged bit for bit.
     constexpr int kRegU = 4;
     for (int s0 = l; s0 < ns; s0 += kRegU * kRegLanes) {
         float tv[kRegU], ev[kRegU];
+        float kv[PLANAR ? kRegU : 1];
 #pragma unroll
         for (int u = 0; u < kRegU; u++) {
             const int s = s0 + u * kRegLanes;
             tv[u] = 0.0f;
             ev[u] = 0.0f;
+            if constexpr (PLANAR) kv[u] = 1.0f;
             if (s >= ns) continue;
-            if (sidx) {  // the cached indices (k_regidx: the same arithmetic as below)
+            if (PLANAR || sidx) {  // the cached indices (k_regidx: the same arithmetic as below)
                 const int2 ix = sidx[rg.soff + s];
                 tv[u] = tile[ix.x];
                 ev[u] = em[ix.y];
+                if constexpr (PLANAR) kv[u] = kfs[rg.soff + s];
                 continue;
             }
             int r = s / ncol, c = s - r * ncol;
@@ -222,6 +241,19 @@ __device__ __forceinline__ void register_tile(
             double X = clamp_sample((double)tv[u]);
             double Yv = clamp_sample((double)ev[u]);
             double X2 = X * X, X3 = X * X * X;
+            if constexpr (PLANAR) {
+                const double K = (double)kv[u];
+                const double e3 = K * X3, e2 = K * X2, e1 = K * X, e0 = K;
+                acc[0] = acc[0] + e3 * e3; acc[1] = acc[1] + e3 * e2; acc[2] = acc[2] + e3 * e1;
+                acc[3] = acc[3] + e3 * e0; acc[4] = acc[4] + e2 * e2; acc[5] = acc[5] + e2 * e1;
+                acc[6] = acc[6] + e2 * e0; acc[7] = acc[7] + e1 * e1; acc[8] = acc[8] + e1 * e0;
+                acc[9] = acc[9] + e0 * e0;
+                acc[10] = acc[10] + e3 * Yv; acc[11] = acc[11] + e2 * Yv;
+                acc[12] = acc[12] + e1 * Yv; acc[13] = acc[13] + e0 * Yv;
+                acc[14] = acc[14] + Yv * Yv;
+                if constexpr (MASK) acc[15] = acc[15] + 1.0;
+                continue;
+            }
             acc[0] = acc[0] + X3 * X3; acc[1] = acc[1] + X3 * X2; acc[2] = acc[2] + X3 * X;
             acc[3] = acc[3] + X3;      acc[4] = acc[4] + X2 * X2; acc[5] = acc[5] + X2 * X;
             acc[6] = acc[6] + X2;      acc[7] = acc[7] + X * X;   acc[8] = acc[8] + X;
@@ -232,21 +264,24 @@ __device__ __forceinline__ void register_tile(
         }
     }
 #pragma unroll
-    for (int k = 0; k < kRegSums; k++) part[k][l] = acc[k];
+    for (int k = 0; k < kNS; k++) part[k][l] = acc[k];
     __syncthreads();
     for (int stride = kRegLanes / 2; stride >= 1; stride >>= 1) {
         if (l < stride)
-            for (int k = 0; k < kRegSums; k++) part[k][l] = part[k][l] + part[k][l + stride];
+            for (int k = 0; k < kNS; k++) part[k][l] = part[k][l] + part[k][l + stride];
         __syncthreads();
     }
     if (l == 0) {
-        double S[kRegSums];
-        for (int k = 0; k < kRegSums; k++) S[k] = part[k][0];
+        double S[kNS];
+        for (int k = 0; k < kNS; k++) S[k] = part[k][0];
         if (sums) {  // joint solve: hand the tile's normal-equation sums to k_register_joint
             for (int k = 0; k < kRegSums; k++) sums[((long long)b * ntiles + p) * kRegSums + k] = S[k];
             return;
         }
-        if constexpr (MASK)
+        if constexpr (MASK && PLANAR)
+            solve_store_valid(S, degree, solver, coeffs, coeffs64, ((long long)b * ntiles + p) * 4,
+                              S[kRegSums]);
+        else if constexpr (MASK)
             solve_store_valid(S, degree, solver, coeffs, coeffs64, ((long long)b * ntiles + p) * 4);
         else
             solve_store(S, degree, solver, coeffs, coeffs64, ((long long)b * ntiles + p) * 4);
@@ -279,6 +314,32 @@ __global__ void __launch_bounds__(kRegLanes) k_register_valid(
     register_tile<true>(geom, grids, rcols, rrows, ntiles, emap, ew, eh, ec, estride, tiles,
                         tstride, degree, solver, coeffs, coeffs64, sums, active, sidx, vlo, vhi,
                         part);
+}
+
+// The same under PF_TILE_DEPTH_PLANAR: kfs is the samples' ray factor (k_reg_kf), sidx is required.
+__global__ void __launch_bounds__(kRegLanes) k_register_planar(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, int degree, int solver, float* __restrict__ coeffs,
+    double* __restrict__ coeffs64, const int2* __restrict__ sidx, const float* __restrict__ kfs)
+{
+    __shared__ double part[kRegSums][kRegLanes];
+    register_tile<false, true>(geom, grids, nullptr, nullptr, ntiles, emap, 0, 0, 0, estride,
+                               tiles, tstride, degree, solver, coeffs, coeffs64, nullptr, nullptr,
+                               sidx, 0.0f, 0.0f, part, kfs);
+}
+
+__global__ void __launch_bounds__(kRegLanes) k_register_planar_valid(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, int degree, int solver, float* __restrict__ coeffs,
+    double* __restrict__ coeffs64, const int2* __restrict__ sidx, const float* __restrict__ kfs,
+    float vlo, float vhi)
+{
+    __shared__ double part[kRegSums + 1][kRegLanes];
+    register_tile<true, true>(geom, grids, nullptr, nullptr, ntiles, emap, 0, 0, 0, estride, tiles,
+                              tstride, degree, solver, coeffs, coeffs64, nullptr, nullptr, sidx,
+                              vlo, vhi, part, kfs);
 }
 
 // pf_tile_valid_counts: block (p, b) counts the registration samples k_register_valid keeps and
@@ -378,6 +439,97 @@ __global__ void __launch_bounds__(kBlock) k_apply_cubic_valid(const TileGeom* __
         t[i * g.c] = tile_ok(v, vlo, vhi) ? cubic_map(v, abcd.x, abcd.y, abcd.z, abcd.w)
                                           : __uint_as_float(0x7FC00000u);
     }
+}
+
+// ---- planar-depth tiles (pf_set_tile_depth) ---------------------------------------------------
+// pf_tile_ray_factor: kf of every tile pixel, layout order (one float per pixel, no channels).
+__global__ void __launch_bounds__(kBlock) k_ray_factor(const TileGeom* __restrict__ geom,
+                                                       const RayTile* __restrict__ ray,
+                                                       const double* __restrict__ tab,
+                                                       float* __restrict__ out)
+{
+    const int p = blockIdx.y;
+    const TileGeom g = geom[p];
+    const RayTile rt = ray[p];
+    const int npx = g.w * g.h;
+    float* o = out + g.pix_off;
+    // i stays below npx <= INT32_MAX inside the loop; the 64-bit counter only keeps the stride add
+    // from wrapping
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < npx;
+         i += (long long)gridDim.x * kBlock)
+        o[i] = ray_kf(tab, rt, (int)i % g.w, (int)i / g.w);
+}
+
+// The registration samples' ray factor, next to their indices (k_regidx): sample s of tile p reads
+// tile element sidx[s].x, i.e. pixel sidx[s].x / c.  Layout- and baseline-size-only, built once,
+// so the sample-wise solvers' 8-27 passes load a float instead of taking an fp64 sqrt.
+__global__ void __launch_bounds__(256) k_reg_kf(const TileGeom* __restrict__ geom,
+                                                const RegGrid* __restrict__ grids,
+                                                const RayTile* __restrict__ ray,
+                                                const double* __restrict__ tab,
+                                                const int2* __restrict__ sidx,
+                                                float* __restrict__ kfs)
+{
+    const int p = blockIdx.y;
+    const TileGeom g = geom[p];
+    const RegGrid rg = grids[p];
+    const RayTile rt = ray[p];
+    const int ns = (rg.cols + 1) * (rg.rows + 1);
+    for (int s = blockIdx.x * 256 + threadIdx.x; s < ns; s += gridDim.x * 256) {
+        const int pix = sidx[rg.soff + s].x / g.c;
+        kfs[rg.soff + s] = ray_kf(tab, rt, pix % g.w, pix / g.w);
+    }
+}
+
+// Depth2DepthTransform composed with the ray factor, src -> dst (in place when they are equal):
+// clamp01(kf * T32(X)), T32 = cubic_map's fp32 value before its final clamp, in its operation
+// order; one fp32 multiply by kf (the unit is built without contraction); NaN stays NaN.  VALID:
+// a pixel that fails the rule becomes a quiet NaN.
+template <bool VALID>
+__device__ __forceinline__ void apply_cubic_planar(const TileGeom* __restrict__ geom,
+                                                   const RayTile* __restrict__ ray,
+                                                   const double* __restrict__ tab, int ntiles,
+                                                   const float* src, float* dst, long long tstride,
+                                                   const float* __restrict__ coeffs, float vlo,
+                                                   float vhi)
+{
+    const int p = blockIdx.y, b = blockIdx.z;
+    const TileGeom g = geom[p];
+    const RayTile rt = ray[p];
+    const int npx = g.w * g.h;
+    const float4 abcd = *reinterpret_cast<const float4*>(coeffs + ((long long)b * ntiles + p) * 4);
+    const float* in = src + b * tstride + g.off;
+    float* t = dst + b * tstride + g.off;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < npx;
+         i += (long long)gridDim.x * kBlock) {
+        const float v = in[i * g.c];
+        float X = v;
+        if (X <= 9.99999974737875e-05f) X = (float)1e-4;  // cubic_map's clamps
+        else if (X > 0.99989998340606689f) X = (float)(1 - 1e-4);
+        float Y = abcd.x * X * X * X + abcd.y * X * X + abcd.z * X + abcd.w;
+        Y = ray_kf(tab, rt, (int)i % g.w, (int)i / g.w) * Y;
+        if (Y < 0) Y = 0;
+        else if (Y > 1) Y = 1;
+        if constexpr (VALID)
+            if (!tile_ok(v, vlo, vhi)) Y = __uint_as_float(0x7FC00000u);
+        t[i * g.c] = Y;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_apply_cubic_planar(
+    const TileGeom* __restrict__ geom, const RayTile* __restrict__ ray,
+    const double* __restrict__ tab, int ntiles, const float* src, float* dst, long long tstride,
+    const float* __restrict__ coeffs)
+{
+    apply_cubic_planar<false>(geom, ray, tab, ntiles, src, dst, tstride, coeffs, 0.0f, 0.0f);
+}
+
+__global__ void __launch_bounds__(kBlock) k_apply_cubic_planar_valid(
+    const TileGeom* __restrict__ geom, const RayTile* __restrict__ ray,
+    const double* __restrict__ tab, int ntiles, const float* src, float* dst, long long tstride,
+    const float* __restrict__ coeffs, float vlo, float vhi)
+{
+    apply_cubic_planar<true>(geom, ray, tab, ntiles, src, dst, tstride, coeffs, vlo, vhi);
 }
 
 // Depth2DepthTransform of one map (PerspectiveMap::Depth2DepthTransform, Depth.cpp:245-274),
@@ -528,6 +680,62 @@ void launch_apply_cubic(hipStream_t s, const TileGeom* geom, int ntiles, long lo
     else
         hipLaunchKernelGGL(k_apply_cubic, grid, dim3(kBlock), 0, s, geom, ntiles, tiles, tstride,
                            coeffs);
+}
+
+void launch_register_planar(hipStream_t s, const TileGeom* geom, const RegGrid* grids, int ntiles,
+                            const float* emap, long long estride, const float* tiles,
+                            long long tstride, int degree, int solver, float* coeffs,
+                            double* coeffs64, int batch, const int2* sidx, const float* kfs,
+                            TileValid tv)
+{
+    dim3 grid((unsigned)(ntiles * batch));
+    if (tv.on)
+        hipLaunchKernelGGL(k_register_planar_valid, grid, dim3(kRegLanes), 0, s, geom, grids,
+                           ntiles, emap, estride, tiles, tstride, degree, solver, coeffs, coeffs64,
+                           sidx, kfs, tv.lo, tv.hi);
+    else
+        hipLaunchKernelGGL(k_register_planar, grid, dim3(kRegLanes), 0, s, geom, grids, ntiles,
+                           emap, estride, tiles, tstride, degree, solver, coeffs, coeffs64, sidx,
+                           kfs);
+}
+
+static unsigned pixel_blocks(long long tile_pixels, int ntiles)
+{
+    unsigned gx = nblocks(tile_pixels / (ntiles > 0 ? ntiles : 1));
+    if (gx > 1024) gx = 1024;
+    if (gx == 0) gx = 1;
+    return gx;
+}
+
+void launch_ray_factor(hipStream_t s, const TileGeom* geom, const RayTile* ray, const double* tab,
+                       int ntiles, long long tile_pixels, float* out)
+{
+    hipLaunchKernelGGL(k_ray_factor, dim3(pixel_blocks(tile_pixels, ntiles), ntiles), dim3(kBlock),
+                       0, s, geom, ray, tab, out);
+}
+
+void launch_reg_kf(hipStream_t s, const TileGeom* geom, const RegGrid* grids, const RayTile* ray,
+                   const double* tab, int ntiles, int max_samples, const int2* sidx, float* kfs)
+{
+    unsigned gx = (unsigned)((max_samples + 255) / 256);
+    if (gx < 1) gx = 1;
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(k_reg_kf, dim3(gx, (unsigned)ntiles), dim3(256), 0, s, geom, grids, ray,
+                       tab, sidx, kfs);
+}
+
+void launch_apply_cubic_planar(hipStream_t s, const TileGeom* geom, const RayTile* ray,
+                               const double* tab, int ntiles, long long tile_pixels,
+                               const float* src, float* dst, long long tstride,
+                               const float* coeffs, int batch, TileValid tv)
+{
+    dim3 grid(pixel_blocks(tile_pixels, ntiles), ntiles, batch);
+    if (tv.on)
+        hipLaunchKernelGGL(k_apply_cubic_planar_valid, grid, dim3(kBlock), 0, s, geom, ray, tab,
+                           ntiles, src, dst, tstride, coeffs, tv.lo, tv.hi);
+    else
+        hipLaunchKernelGGL(k_apply_cubic_planar, grid, dim3(kBlock), 0, s, geom, ray, tab, ntiles,
+                           src, dst, tstride, coeffs);
 }
 
 void launch_d2d_map(hipStream_t s, float* data, long long npx, int c, const float* abcd)

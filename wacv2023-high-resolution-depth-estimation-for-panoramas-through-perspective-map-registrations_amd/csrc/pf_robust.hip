@@ -30,14 +30,37 @@ __device__ __forceinline__ double cubic_residual(double X, double Y, const doubl
     return (((X3 * p[0] + X2 * p[1]) + X * p[2]) + p[3]) - Y;
 }
 
-__device__ __forceinline__ void rob_terms(double X, double Y, const double p[4],
+// The same for a planar-depth tile (pf_set_tile_depth): the model is K times the cubic, K the
+// sample's ray factor, so r = K m - Y and the row is (K X3, K X2, K X, K).
+__device__ __forceinline__ double planar_residual(double X, double Y, double K, const double p[4],
+                                                  double& X2, double& X3)
+{
+    X2 = X * X;
+    X3 = X * X * X;
+    return K * (((X3 * p[0] + X2 * p[1]) + X * p[2]) + p[3]) - Y;
+}
+
+template <bool PLANAR>
+__device__ __forceinline__ void rob_terms(double X, double Y, double K, const double p[4],
                                           double acc[kRobSums], const RegLoss& L)
 {
     double X2, X3, rho0, rho1;
-    const double r = cubic_residual(X, Y, p, X2, X3);
+    const double r = PLANAR ? planar_residual(X, Y, K, p, X2, X3) : cubic_residual(X, Y, p, X2, X3);
     loss_eval(L, r * r, rho0, rho1);
     const double w = sqrt(rho1);
-    const double rc = w * r, j0 = w * X3, j1 = w * X2, j2 = w * X, j3 = w;
+    const double rc = w * r;
+    double j0, j1, j2, j3;
+    if constexpr (PLANAR) {
+        j0 = w * (K * X3);
+        j1 = w * (K * X2);
+        j2 = w * (K * X);
+        j3 = w * K;
+    } else {
+        j0 = w * X3;
+        j1 = w * X2;
+        j2 = w * X;
+        j3 = w;
+    }
     acc[0] = acc[0] + 0.5 * rho0;
     acc[1] = acc[1] + j0 * rc;
     acc[2] = acc[2] + j1 * rc;
@@ -55,11 +78,12 @@ __device__ __forceinline__ void rob_terms(double X, double Y, const double p[4],
     acc[14] = acc[14] + j3 * j3;
 }
 
-__device__ __forceinline__ void rob_cost_term(double X, double Y, const double p[4], double& acc,
-                                              const RegLoss& L)
+template <bool PLANAR>
+__device__ __forceinline__ void rob_cost_term(double X, double Y, double K, const double p[4],
+                                              double& acc, const RegLoss& L)
 {
     double X2, X3, rho0, rho1;
-    const double r = cubic_residual(X, Y, p, X2, X3);
+    const double r = PLANAR ? planar_residual(X, Y, K, p, X2, X3) : cubic_residual(X, Y, p, X2, X3);
     loss_eval(L, r * r, rho0, rho1);
     acc = acc + 0.5 * rho0;
 }
@@ -67,15 +91,18 @@ __device__ __forceinline__ void rob_cost_term(double X, double Y, const double p
 
 // MASK: under the validity rule (k_register_valid's: a sample whose raw tile value fails the rule,
 // or whose baseline value is not finite, is skipped and adds nothing).
-template <bool MASK>
-__global__ void __launch_bounds__(kDispLanes) k_register_robust(
+// PLANAR (k_register_robust_planar): with the samples' ray factor kfs (k_reg_kf).  The resident
+// registers hold (x, y) as before -- a third resident value per sample does not fit beside them --
+// and K is a float load from the cached table in every pass (coalesced: lane l reads
+// kfs[l + 256 u]), widened to fp64.  The lane-to-sample order is unchanged.
+template <bool MASK, bool PLANAR>
+__device__ __forceinline__ void register_robust_tile(
     const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
     const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
-    long long tstride, const int2* __restrict__ sidx, float* __restrict__ coeffs,
-    double* __restrict__ coeffs64, double* __restrict__ summary, RegLoss L, float vlo, float vhi)
+    long long tstride, const int2* __restrict__ sidx, const float* __restrict__ kfs,
+    float* __restrict__ coeffs, double* __restrict__ coeffs64, double* __restrict__ summary,
+    const RegLoss L, float vlo, float vhi, double (*part)[kDispLanes], double* tot)
 {
-    __shared__ double part[kRobSums][kDispLanes];
-    __shared__ double tot[kRobSums];
     // k_register_disp's block order: the tiles of one panorama on one XCD
     const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
     const int p = (int)(lb % (unsigned)ntiles), b = (int)(lb / (unsigned)ntiles), l = threadIdx.x;
@@ -84,6 +111,8 @@ __global__ void __launch_bounds__(kDispLanes) k_register_robust(
     const float* em = emap + b * estride;
     const int2* ix = sidx + rg.soff;
     const int ns = (rg.cols + 1) * (rg.rows + 1);
+    const float* kf = PLANAR ? kfs + rg.soff : nullptr;
+    auto Kof = [&](int s) { return PLANAR ? (double)kf[s] : 1.0; };
     auto kept = [&](float tv, float ev) {
         if constexpr (MASK) return tile_ok(tv, vlo, vhi) && isfinite(ev);
         return true;
@@ -106,7 +135,8 @@ __global__ void __launch_bounds__(kDispLanes) k_register_robust(
         }
     }
 
-    // each(f): f(X, Y) on the lane's kept samples in order, X and Y clamped in fp64.  The empty
+    // each(f): f(X, Y, K) on the lane's kept samples in order, X and Y clamped in fp64 (K: the
+    // constant 1.0, unused, without PLANAR).  The empty
     // asm keeps the compiler from widening the 64 resident floats to clamped doubles once and
     // holding those across the evaluations: that form spills to scratch.
     auto each = [&](auto&& f) {
@@ -115,19 +145,19 @@ __global__ void __launch_bounds__(kDispLanes) k_register_robust(
             if (live >> u & 1u) {
                 float xv = xs[u], yv = ys[u];
                 asm volatile("" : "+v"(xv), "+v"(yv));
-                f(clamp_sample((double)xv), clamp_sample((double)yv));
+                f(clamp_sample((double)xv), clamp_sample((double)yv), Kof(l + u * kDispLanes));
             }
         for (int s = l + kDispResident; s < ns; s += kDispLanes) {  // past the capacity
             const int2 i2 = ix[s];
             const float tv = tile[i2.x], ev = em[i2.y];
-            if (kept(tv, ev)) f(clamp_sample((double)tv), clamp_sample((double)ev));
+            if (kept(tv, ev)) f(clamp_sample((double)tv), clamp_sample((double)ev), Kof(s));
         }
     };
     auto eval_full = [&](const double (&q)[4], double& cost, double (&g)[4], double (&M)[4][4]) {
         double S[kRobSums];
 #pragma unroll
         for (int k = 0; k < kRobSums; k++) S[k] = 0.0;
-        each([&](double X, double Y) { rob_terms(X, Y, q, S, L); });
+        each([&](double X, double Y, double K) { rob_terms<PLANAR>(X, Y, K, q, S, L); });
         disp_reduce<kRobSums>(S, part, tot, l);
         cost = S[0];
         int at = 5;  // upper J'J, row-major
@@ -138,7 +168,7 @@ __global__ void __launch_bounds__(kDispLanes) k_register_robust(
     };
     auto eval_cost = [&](const double (&q)[4]) {
         double c = 0.0;
-        each([&](double X, double Y) { rob_cost_term(X, Y, q, c, L); });
+        each([&](double X, double Y, double K) { rob_cost_term<PLANAR>(X, Y, K, q, c, L); });
         disp_reduce<1>(&c, part, tot, l);
         return c;
     };
@@ -148,7 +178,7 @@ __global__ void __launch_bounds__(kDispLanes) k_register_robust(
     double used = (double)ns;
     if constexpr (MASK) {
         used = 0.0;
-        each([&](double, double) { used = used + 1.0; });
+        each([&](double, double, double) { used = used + 1.0; });
         disp_reduce<1>(&used, part, tot, l);
         if (used < 4.0) {  // block-uniform: too few samples for the four coefficients
             if (l == 0) {
@@ -178,9 +208,10 @@ __global__ void __launch_bounds__(kDispLanes) k_register_robust(
 
     // one more pass at the returned parameters: the samples with r r <= a a (exact counts)
     double inliers = 0.0;
-    each([&](double X, double Y) {
+    each([&](double X, double Y, double K) {
         double X2, X3;
-        const double r = cubic_residual(X, Y, best, X2, X3);
+        const double r =
+            PLANAR ? planar_residual(X, Y, K, best, X2, X3) : cubic_residual(X, Y, best, X2, X3);
         if (r * r <= L.b) inliers = inliers + 1.0;
     });
     disp_reduce<1>(&inliers, part, tot, l);
@@ -202,6 +233,52 @@ __global__ void __launch_bounds__(kDispLanes) k_register_robust(
             summary[o * 6 + 5] = inliers;
         }
     }
+}
+
+template <bool MASK>
+__global__ void __launch_bounds__(kDispLanes) k_register_robust(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, const int2* __restrict__ sidx, float* __restrict__ coeffs,
+    double* __restrict__ coeffs64, double* __restrict__ summary, RegLoss L, float vlo, float vhi)
+{
+    __shared__ double part[kRobSums][kDispLanes];
+    __shared__ double tot[kRobSums];
+    register_robust_tile<MASK, false>(geom, grids, ntiles, emap, estride, tiles, tstride, sidx,
+                                      nullptr, coeffs, coeffs64, summary, L, vlo, vhi, part, tot);
+}
+
+template <bool MASK>
+__global__ void __launch_bounds__(kDispLanes) k_register_robust_planar(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, const int2* __restrict__ sidx, const float* __restrict__ kfs,
+    float* __restrict__ coeffs, double* __restrict__ coeffs64, double* __restrict__ summary,
+    RegLoss L, float vlo, float vhi)
+{
+    __shared__ double part[kRobSums][kDispLanes];
+    __shared__ double tot[kRobSums];
+    register_robust_tile<MASK, true>(geom, grids, ntiles, emap, estride, tiles, tstride, sidx, kfs,
+                                     coeffs, coeffs64, summary, L, vlo, vhi, part, tot);
+}
+
+void launch_register_robust_planar(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
+                                   int ntiles, const float* emap, long long estride,
+                                   const float* tiles, long long tstride, const int2* sidx,
+                                   const float* kfs, float* coeffs, double* coeffs64,
+                                   double* summary, int batch, int loss_kind, double loss_a,
+                                   TileValid tv)
+{
+    const dim3 grid((unsigned)(ntiles * batch)), block(kDispLanes);
+    const RegLoss L = make_loss(loss_kind, loss_a);
+    if (tv.on)
+        hipLaunchKernelGGL(k_register_robust_planar<true>, grid, block, 0, s, geom, grids, ntiles,
+                           emap, estride, tiles, tstride, sidx, kfs, coeffs, coeffs64, summary, L,
+                           tv.lo, tv.hi);
+    else
+        hipLaunchKernelGGL(k_register_robust_planar<false>, grid, block, 0, s, geom, grids,
+                           ntiles, emap, estride, tiles, tstride, sidx, kfs, coeffs, coeffs64,
+                           summary, L, 0.0f, 0.0f);
 }
 
 void launch_register_robust(hipStream_t s, const TileGeom* geom, const RegGrid* grids, int ntiles,

@@ -64,6 +64,7 @@ int pf_fuse_partial(pf_ctx* c, const float* tiles, const float* coeffs, int t0, 
     const LevelDims* L = nullptr;
     if ((rc = check_common(c, 1))) return rc;
     if ((rc = check_unmasked(c, "pf_fuse_partial"))) return rc;
+    if ((rc = check_ray_coeffs(c, "pf_fuse_partial", coeffs))) return rc;
     if (!tiles || !lsum || !cnt) return fail(c, PF_EINVAL, "NULL buffer");
     if ((rc = check_tile_range(c, t0, t1))) return rc;
     if ((rc = level_at(c, out_w, out_h, zr0, zr1, level, &L))) return rc;
@@ -79,6 +80,7 @@ int pf_fuse_partial_rows(pf_ctx* c, const float* tiles, const float* coeffs, int
     int rc;
     const LevelDims* L = nullptr;
     if ((rc = check_unmasked(c, "pf_fuse_partial_rows"))) return rc;
+    if ((rc = check_ray_coeffs(c, "pf_fuse_partial_rows", coeffs))) return rc;
     if ((rc = level_rows(c, out_w, out_h, zr0, zr1, level, row0, row1, &L))) return rc;
     if (!tiles || !lsum || !cnt) return fail(c, PF_EINVAL, "NULL buffer");
     if ((rc = check_tile_range(c, t0, t1))) return rc;
@@ -242,6 +244,7 @@ int pf_fuse_targets(pf_ctx* c, const float* tiles, const float* coeffs, int out_
     int rc;
     const LevelDims* L = nullptr;
     if ((rc = check_common(c, 1))) return rc;
+    if ((rc = check_ray_coeffs(c, "pf_fuse_targets", coeffs))) return rc;
     if (!tiles || !lnorm) return fail(c, PF_EINVAL, "NULL buffer");
     if ((rc = level_at(c, out_w, out_h, zr0, zr1, level, &L))) return rc;
     const LevelCache& lc = c->lc;
@@ -340,6 +343,7 @@ int pf_fuse_multicover(pf_ctx* c, const float* tiles, const float* coeffs, int t
     const LevelDims* L = nullptr;
     if ((rc = check_common(c, 1))) return rc;
     if ((rc = check_unmasked(c, "pf_fuse_multicover"))) return rc;
+    if ((rc = check_ray_coeffs(c, "pf_fuse_multicover", coeffs))) return rc;
     if ((rc = level_at(c, out_w, out_h, zr0, zr1, level, &L))) return rc;
     const LevelCache& lc = c->lc;
     if (npairs) *npairs = lc.nmc[level];

@@ -16,6 +16,7 @@ int pf_solve_smoothing(pf_ctx* c, const float* tiles, const float* coeffs, int b
     int rc;
     if ((rc = check_common(c, batch))) return rc;
     if ((rc = check_unmasked(c, "pf_solve_smoothing"))) return rc;
+    if ((rc = check_ray_coeffs(c, "pf_solve_smoothing", coeffs))) return rc;
     if ((rc = jres_check(c))) return rc;  // an earlier call's timeout, once it has landed
     if (!tiles || !out) return fail(c, PF_EINVAL, "tiles/out is NULL");
     if (out_w < 3 || out_h < 3 || (long long)out_w * out_h >= (1LL << 31))

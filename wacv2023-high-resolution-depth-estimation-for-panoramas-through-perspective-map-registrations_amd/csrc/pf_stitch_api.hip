@@ -14,6 +14,7 @@ int pf_stitch(pf_ctx* c, const float* tiles, const float* coeffs, int batch, int
 {
     int rc;
     if ((rc = check_common(c, batch))) return rc;
+    if ((rc = check_ray_coeffs(c, "pf_stitch", coeffs))) return rc;
     if (!tiles || !out) return fail(c, PF_EINVAL, "tiles/out is NULL");
     if (out_w < 2 || out_h < 2 || (long long)out_w * out_h >= (1LL << 31) - 512)
         return fail(c, PF_EINVAL, "output %dx%d out of range", out_w, out_h);
@@ -81,6 +82,7 @@ int pf_fuse_check(pf_ctx* c, const float* emap, int ew, int eh, int ec, const fl
 {
     int rc;
     if ((rc = check_common(c, 1))) return rc;
+    if ((rc = check_ray_coeffs(c, "pf_fuse_check", coeffs))) return rc;
     if ((rc = check_emap(c, emap, ew, eh, ec))) return rc;
     if (!tiles || !err) return fail(c, PF_EINVAL, "tiles/err is NULL");
     if ((rc = jres_check(c))) return rc;  // an earlier fusion's timeout, once it has landed

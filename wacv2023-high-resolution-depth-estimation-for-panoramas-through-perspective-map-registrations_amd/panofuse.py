@@ -38,6 +38,7 @@ EXPORTS = [
     "pf_result_transform", "pf_median_scale", "pf_copy_invalid", "pf_layout_audit",
     "pf_stitch", "pf_laplacian_residual", "pf_fuse_check", "pf_set_tile_validity",
     "pf_tile_valid_counts", "pf_set_register_loss", "pf_register_ex",
+    "pf_set_tile_depth", "pf_tile_ray_tables", "pf_tile_ray_factor",
 ]
 NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
           "pf_debug_smooth_fault", "pf_fuse_partial_rows", "pf_fuse_coverage_rows",
@@ -47,6 +48,7 @@ METRICS_ORDERS = {"tree": 0, "sequential": 1}  # PF_METRICS_*; "sequential" = th
 SOLVERS = {"normal": 0, "lm": 1}  # PF_SOLVER_*; "lm" = the reference's Ceres LM (default)
 PF_VALID_ALL, PF_VALID_RANGE = 0, 1  # pf_set_tile_validity's modes
 LOSSES = {None: 0, "none": 0, "huber": 1, "softl1": 2}  # PF_LOSS_* of pf_set_register_loss
+TILE_DEPTHS = {None: 0, "ray": 0, "planar": 1}  # PF_TILE_DEPTH_* of pf_set_tile_depth
 
 STAGES = ["warp", "register", "seed", "targets", "jacobi", "quantize", "metrics"]
 
@@ -134,6 +136,9 @@ def load():
     L.pf_tile_valid_counts.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, vp]
     L.pf_set_register_loss.argtypes = [vp, ip, C.c_double]
     L.pf_register_ex.argtypes = [vp, vp, ip, ip, ip, vp, ip, fp, fp, ip, ip, vp, vp, vp]
+    L.pf_set_tile_depth.argtypes = [vp, ip]
+    L.pf_tile_ray_tables.argtypes = [vp, ip, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.pf_tile_ray_factor.argtypes = [vp, vp]
     L.pf_fuse_normalize.argtypes = [vp, vp, vp, ip, ip, fp, fp, ip, vp]
     L.pf_fuse_multicover.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, ip, vp,
                                      C.POINTER(C.c_int)]
@@ -311,6 +316,42 @@ class Fuser:
             raise ValueError(f"unknown loss {kind!r}: one of {sorted(k for k in LOSSES if k)}")
         self._check(self.L.pf_set_register_loss(self.h, LOSSES[kind], float(a)))
         self._loss = LOSSES[kind]
+
+    def set_tile_depth(self, kind=None):
+        """What the tiles hold (pf_set_tile_depth): None / "ray" (ray distance, as the reference
+        assumes; the default) or "planar" (depth along the optical axis, what perspective depth
+        networks predict).  Under "planar" register / register_disparity fit the per-tile model
+        times the pixel's ray factor and apply writes clamp01(kf * T(x)); merge / merge_disparity
+        apply into a private copy and fuse it; the entry points that fuse a transform into their
+        gather raise PF_ESTATE when given coeffs, and register_joint always does."""
+        if kind not in TILE_DEPTHS:
+            raise ValueError(f"unknown tile depth {kind!r}: \"ray\" or \"planar\"")
+        self._check(self.L.pf_set_tile_depth(self.h, TILE_DEPTHS[kind]))
+
+    def tile_ray_tables(self, tile):
+        """pf_tile_ray_tables: (cu float64 [tile_w], rv float64 [tile_h]) of one tile of the stored
+        layout; the ray factor of pixel (i, j) is float32(sqrt(1.0 + cu[i] + rv[j]))."""
+        import numpy as np
+        if self.layout is None or not 0 <= tile < self.layout.ntiles:
+            raise ValueError(f"tile {tile} outside the stored layout")
+        cu = np.zeros(int(self.layout.tile_w[tile]), np.float64)
+        rv = np.zeros(int(self.layout.tile_h[tile]), np.float64)
+        dp = C.POINTER(C.c_double)
+        self._check(self.L.pf_tile_ray_tables(self.h, int(tile), cu.ctypes.data_as(dp),
+                                              rv.ctypes.data_as(dp)))
+        return cu, rv
+
+    def tile_ray_factor(self, out=None):
+        """pf_tile_ray_factor: the ray factor of every tile pixel, float32 [tile pixels] device
+        tensor in layout order (made when None).  Works in either mode.  No sync."""
+        import torch
+        n = self.tile_elems // self.channels
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=f"cuda:{self.device}")
+        if out.numel() != n or out.dtype != torch.float32:
+            raise ValueError(f"out must hold {n} float32 values")
+        self._check(self.L.pf_tile_ray_factor(self.h, _ptr(out)))
+        return out
 
     def _summary_ptr(self, summary, B, width):
         if summary is not None and summary.numel() != B * self.layout.ntiles * width:
