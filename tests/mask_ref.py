@@ -2,7 +2,11 @@
 oracle's own building blocks.
 
 TEST INFRASTRUCTURE ONLY.  tests/test_mask_ref.py proves the compositions against the oracle on
-unmasked inputs (bit for bit); tests/test_gpu_mask.py holds the library to them.
+unmasked inputs (bit for bit); tests/test_gpu_mask.py holds the library to them.  The functions
+take any layout, tile data, channel count and output size: tests/mask_shapes.py builds the cases
+beyond 512x256 C1 on them (apply_holes, masked_targets, level_stats), tests/test_mask_shapes.py
+proves those, tests/test_gpu_mask_shapes.py runs them.  HOLES, with_holes and the c1_* caches are
+the C1 case of tests/test_gpu_mask.py.
 
 Fusion.  Per level and tile p, O.targets_subset(tiles, p, p + 1, data, lv) on tile data that
 carries NaN at every invalid pixel: a NaN tap poisons exactly the stencils that read it, so tile p
@@ -148,32 +152,93 @@ def register_joint(sums, active):
 
 
 # ---- fusion -----------------------------------------------------------------------------------
-def masked_fuse(emap, tiles, data_nan, out_w=OUT_W, out_h=OUT_H, zr=ZR):
-    """(u16 [out_h][out_w], stats) of the masked fusion.  stats per level: `dropped`, the pixels
-    whose cover went from 2 to 1; `unwindowed`, the covered band pixels left without a valid
-    tile; `max_cover`, the largest layout cover (asserted <= 2)."""
+PATCH_W, PATCH_H = 64, 8  # kTPW, kTPH (csrc/pf_targets.hip): a block's patch of band pixels
+# every strip width V = 128 - 2 * Tp of the streamed Jacobi passes (csrc/pf_ctx.hpp
+# strip_geometry: Tp = the pass depth 1..10 rounded up to even)
+STRIP_WIDTHS = (124, 120, 116, 112, 108)
+
+
+def apply_holes(tiles, data, holes, value=np.nan):
+    """A copy of `data` (any layout, size and channel count) with `value` at the elements of
+    `holes`: [(tile p, element indices inside tile p)]."""
+    d = np.array(data, np.float32).ravel()
+    for p, idx in holes:
+        d[tiles[p].offset + np.asarray(idx, np.int64)] = value
+    return d
+
+
+def masked_targets(tiles, data_nan, lv, cover_limit=2):
+    """(Lsum, cnt, cover) of one level: the valid tiles' sums added in ascending tile order, how
+    many there were, and the layout's cover.  cover_limit None lifts the cover-of-two condition:
+    the ascending order is then targets_patch's order restated, not derived from the oracle."""
+    Lsum = np.zeros((lv.h, lv.w), np.float32)
+    cnt = np.zeros((lv.h, lv.w), np.int32)
+    cover = np.zeros((lv.h, lv.w), np.int32)
+    for p in range(len(tiles)):
+        s, c = O.targets_subset(tiles, p, p + 1, data_nan, lv)
+        ok = (c > 0) & ~np.isnan(s)
+        with np.errstate(invalid="ignore"):
+            Lsum = np.where(ok, Lsum + s, Lsum).astype(np.float32)
+        cnt += ok
+        cover += c > 0
+    if cover_limit is not None:
+        assert cover.max() <= cover_limit, "the composition is exact only up to a cover of two"
+    return Lsum, cnt, cover
+
+
+def level_stats(cnt, cover, lv):
+    """What the holes did to one level.  `dropped`: pixels whose cover went from 2 to 1;
+    `unwindowed`: covered band pixels left without a valid tile (they carry the marker);
+    `max_cover`; `unwindowed_first_row` / `_last_row`: those on band rows h0+1 / h1-1;
+    `unwindowed_first_col` / `_last_col`: those in the first / last covered column of row h0+1;
+    `unwindowed_patches`: the 64 x 8 target patches that hold one; `strip_seams`: the strip widths
+    V of STRIP_WIDTHS with one in columns k*V - 1 and k*V for some k >= 1; `isolated`: pixels with
+    a valid tile whose four neighbours have none."""
+    band = np.zeros((lv.h, lv.w), bool)
+    band[lv.h0 + 1:lv.h1] = True
+    un = (cover > 0) & (cnt == 0) & band
+    cols = np.flatnonzero(cover[lv.h0 + 1] > 0)
+    ys, xs = np.nonzero(un)
+    patches = set(zip(((ys - lv.h0) // PATCH_H).tolist(), (xs // PATCH_W).tolist()))
+    ucol = un.any(0)
+    seams = [V for V in STRIP_WIDTHS
+             if any(ucol[b - 1] and ucol[b] for b in range(V, lv.w, V))]
+    ok = (cnt > 0) & band
+    none = np.pad(cnt == 0, 1, constant_values=False)
+    iso = ok & none[1:-1, :-2] & none[1:-1, 2:] & none[:-2, 1:-1] & none[2:, 1:-1]
+    return {"dropped": int(((cover == 2) & (cnt == 1) & band).sum()),
+            "unwindowed": int(un.sum()),
+            "max_cover": int(cover.max()),
+            "unwindowed_first_row": int(un[lv.h0 + 1].sum()),
+            "unwindowed_last_row": int(un[lv.h1 - 1].sum()),
+            "unwindowed_first_col": int(un[:, cols[0]].sum()) if cols.size else 0,
+            "unwindowed_last_col": int(un[:, cols[-1]].sum()) if cols.size else 0,
+            "unwindowed_patches": len(patches),
+            "strip_seams": seams,
+            "isolated": int(iso.sum())}
+
+
+def masked_stats(tiles, data_nan, out_w=OUT_W, out_h=OUT_H, zr=ZR, cover_limit=2):
+    """masked_fuse's stats alone (no solve): one level_stats per level."""
+    data_nan = np.ascontiguousarray(data_nan, np.float32)
+    stats = []
+    for level in range(O.num_levels(out_w)):
+        lv = O.level_dims(out_w, out_h, zr, level)
+        _, cnt, cover = masked_targets(tiles, data_nan, lv, cover_limit)
+        stats.append(level_stats(cnt, cover, lv))
+    return stats
+
+
+def masked_fuse(emap, tiles, data_nan, out_w=OUT_W, out_h=OUT_H, zr=ZR, cover_limit=2):
+    """(u16 [out_h][out_w], stats) of the masked fusion; stats: level_stats() per level."""
     data_nan = np.ascontiguousarray(data_nan, np.float32)
     stats = []
     prev = None
     buf = None
     for level in range(O.num_levels(out_w)):
         lv = O.level_dims(out_w, out_h, zr, level)
-        Lsum = np.zeros((lv.h, lv.w), np.float32)
-        cnt = np.zeros((lv.h, lv.w), np.int32)
-        cover = np.zeros((lv.h, lv.w), np.int32)
-        for p in range(len(tiles)):
-            s, c = O.targets_subset(tiles, p, p + 1, data_nan, lv)
-            ok = (c > 0) & ~np.isnan(s)
-            with np.errstate(invalid="ignore"):
-                Lsum = np.where(ok, Lsum + s, Lsum).astype(np.float32)
-            cnt += ok
-            cover += c > 0
-        assert cover.max() <= 2, "the composition is exact only up to a cover of two"
-        band = np.zeros((lv.h, lv.w), bool)
-        band[lv.h0 + 1:lv.h1] = True
-        stats.append({"dropped": int(((cover == 2) & (cnt == 1) & band).sum()),
-                      "unwindowed": int(((cover > 0) & (cnt == 0) & band).sum()),
-                      "max_cover": int(cover.max())})
+        Lsum, cnt, cover = masked_targets(tiles, data_nan, lv, cover_limit)
+        stats.append(level_stats(cnt, cover, lv))
         Lnorm = O.normalize(Lsum, cnt, lv)
         buf = O.seed_level0(emap, lv) if level == 0 else O.upsample(prev, lv)
         buf = O.jacobi(buf, Lnorm, lv, lv.iters)

@@ -134,14 +134,15 @@ def resident_blockings(lv):
     return plans
 
 
-def expected_engines(tiles, data, out_w, out_h):
-    """[(engine, form)] per level for a layout's oracle tiles: the host's rules restated."""
+def expected_engines(tiles, data, out_w, out_h, certificate=None):
+    """[(engine, form)] per level for a layout's oracle tiles: the host's rules restated.
+    certificate=False: under the tile validity rule, where level_full() answers false."""
     res = []
     for level in range(O.num_levels(out_w)):
         lv = O.level_dims(out_w, out_h, ZR, level)
         _, cnt, oops, _ = O.targets(tiles, data, lv)
         assert oops == 0
-        cert = has_certificate(cnt, lv)
+        cert = has_certificate(cnt, lv) if certificate is None else bool(certificate)
         if tcap(lv) < 1:
             engine = "sweeps"
         elif cert and resident_blockings(lv):

@@ -4,7 +4,8 @@ compositions of tests/mask_ref.py (which tests/test_mask_ref.py proves against t
 Shapes are C1 only: 6 tiles of 256^2, a 128x64 baseline, a 512x256 output.  The holes are a
 rectangle of tile 0 (rows 100..255 x columns 100..179: it crosses the row two tiles share and
 several 64x8 patch borders), a whole tile and a single pixel; written as NaN, or as 0.0 under
-lo = 0.  The references are computed once per process (mask_ref's caches) and shared.
+lo = 0.  The references are computed once per process (mask_ref's caches) and shared.  Other
+output sizes, hole positions, layouts and channel counts: tests/test_gpu_mask_shapes.py.
 """
 import numpy as np
 import pytest
