@@ -261,6 +261,57 @@ int pf_tile_ray_tables(pf_ctx* ctx, int tile, double* cu, double* rv);
  * order, rows top-first.  Works in either mode.  Stream-ordered. */
 int pf_tile_ray_factor(pf_ctx* ctx, float* k);
 
+/* ---- overlap-consistent registration (an extension: the reference registers every tile to the
+ * baseline on its own, Depth.cpp:794-805, and neighbouring tiles never meet) ----
+ *
+ * Two neighbours can each fit the blurry baseline well and still disagree where they overlap; the
+ * stitch shows that as seams, and the fusion can only average the conflicting targets.  The cubic
+ * is linear in its coefficients, so "fit the baseline and agree with your neighbours" is one linear
+ * least-squares problem per panorama in 4 ntiles unknowns, c_p the cubic of tile p:
+ *   E(c) = sum_p sum_{s in S_p} (u_s.c_p - y_s)^2
+ *        + lambda sum_{(p,q)} sum_{s in O_pq} (u_s.c_p - v_s.c_q)^2
+ * S_p: the registration samples of tile p exactly as pf_register reads them, u = (X^3, X^2, X, 1),
+ * X and y clamped to [1e-4, 1 - 1e-4] in fp64.  O_pq, for an ordered pair p != q: the samples of
+ * S_p whose grid direction, projected into tile q by SphericalTo2D with the tabulated trig values of
+ * tile p's grid, has dir.middle > 0 and 0 <= x <= 1 and 0 <= y <= 1 in fp32, with no clamping;
+ * v is the same row of tile q's value at Value(x, y).  The pairs with |O_pq| > 0 are listed in
+ * ascending (p, q).
+ *
+ * The overlap table depends on the layout, the tile sizes and the zenith range only; it is built on
+ * the first call that needs it (two deterministic passes: count, then fill in sample order) and
+ * cached until pf_set_tiles or another zenith range replaces the registration grids.
+ *   pf_overlap_pairs  HOST counts: the pairs and the pair samples of all pairs together.
+ *   pf_overlap_table  DEVICE copies: pairs [npairs][4] ints {p, q, first, count} and index
+ *                     [nsamples][2] ints {element in tile p, element in tile q} (offsets inside the
+ *                     tile, channel 0), pair after pair, each in ascending sample order of p.
+ *   pf_overlap_stats  stats [batch][npairs][5] doubles {count, sum d, sum d^2, max |d|, samples
+ *                     left out because a side is NaN}, d = (double)T32_p - (double)T32_q with T32
+ *                     Depth2DepthTransform's fp32 value under coeffs ([batch][ntiles][4] floats),
+ *                     or the raw tile values with coeffs == NULL.
+ *   pf_register_consistent  the minimiser of E: the 15 moment sums of pf_register per tile, 36
+ *     moment sums per pair (u u', v v', u v'), the normal equations assembled in a fixed order and
+ *     solved by an in-place right-looking Cholesky factorisation with column-oriented substitutions,
+ *     one workgroup per panorama, all in fp64 + - * / sqrt in a fixed order:
+ *     reproducible bit for bit.  lambda must be finite and >= 0 (PF_EINVAL otherwise); lambda = 0 is
+ *     the exact per-tile least squares (PF_SOLVER_NORMAL's minimiser by another elimination).
+ *       coeffs   (optional) [batch][ntiles][4] floats, coeffs64 (optional) the unrounded doubles
+ *       summary  (optional) [batch][4] doubles {data cost, pair cost, pair samples, status}: the
+ *                first sum of E and the second without its factor lambda, both at the returned
+ *                fp64 coefficients, evaluated from the moment sums; status 1: a pivot was not > 0
+ *                or the solution is not finite -- every coefficient of that panorama is a quiet
+ *                NaN, as are the two costs; other panoramas of the batch are unaffected.
+ *     apply != 0 then runs Depth2DepthTransform on the tiles, as pf_register's.
+ * All four return PF_ESTATE while the validity rule (pf_set_tile_validity), a loss
+ * (pf_set_register_loss) or PF_TILE_DEPTH_PLANAR (pf_set_tile_depth) is on: their consistent forms
+ * are out of scope and the modes are never silently ignored.  No existing entry point changes. */
+int pf_overlap_pairs(pf_ctx* ctx, float zr0, float zr1, int* npairs, long long* nsamples);
+int pf_overlap_table(pf_ctx* ctx, float zr0, float zr1, int* pairs, int* index);
+int pf_overlap_stats(pf_ctx* ctx, const float* tiles, const float* coeffs, int batch, float zr0,
+                     float zr1, double* stats);
+int pf_register_consistent(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, float* tiles,
+                           int batch, float zr0, float zr1, double lambda, int apply,
+                           float* coeffs, double* coeffs64, double* summary);
+
 /* ---- post-fusion calibration (no tile layout needed; all pointers are device pointers) ----
  *
  * SolveDepthToDepth2 (Depth.cpp:1158-1259): one cubic per panorama from the fused u16 result

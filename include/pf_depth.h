@@ -291,6 +291,27 @@ bool SolveDisparityToDepth(EquirectangularMap& emap, std::vector<PerspectiveMap>
 bool SolveDepthToDepth(EquirectangularMap& emap, std::vector<PerspectiveMap>& pmaps,
                        std::vector<bool>& pmaps_actives, Vec2f& zenith_range, Vec4f& abcd);
 
+/* EXTENSION (the reference registers every map to the baseline on its own, so neighbours never
+ * meet): the cubics of all maps fitted at once, each to the baseline and to its neighbours where
+ * their windows overlap, lambda >= 0 weighing the overlap term (pf_register_consistent,
+ * include/panofuse.h; lambda = 0 is the independent least squares).  abcd_out[i] belongs to
+ * pmaps[i]; the maps are not modified.  Prints the library's message and returns false under
+ * SetTileValidity, SetRegistrationLoss or SetTileDepth(1), for a bad lambda, and when the joint
+ * system is singular. */
+bool SolveDepthToDepthConsistent(EquirectangularMap& emap, std::vector<PerspectiveMap>& pmaps,
+                                 Vec2f& zenith_range, double lambda, std::vector<Vec4f>& abcd_out);
+/* EXTENSION: how much the maps disagree where they overlap (pf_overlap_stats).  One entry per
+ * ordered pair (p, q) with overlap samples, in ascending (p, q): over the registration samples of
+ * map p that fall inside map q's window, d = T_p(value in p) - T_q(value in q) with T the
+ * Depth2DepthTransform of abcds (one Vec4f per map; an empty vector: the values as they are). */
+struct TileOverlapStat {
+    int p, q;
+    double count, sum, sum_sq, max_abs;  /* of d over the samples counted */
+    double nan_count;                    /* samples left out: a NaN on either side */
+};
+bool TileOverlapStats(std::vector<PerspectiveMap>& pmaps, std::vector<Vec4f>& abcds,
+                      Vec2f& zenith_range, std::vector<TileOverlapStat>& stats_out);
+
 /* Depth.h:300-301, Depth.cpp:1158-1259: the final global registration of a fused u16 result
  * (data [height][width]) to the baseline emap: one cubic fitted on every pixel of the band rows by
  * the reference's LM from (0, 0, 1, 0), on the GPU (pf_register_global).  Prints the reference's

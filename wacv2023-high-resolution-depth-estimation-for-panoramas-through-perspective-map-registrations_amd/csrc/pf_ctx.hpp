@@ -1,6 +1,6 @@
 // pf_ctx.hpp -- private to the host units of libpanofuse (pf_ctx.hip, pf_layout.hip, pf_plan.hip,
 // pf_fuse.hip, pf_shard.hip, pf_warp_api.hip, pf_smooth_api.hip, pf_eval.hip, pf_disp_api.hip,
-// pf_global_api.hip, pf_stitch_api.hip): the context struct
+// pf_global_api.hip, pf_stitch_api.hip, pf_consist_api.hip): the context struct
 // behind the C-ABI's opaque pf_ctx, the error / allocation / upload helpers, the argument-check
 // prologues the entry points share, and the few functions that cross those units.  No kernel unit
 // includes it.
@@ -88,6 +88,14 @@ struct pf_ctx {
     std::vector<pf::RayTile> ray_h;
     pf::DevBuf ray_tab, ray, reg_kf;
     int reg_kf_key[3] = {-1, -1, -1};
+    // the tile-pair overlap table (pf_consist_api.hip) of the registration grids: the pair list
+    // {p, q, first, count} (host copy and device copy) and the samples' {element in p, element in
+    // q}; rebuilt when the grids are (prepare_registration drops it).  Then the pair moment sums,
+    // the statistics and the solve's global workspace of pf_register_consistent.
+    bool pair_valid = false;
+    std::vector<int> pairs_h;
+    long long pair_samples = 0;
+    pf::DevBuf pair_counts, pair_list, pair_index, pair_sums, consist_ws;
     std::vector<pf::RgbCam> cams_h;  // GL cameras of the RGB warp (SaveCubeMap), host only
     // RGB warp taps for one panorama size (rgb_taps_host), built on first use
     int rgb_pw = 0, rgb_ph = 0;

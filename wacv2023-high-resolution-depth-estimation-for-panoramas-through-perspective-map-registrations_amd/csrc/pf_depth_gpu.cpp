@@ -340,6 +340,80 @@ bool SolveDisparityToDepth(EquirectangularMap& emap, std::vector<PerspectiveMap>
                  });
 }
 
+// EXTENSION: every map's cubic fitted to the baseline and to its neighbours in the overlaps, one
+// linear least-squares problem (pf_register_consistent); abcd_out[i] belongs to pmaps[i].
+bool SolveDepthToDepthConsistent(EquirectangularMap& emap, std::vector<PerspectiveMap>& pmaps,
+                                 Vec2f& zr, double lambda, std::vector<Vec4f>& abcd_out)
+{
+    pf_ctx* c = facade_ctx();
+    if (!c || !emap.data) return false;
+    if (pmaps.empty()) {
+        std::cout << "[SolveDepthToDepthConsistent] no map" << std::endl;
+        return false;
+    }
+    DevMem dt = tiles_on_device(c, pmaps);
+    if (!dt.ok) return false;
+    const size_t n = pmaps.size();
+    DevMem de = on_device(emap), dc(4 * n * sizeof(float)), ds(4 * sizeof(double));
+    if (!de.ok || !dc.ok || !ds.ok) return false;
+    std::vector<float> k(4 * n);
+    double sm[4];
+    if (!pf_ok(c, pf_register_consistent(c, de.as<float>(), emap.width, emap.height, emap.channels,
+                                         dt.as<float>(), 1, zr[0], zr[1], lambda, 0,
+                                         dc.as<float>(), nullptr, ds.as<double>()),
+               "pf_register_consistent") ||
+        !download(k.data(), dc, 4 * n) || !download(sm, ds, 4))
+        return false;
+    if (sm[3] != 0.0) {
+        std::cout << "[SolveDepthToDepthConsistent] the joint system is singular" << std::endl;
+        return false;
+    }
+    abcd_out.resize(n);
+    for (size_t i = 0; i < n; ++i) abcd_out[i] = to_vec4(&k[4 * i]);
+    return true;
+}
+
+// EXTENSION: the statistics of the maps' disagreement on their overlaps (pf_overlap_stats), under
+// abcds (one per map) or, with abcds empty, of the maps as they are.
+bool TileOverlapStats(std::vector<PerspectiveMap>& pmaps, std::vector<Vec4f>& abcds, Vec2f& zr,
+                      std::vector<TileOverlapStat>& stats_out)
+{
+    pf_ctx* c = facade_ctx();
+    if (!c) return false;
+    if (pmaps.empty() || (!abcds.empty() && abcds.size() != pmaps.size())) {
+        std::cout << "[TileOverlapStats] needs maps, and no coefficients or one Vec4f per map"
+                  << std::endl;
+        return false;
+    }
+    DevMem dt = tiles_on_device(c, pmaps);
+    if (!dt.ok) return false;
+    int npairs = 0;
+    long long nsamples = 0;
+    if (!pf_ok(c, pf_overlap_pairs(c, zr[0], zr[1], &npairs, &nsamples), "pf_overlap_pairs"))
+        return false;
+    stats_out.clear();
+    if (npairs == 0) return true;
+    std::vector<float> k;
+    for (const Vec4f& v : abcds) k.insert(k.end(), {v[0], v[1], v[2], v[3]});
+    DevMem dk(k.data(), k.size()), dp(4 * (size_t)npairs * sizeof(int)),
+        di(2 * (size_t)nsamples * sizeof(int)), ds(5 * (size_t)npairs * sizeof(double));
+    if (!dk.ok || !dp.ok || !di.ok || !ds.ok) return false;
+    std::vector<int> pairs(4 * (size_t)npairs);
+    std::vector<double> st(5 * (size_t)npairs);
+    if (!pf_ok(c, pf_overlap_table(c, zr[0], zr[1], dp.as<int>(), di.as<int>()),
+               "pf_overlap_table") ||
+        !pf_ok(c, pf_overlap_stats(c, dt.as<float>(), abcds.empty() ? nullptr : dk.as<float>(), 1,
+                                   zr[0], zr[1], ds.as<double>()),
+               "pf_overlap_stats") ||
+        !download(pairs.data(), dp, pairs.size()) || !download(st.data(), ds, st.size()))
+        return false;
+    stats_out.resize(npairs);
+    for (int i = 0; i < npairs; ++i)
+        stats_out[i] = TileOverlapStat{pairs[4 * i], pairs[4 * i + 1], st[5 * i], st[5 * i + 1],
+                                       st[5 * i + 2], st[5 * i + 3], st[5 * i + 4]};
+    return true;
+}
+
 bool SolveDepthToDepth2(EquirectangularMap& emap, unsigned short* data, int width, int height,
                         Vec2f& zr, Vec4f& abcd)  // Depth.cpp:1158-1259
 {

@@ -21,7 +21,8 @@ namespace {
 using namespace pff;
 
 // The environment switches of a Merge* call (panofuse_main sets them from --fusion,
-// --save-stitch, --check-laplacian, --global-align), read once at the top of the call.
+// --save-stitch, --check-laplacian, --global-align, --reg-consistent), read once at the top of the
+// call.
 // fusion: what fills the result (Depth.cpp:904-922, :851), the choice the reference makes by
 // editing `if (true/false)`; save_stitch / check_laplacian: its two `if (false)` diagnostics
 // (:817-865, :1738-1758); global_align: the fused result is pulled back onto the baseline by
@@ -38,7 +39,18 @@ struct MergeSwitches {
     // PF_TILE_DEPTH=planar|ray (panofuse_main --tile-depth): what the tiles of this call hold;
     // without it SetTileDepth's
     int tile_depth = PF_TILE_DEPTH_RAY;
+    // PF_REG_CONSISTENT=LAMBDA (panofuse_main --reg-consistent): the tiles are registered together,
+    // to the baseline and to each other in their overlaps (pf_register_consistent); < 0: off
+    double consistent = -1.0;
 };
+
+// A finite LAMBDA >= 0, the whole string.
+bool parse_lambda(const char* s, double& v)
+{
+    char* end = nullptr;
+    v = std::strtod(s ? s : "", &end);
+    return s && *s && end && *end == '\0' && v >= 0.0 && v < HUGE_VAL;
+}
 
 bool read_merge_switches(MergeSwitches& s)
 {
@@ -78,6 +90,13 @@ bool read_merge_switches(MergeSwitches& s)
         if (s.tile_depth < 0) {
             std::cout << "[MergeDepthMaps] bad PF_TILE_DEPTH " << td << " (want planar or ray)"
                       << std::endl;
+            return false;
+        }
+    }
+    if (const char* rc = std::getenv("PF_REG_CONSISTENT")) {
+        if (!parse_lambda(rc, s.consistent)) {
+            std::cout << "[MergeDepthMaps] bad PF_REG_CONSISTENT " << rc
+                      << " (want a finite LAMBDA >= 0)" << std::endl;
             return false;
         }
     }
@@ -194,6 +213,63 @@ bool register_tiles(const Job& j, float* d_coeffs, bool disparity_tiles, int nti
                          : pf_register(j.c, j.d_emap, e.width, e.height, e.channels, j.d_tiles, 1,
                                        j.zr[0], j.zr[1], 3, apply, d_coeffs, nullptr),
                      disparity_tiles ? "pf_register_disparity" : "pf_register");
+}
+
+// sqrt(sum sum d^2 / sum count) over the pairs of pf_overlap_stats under coeffs.
+bool overlap_rms(const Job& j, const float* d_coeffs, int npairs, double& rms)
+{
+    DevMem ds(sizeof(double) * 5 * (size_t)npairs);
+    std::vector<double> st((size_t)5 * npairs);
+    if (!ds.ok ||
+        !call_sync(j.c, pf_overlap_stats(j.c, j.d_tiles, d_coeffs, 1, j.zr[0], j.zr[1],
+                                         ds.as<double>()),
+                   "pf_overlap_stats") ||
+        !download(st.data(), ds, st.size()))
+        return false;
+    double n = 0.0, dd = 0.0;
+    for (int i = 0; i < npairs; i++) {
+        n = n + st[(size_t)5 * i];
+        dd = dd + st[(size_t)5 * i + 2];
+    }
+    rms = n > 0.0 ? std::sqrt(dd / n) : 0.0;
+    return true;
+}
+
+// PF_REG_CONSISTENT: the tiles registered together (pf_register_consistent) instead of one by one,
+// and "[consistent] lambda <L>: <P> pairs, <S> pair samples, overlap rms <before> -> <after>",
+// before under the independent coefficients of pf_register, after under the consistent ones.
+bool register_consistent(const Job& j, float* d_coeffs, int ntiles, double lambda)
+{
+    const EquirectangularMap& e = j.emap;
+    int npairs = 0;
+    long long nsamples = 0;
+    if (!pf_ok(j.c, pf_overlap_pairs(j.c, j.zr[0], j.zr[1], &npairs, &nsamples), "pf_overlap_pairs"))
+        return false;
+    DevMem dind(sizeof(float) * 4 * ntiles), dsum(sizeof(double) * 4);
+    double before = 0.0, after = 0.0, sm[4];
+    if (!dind.ok || !dsum.ok ||
+        !pf_ok(j.c, pf_register(j.c, j.d_emap, e.width, e.height, e.channels, j.d_tiles, 1, j.zr[0],
+                                j.zr[1], 3, 0, dind.as<float>(), nullptr),
+               "pf_register") ||
+        (npairs > 0 && !overlap_rms(j, dind.as<float>(), npairs, before)) ||
+        !call_sync(j.c, pf_register_consistent(j.c, j.d_emap, e.width, e.height, e.channels,
+                                               j.d_tiles, 1, j.zr[0], j.zr[1], lambda, 0, d_coeffs,
+                                               nullptr, dsum.as<double>()),
+                   "pf_register_consistent") ||
+        !download(sm, dsum, 4))
+        return false;
+    if (sm[3] != 0.0) {
+        std::cout << "[MergeDepthMaps] pf_register_consistent: the joint system is singular"
+                  << std::endl;
+        return false;
+    }
+    if (npairs > 0 && !overlap_rms(j, d_coeffs, npairs, after)) return false;
+    char line[192];
+    std::snprintf(line, sizeof(line),
+                  "[consistent] lambda %g: %d pairs, %lld pair samples, overlap rms %.6g -> %.6g",
+                  lambda, npairs, nsamples, before, after);
+    std::cout << line << std::endl;
+    return true;
 }
 
 // The fusion (Depth.cpp:904-913), or the smoothing (:919-922) / the stitch (:851) on the
@@ -380,6 +456,30 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
         }
         return false;
     }
+    // the consistent registration: depth tiles only, no global fit after it; under a mode it has no
+    // form for, the library's message -- all before any file is read
+    if (sw.consistent >= 0.0) {
+        if (disparity_tiles || sw.global_align) {
+            std::cout << "[MergeDepthMaps] PF_REG_CONSISTENT registers depth tiles by a linear "
+                         "solve: not with "
+                      << (disparity_tiles ? "disparity tiles" : "PF_GLOBAL_ALIGN") << std::endl;
+            return false;
+        }
+        if (sw.rule.on || sw.loss.kind != PF_LOSS_NONE || sw.tile_depth != PF_TILE_DEPTH_RAY) {
+            if (pf_ctx* c = facade_ctx()) {
+                apply_rule(c, sw.rule);
+                apply_loss(c, sw.loss);
+                pf_set_tile_depth(c, sw.tile_depth);
+                pf_ok(c, pf_register_consistent(c, nullptr, 0, 0, 0, nullptr, 1, 0.0f, 0.0f,
+                                                sw.consistent, 0, nullptr, nullptr, nullptr),
+                      "pf_register_consistent");
+                apply_rule(c, tile_rule());
+                apply_loss(c, reg_loss());
+                pf_set_tile_depth(c, tile_depth());
+            }
+            return false;
+        }
+    }
     EquirectangularMap emap, gt;
     std::vector<PerspectiveMap> pmaps;
     // the ground truth decodes on a host thread while the tiles load and the GPU fuses
@@ -423,7 +523,9 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
 
     if (sw.rule.on && !print_mask_lines(j, (int)pmaps.size(), sw.rule)) return false;
     auto t = std::chrono::steady_clock::now();
-    if (!register_tiles(j, dc.as<float>(), disparity_tiles, (int)pmaps.size(), sw.loss, planar))
+    if (sw.consistent >= 0.0
+            ? !register_consistent(j, dc.as<float>(), (int)pmaps.size(), sw.consistent)
+            : !register_tiles(j, dc.as<float>(), disparity_tiles, (int)pmaps.size(), sw.loss, planar))
         return false;
     // the transformed planar tiles carry NaN at their invalid pixels: what follows reads them
     // under (-inf, +inf), not under the caller's lo / hi (a value clamped to exactly 0 is valid)

@@ -157,6 +157,14 @@ __host__ __device__ inline void sph_to_2d(const TileGeom& g, float sz, float cz,
     y = (ev / g.vl) / g.vl;
 }
 
+// sph_to_2d's denominator dir.middle, by the same expression: > 0 iff the direction faces the
+// tile's plane (the overlap table's front-facing test, pf_consist.hip).
+__host__ __device__ inline float sph_den(const TileGeom& g, float sz, float cz, float ca, float sa)
+{
+    float d0 = sz * ca, d1 = sz * sa, d2 = cz;
+    return d0 * g.middle[0] + d1 * g.middle[1] + d2 * g.middle[2];
+}
+
 // PerspectiveMap::Value (Depth.cpp:111-118): truncating nearest lookup; returns the linear
 // element index (Y*W+X)*C.
 __host__ __device__ inline long long tile_index(const TileGeom& g, float x, float y)
@@ -423,6 +431,30 @@ void launch_apply_disp_planar(hipStream_t s, const TileGeom* geom, const RayTile
                               const double* tab, int ntiles, long long tile_pixels,
                               const float* src, float* dst, long long tstride,
                               const float* coeffs, int batch);
+// Overlap-consistent registration (pf_consist.hip).  The pair table: counts [ntiles][ntiles] of the
+// registration samples of tile p inside tile q's window, then per pair {p, q, first, count} (the
+// host's scan of the counts, ascending (p, q)) its samples' {element in p, element in q}.
+void launch_paircount(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
+                      const GridCol* rcols, const GridRow* rrows, int ntiles, int* counts);
+void launch_pairidx(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
+                    const GridCol* rcols, const GridRow* rrows, const int* pairs, int npairs,
+                    int2* index);
+// the 36 moment sums per (panorama, pair): out [batch][npairs][36]
+int pair_sums_per_pair();
+void launch_pair_moments(hipStream_t s, const TileGeom* geom, const int* pairs, int npairs,
+                         const int2* index, const float* tiles, long long tstride, double* out,
+                         int batch);
+// the joint solve of one panorama per workgroup from k_register's sums (dsums) and the pair sums;
+// ws == nullptr: the matrix in LDS (consist_fits_lds), else consist_workspace_doubles per panorama
+bool consist_fits_lds(int ntiles);
+size_t consist_workspace_doubles(int ntiles);
+void launch_consist_solve(hipStream_t s, const double* dsums, const double* psums,
+                          const int* pairs, int npairs, int ntiles, double lambda,
+                          double pair_samples, double* ws, float* coeffs, double* coeffs64,
+                          double* summary, int batch);
+void launch_overlap_stats(hipStream_t s, const TileGeom* geom, const int* pairs, int npairs,
+                          int ntiles, const int2* index, const float* tiles, long long tstride,
+                          const float* coeffs, double* out, int batch);
 // D2DTransform (Depth.cpp:214-243) on all tiles / on one map, channel 0, in place
 void launch_apply_disp(hipStream_t s, const TileGeom* geom, int ntiles, long long tile_pixels,
                        float* tiles, long long tstride, const float* coeffs, int batch);

@@ -371,6 +371,7 @@ int pf::prepare_registration(pf_ctx* c, float zr0, float zr1)
     c->reg_valid = true;
     c->reg_sidx_key[0] = -1;  // the sample indices follow the grids
     c->reg_kf_key[0] = -1;
+    c->pair_valid = false;  // and so does the overlap table
     c->reg_zr0 = b0;
     c->reg_zr1 = b1;
     return PF_OK;

@@ -76,6 +76,13 @@
 // --check-laplacian run on those without coefficients, and the run prints per panorama
 // "[tile-depth] planar: ray factor up to <max> over <n> tiles".  Works with both --tile-model
 // values.  Carried in PF_TILE_DEPTH; not in the usage text either.
+// --reg-consistent LAMBDA (opt-in): the tiles are registered together instead of one by one, each to
+// the baseline and to its neighbours where their windows overlap, LAMBDA >= 0 weighing the overlap
+// term (pf_register_consistent); the fusion, stitch or smoothing then runs as ever.  Prints per
+// panorama "[consistent] lambda <L>: <P> pairs, <S> pair samples, overlap rms <before> -> <after>".
+// Not with --tile-model disparity or --global-align (refused here), nor with --tile-valid,
+// --reg-loss or --tile-depth planar (refused with the library's message).  Carried in
+// PF_REG_CONSISTENT; not in the usage text either.
 #include "pf_facade.hpp"  // the inline to_window and load_pair; it includes the two public headers
 #include "pf_ray.hpp"
 #include "pf_valid.hpp"
@@ -338,9 +345,10 @@ static int mode0_command(int argc, char* argv[])
     }
     std::string tiles = "test_images", ext = "auto", fusion;
     int width = 2048, device = 0, shard = 0, nshards = 1;
-    bool check_laplacian = false;
+    bool check_laplacian = false, consistent = false, global_align = false, disparity = false;
     const auto on_switch = [&](const std::string& k) {
         if (k == "--check-laplacian") check_laplacian = true;
+        if (k == "--global-align") global_align = true;
         return take_env_flag(k, nullptr);
     };
     const auto on_value = [&](const std::string& k, const std::string& v) {
@@ -364,6 +372,14 @@ static int mode0_command(int argc, char* argv[])
             if (pf::parse_tile_depth(v.c_str()) < 0) return bad(k, v, "planar or ray");
             setenv("PF_TILE_DEPTH", v.c_str(), 1);  // read by MergeDepthMaps / MergeDisparityMaps
         }
+        else if (k == "--reg-consistent") {
+            char* end = nullptr;
+            const double lam = std::strtod(v.c_str(), &end);
+            if (v.empty() || !end || *end != '\0' || !(lam >= 0.0 && lam < HUGE_VAL))
+                return bad(k, v, "a finite LAMBDA >= 0");
+            consistent = true;
+            setenv("PF_REG_CONSISTENT", v.c_str(), 1);  // read by MergeDepthMaps
+        }
         else if (k == "--shard") {  // R/N: one process per GPU over the sorted folder
             if (std::sscanf(v.c_str(), "%d/%d", &shard, &nshards) != 2 || nshards < 1 ||
                 shard < 0 || shard >= nshards)
@@ -371,6 +387,7 @@ static int mode0_command(int argc, char* argv[])
         }
         else {
             if (k == "--fusion") fusion = v;
+            if (k == "--tile-model") disparity = v == "disparity";
             return take_env_flag(k, v.c_str());
         }
         return 0;
@@ -381,6 +398,11 @@ static int mode0_command(int argc, char* argv[])
     if (check_laplacian && !fusion.empty() && fusion != "laplacian") {
         std::cout << "--check-laplacian needs --fusion laplacian (got " << fusion << ")"
                   << std::endl;
+        return 2;
+    }
+    if (consistent && (disparity || global_align)) {
+        std::cout << "--reg-consistent registers depth tiles by a linear solve: not with "
+                  << (disparity ? "--tile-model disparity" : "--global-align") << std::endl;
         return 2;
     }
     if (!select_device(device)) return 1;

@@ -39,6 +39,7 @@ EXPORTS = [
     "pf_stitch", "pf_laplacian_residual", "pf_fuse_check", "pf_set_tile_validity",
     "pf_tile_valid_counts", "pf_set_register_loss", "pf_register_ex",
     "pf_set_tile_depth", "pf_tile_ray_tables", "pf_tile_ray_factor",
+    "pf_overlap_pairs", "pf_overlap_table", "pf_overlap_stats", "pf_register_consistent",
 ]
 NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
           "pf_debug_smooth_fault", "pf_fuse_partial_rows", "pf_fuse_coverage_rows",
@@ -139,6 +140,11 @@ def load():
     L.pf_set_tile_depth.argtypes = [vp, ip]
     L.pf_tile_ray_tables.argtypes = [vp, ip, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.pf_tile_ray_factor.argtypes = [vp, vp]
+    L.pf_overlap_pairs.argtypes = [vp, fp, fp, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+    L.pf_overlap_table.argtypes = [vp, fp, fp, vp, vp]
+    L.pf_overlap_stats.argtypes = [vp, vp, vp, ip, fp, fp, vp]
+    L.pf_register_consistent.argtypes = [vp, vp, ip, ip, ip, vp, ip, fp, fp, C.c_double, ip, vp,
+                                         vp, vp]
     L.pf_fuse_normalize.argtypes = [vp, vp, vp, ip, ip, fp, fp, ip, vp]
     L.pf_fuse_multicover.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, ip, vp,
                                      C.POINTER(C.c_int)]
@@ -352,6 +358,58 @@ class Fuser:
             raise ValueError(f"out must hold {n} float32 values")
         self._check(self.L.pf_tile_ray_factor(self.h, _ptr(out)))
         return out
+
+    def overlap_pairs(self, zr):
+        """pf_overlap_pairs: (pairs, pair samples) of the stored layout's overlap table for this
+        zenith range; builds the table on first use (synchronises then)."""
+        n, m = C.c_int(0), C.c_longlong(0)
+        self._check(self.L.pf_overlap_pairs(self.h, float(zr[0]), float(zr[1]), C.byref(n),
+                                            C.byref(m)))
+        return n.value, m.value
+
+    def overlap_table(self, zr):
+        """pf_overlap_table: (pairs int32 [npairs, 4] = {p, q, first, count} in ascending (p, q),
+        index int32 [nsamples, 2] = {element in tile p, element in tile q}) device tensors."""
+        import torch
+        n, m = self.overlap_pairs(zr)
+        dev = f"cuda:{self.device}"
+        pairs = torch.zeros((max(n, 1), 4), dtype=torch.int32, device=dev)
+        index = torch.zeros((max(m, 1), 2), dtype=torch.int32, device=dev)
+        self._check(self.L.pf_overlap_table(self.h, float(zr[0]), float(zr[1]), _ptr(pairs),
+                                            _ptr(index)))
+        return pairs[:n], index[:m]
+
+    def overlap_stats(self, tiles, zr, coeffs=None, stats=None):
+        """pf_overlap_stats: float64 [B, npairs, 5] device tensor (made when None) of {count,
+        sum d, sum d^2, max |d|, NaN samples} per panorama and pair, d the difference of the two
+        tiles' values at a pair sample under coeffs (float32 [B, ntiles, 4]; None: the raw
+        values).  tiles: [B, tile_elems].  No sync once the table exists."""
+        import torch
+        B = tiles.shape[0]
+        n, _ = self.overlap_pairs(zr)
+        if stats is None:
+            stats = torch.zeros((B, n, 5), dtype=torch.float64, device=tiles.device)
+        if stats.numel() != B * n * 5 or stats.dtype != torch.float64:
+            raise ValueError(f"stats must hold [B, {n}, 5] float64 values")
+        self._check(self.L.pf_overlap_stats(self.h, _ptr(tiles), _ptr(coeffs), B, float(zr[0]),
+                                            float(zr[1]), _ptr(stats)))
+        return stats
+
+    def register_consistent(self, emap, tiles, zr, lam=1.0, apply=True, coeffs=None,
+                            coeffs64=None, summary=None):
+        """pf_register_consistent: every tile's cubic fitted to the baseline and to its
+        neighbours in the overlaps, one linear least-squares problem per panorama with weight lam
+        on the overlap term.  coeffs: float32, coeffs64: float64 [B, ntiles, 4]; summary: float64
+        [B, 4] = {data cost, pair cost, pair samples, status (1: singular, NaN coefficients)}
+        device tensors.  No sync once the table exists."""
+        ew, eh, ec = _emap_dims(emap)
+        B = emap.shape[0]
+        if summary is not None and summary.numel() != B * 4:
+            raise ValueError(f"summary holds {summary.numel()} values, not [B, 4]")
+        self._check(self.L.pf_register_consistent(self.h, _ptr(emap), ew, eh, ec, _ptr(tiles), B,
+                                                  float(zr[0]), float(zr[1]), float(lam),
+                                                  1 if apply else 0, _ptr(coeffs),
+                                                  _ptr(coeffs64), _ptr(summary)))
 
     def _summary_ptr(self, summary, B, width):
         if summary is not None and summary.numel() != B * self.layout.ntiles * width:
