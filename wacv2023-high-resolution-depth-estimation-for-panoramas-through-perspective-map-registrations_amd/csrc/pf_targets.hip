@@ -13,7 +13,12 @@
 //     reference's single-thread accumulation); per tile the tap values of the patch plus a
 //     one-pixel ring gathered through the map (+ the fused Depth2DepthTransform) into LDS, the
 //     five-point sums in std::map key order, then the normalisation of Depth.cpp:1626-1647.
+//     targets_wave (round 7, PF_TGT_WAVE=1, the default) is the same gather with one wave per
+//     patch and the grid rows in registers instead of LDS; targets_patch stays for the validity
+//     rule, the sharded partial sums and as the tests' reference.
 #include "pf_internal.hpp"
+
+#include <cstdlib>
 
 namespace pf {
 
@@ -302,8 +307,204 @@ __device__ __forceinline__ void targets_patch(const TileGeom* __restrict__ geom,
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Per-wave gather (round 7, PF_TGT_WAVE).  A kTPW = 64 column patch row is one wave wide, so a
+// wave can own a whole patch: lane i holds column X0 + i of all kTGH grid rows in registers, the
+// north / centre / south taps are the lane's own registers and the west / east taps are the
+// neighbouring lanes' (DPP wave_shr:1 / wave_shl:1).  No LDS, no barrier; the four waves of a
+// block are four independent work items.
+//
+// The ring columns X0 - 1 and X0 + 64 (the west tap of lane 0, the east tap of lane 63) of the
+// kTPH patch rows are gathered by ONE extra load per tile and panorama: lane j < kTPH takes the
+// west ring point of patch row j, lane kRingE + j the east one.  Row j's two ring values are
+// read out of that register (v_readlane) into the `old` operand of the row's two DPP moves,
+// which lane 0 / lane 63 keep (bound_ctrl off: a lane without a source lane keeps `old`).
+// A grid point outside the tile's tap box takes the value of the box's nearest point; such a
+// value only ever reaches pixels that in_box2 rejects.  The arithmetic per pixel is
+// targets_patch's, operation for operation.
+static constexpr int kRingE = 16;  // first lane of the east ring points
+static_assert(kTPW == 64 && kTPH <= kRingE && kRingE + kTPH <= 64, "one wave per patch row");
+
+__device__ __forceinline__ float dpp_west(float ring, float c)
+{  // lane i <- lane i-1 (wave_shr:1), lane 0 <- ring
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ring), __float_as_int(c),
+                                                      0x138, 0xF, 0xF, false));
+}
+__device__ __forceinline__ float dpp_east(float ring, float c)
+{  // lane i <- lane i+1 (wave_shl:1), lane 63 <- ring
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ring), __float_as_int(c),
+                                                      0x130, 0xF, 0xF, false));
+}
+__device__ __forceinline__ float lane_value(float v, int lane)
+{
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+
+// One wave's work: patch `pid` of level L for panoramas [bgrp*NB, +NB), NP of them in flight.
 template <bool XFORM, int NB>
-__global__ void __launch_bounds__(256) k_targets_patch(const TileGeom* __restrict__ geom,
+__device__ __forceinline__ void targets_wave(const TileGeom* __restrict__ geom,
+                                             const TileBox* __restrict__ box,
+                                             const TapBox* __restrict__ tb, int ntiles,
+                                             const int32_t* __restrict__ map,
+                                             const float* __restrict__ tiles, long long tstride,
+                                             const float* __restrict__ coeffs, const LevelDims& L,
+                                             int npx, int pid, int bgrp,
+                                             float* __restrict__ lnorm, long long lstride,
+                                             int batch, const uint32_t* __restrict__ tmask, int nmw)
+{
+    constexpr int NP = NB < 2 ? NB : 2;  // panoramas in flight (the VGPR budget: DESIGN.md §3)
+    static_assert(NB % NP == 0, "whole groups of panoramas in flight");
+    const int X0 = (pid % npx) * kTPW, Y0 = L.h0 + (pid / npx) * kTPH;
+    const int lane = threadIdx.x & 63;
+    const int X = X0 + lane;
+    const int bbeg = bgrp * NB;
+    float acc[kTPH][NB];
+#pragma unroll
+    for (int j = 0; j < kTPH; j++) {
+#pragma unroll
+        for (int q = 0; q < NB; q++) acc[j][q] = 0.0f;
+    }
+    // bit j: tile bx covers this lane's pixel of patch row j
+    auto covered = [&](const TileBox& bx) {
+        uint32_t in = 0;
+#pragma unroll
+        for (int j = 0; j < kTPH; j++) {
+            const int Y = Y0 + j;
+            if (X < L.w && Y <= L.h1 && Y > L.h0 && Y < L.h1 && in_box2(bx, X, Y)) in |= 1u << j;
+        }
+        return in;
+    };
+    const int X1 = min(X0 + kTPW - 1, L.w - 1), Y1 = min(Y0 + kTPH - 1, L.h1);
+    // The tap-map indices of tile p's grid, loaded once per tile for all NB panoramas.  A grid
+    // point outside the tap box takes the nearest point of the box instead (no predicate, no
+    // branch: every load is in bounds and the loads of a tile issue back to back).  They are kept
+    // as 32-bit byte offsets into the panorama's tile: the launchers take this form only for tile
+    // blocks of at most 2^30 elements, and the gathers need no 64-bit lane address.
+    auto load_indices = [&](const int p, uint32_t (&mi)[kTGH], uint32_t& mr) {
+        const TapBox B = tb[p];
+        const int gx = max(min(X - B.xmin, B.nx - 1), 0);
+#pragma unroll
+        for (int r = 0; r < kTGH; r++) {
+            const int gy = max(min(Y0 - 1 + r - B.ymin, B.ny - 1), 0);  // wave-uniform
+            mi[r] = (uint32_t)map[B.off + (long long)gy * B.nx + gx] * 4u;
+        }
+        // this lane's ring point: patch row rj, column rX (the lanes outside the two runs load
+        // one too, of a line the ring lanes load anyway)
+        const bool reast = lane >= kRingE && lane < kRingE + kTPH;
+        const int rj = reast ? lane - kRingE : lane < kTPH ? lane : 0;
+        const int rX = reast ? X0 + kTPW : X0 - 1;
+        const int rgx = max(min(rX - B.xmin, B.nx - 1), 0);
+        const int rgy = max(min(Y0 + rj - B.ymin, B.ny - 1), 0);
+        mr = (uint32_t)map[B.off + (long long)rgy * B.nx + rgx] * 4u;
+    };
+    // one tile's contribution (tiles come in index order: the reference's accumulation order)
+    auto tile = [&](const int p) {
+        uint32_t mi[kTGH], mr;
+        load_indices(p, mi, mr);
+        const long long toff = geom[p].off;
+        // the pixels of this lane that the tile covers
+        const uint32_t in = covered(box[p]);  // one register, not kTPH lane masks
+#pragma unroll
+        for (int q0 = 0; q0 < NB; q0 += NP) {
+            float v[NP][kTGH], vr[NP];
+#pragma unroll
+            for (int u = 0; u < NP; u++) {
+                const int b = bbeg + q0 + u < batch ? bbeg + q0 + u : batch - 1;
+                const char* tv = reinterpret_cast<const char*>(tiles + b * tstride + toff);
+#pragma unroll
+                for (int r = 0; r < kTGH; r++) v[u][r] = *reinterpret_cast<const float*>(tv + mi[r]);
+                vr[u] = *reinterpret_cast<const float*>(tv + mr);
+            }
+#pragma unroll
+            for (int u = 0; u < NP; u++) {
+                if constexpr (XFORM) {
+                    const int b = bbeg + q0 + u < batch ? bbeg + q0 + u : batch - 1;
+                    const float4 k =
+                        *reinterpret_cast<const float4*>(coeffs + ((long long)b * ntiles + p) * 4);
+#pragma unroll
+                    for (int r = 0; r < kTGH; r++)
+                        v[u][r] = cubic_map(v[u][r], k.x, k.y, k.z, k.w);
+                    vr[u] = cubic_map(vr[u], k.x, k.y, k.z, k.w);
+                }
+#pragma unroll
+                for (int j = 0; j < kTPH; j++) {
+                    // every lane runs the DPP moves: a lane switched off is no source lane
+                    const float W = dpp_west(lane_value(vr[u], j), v[u][j + 1]);
+                    const float E = dpp_east(lane_value(vr[u], kRingE + j), v[u][j + 1]);
+                    // taps in std::map key order: (X-1,Y), (X,Y-1), (X,Y), (X,Y+1), (X+1,Y)
+                    float Lp = 0;
+                    Lp += W * -0.25f;
+                    Lp += v[u][j] * -0.25f;
+                    Lp += v[u][j + 1] * 1.0f;
+                    Lp += v[u][j + 2] * -0.25f;
+                    Lp += E * -0.25f;
+                    if (in & (1u << j)) acc[j][q0 + u] += Lp;
+                }
+            }
+        }
+    };
+    // the tiles whose box meets this patch, as mask words: the host's list, or the box tests
+    const int nw = (ntiles + 31) / 32;
+    auto tile_word = [&](const int w) {
+        uint32_t m = 0;  // wave-uniform
+        if (tmask) {
+            m = tmask[(long long)pid * nmw + w];
+        } else {
+            for (int p = w * 32; p < min(w * 32 + 32, ntiles); p++)
+                if (box_meets(box[p], X0, X1, Y0, Y1)) m |= 1u << (p & 31);
+        }
+        return m;
+    };
+    for (int w = 0; w < nw; w++) {
+        uint32_t m = tile_word(w);
+        while (m) {
+            tile(w * 32 + __builtin_ctz(m));
+            m &= m - 1;
+        }
+    }
+    // the covering tiles per pixel: counted over the same tiles afterwards, so the counts hold
+    // no registers while the sums are gathered
+    int n[kTPH];
+#pragma unroll
+    for (int j = 0; j < kTPH; j++) n[j] = 0;
+    for (int w = 0; w < nw; w++) {
+        uint32_t m = tile_word(w);
+        while (m) {
+            const uint32_t in = covered(box[w * 32 + __builtin_ctz(m)]);
+#pragma unroll
+            for (int j = 0; j < kTPH; j++) n[j] += (in >> j) & 1u;
+            m &= m - 1;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kTPH; j++) {
+        const int Y = Y0 + j;
+        if (!(X < L.w && Y <= L.h1)) continue;
+        float scale = 1.0f;
+        if (n[j] > 1) {
+            float center = 0.0f;
+            for (int i = 0; i < n[j]; i++) center += 1.0f;
+            scale = 1.0f / center;
+        }
+        const long long o = (long long)Y * L.w + X;
+#pragma unroll
+        for (int q = 0; q < NB; q++) {
+            const int b = bbeg + q;
+            if (b >= batch) break;
+            float out;
+            if (n[j] == 0) out = __uint_as_float(PF_NAN_MARKER);
+            else if (n[j] == 1) out = acc[j][q];
+            else out = acc[j][q] * scale;
+            __builtin_nontemporal_store(out, &lnorm[b * lstride + o]);
+        }
+    }
+}
+
+// The block form's kernels take the wave form with WAVE: a block is then four waves with four
+// consecutive (patch, panorama group) work items, and the grid a quarter as many blocks.
+template <bool XFORM, int NB, bool WAVE = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVE ? 4 : 1)))
+k_targets_patch(const TileGeom* __restrict__ geom,
                                                        const TileBox* __restrict__ box,
                                                        const TapBox* __restrict__ tb, int ntiles,
                                                        const int32_t* __restrict__ map,
@@ -316,12 +517,21 @@ __global__ void __launch_bounds__(256) k_targets_patch(const TileGeom* __restric
                                                        const uint32_t* __restrict__ tmask,
                                                        int nmw)
 {
-    __shared__ float sv[NB][kTG];
     // XCD-contiguous runs of patches (neighbouring patches read the same tile lines)
     const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
-    const int pid = (int)(lb % (unsigned)npatch), bgrp = (int)(lb / (unsigned)npatch);
-    targets_patch<XFORM, NB>(geom, box, tb, ntiles, map, tiles, tstride, coeffs, L, npx, pid, bgrp,
-                             lnorm, lstride, batch, sv, tmask, nmw);
+    if constexpr (WAVE) {
+        const unsigned item =  // wave-uniform, and in scalar registers
+            lb * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        if (item >= (unsigned)npatch * (unsigned)((batch + NB - 1) / NB)) return;
+        targets_wave<XFORM, NB>(geom, box, tb, ntiles, map, tiles, tstride, coeffs, L, npx,
+                                (int)(item % (unsigned)npatch), (int)(item / (unsigned)npatch), lnorm, lstride, batch,
+                                tmask, nmw);
+    } else {
+        __shared__ float sv[NB][kTG];
+        const int pid = (int)(lb % (unsigned)npatch), bgrp = (int)(lb / (unsigned)npatch);
+        targets_patch<XFORM, NB>(geom, box, tb, ntiles, map, tiles, tstride, coeffs, L, npx, pid,
+                                 bgrp, lnorm, lstride, batch, sv, tmask, nmw);
+    }
 }
 
 // Every level's targets in ONE launch (round 4).  The per-level launches each streamed the
@@ -332,21 +542,34 @@ __global__ void __launch_bounds__(256) k_targets_patch(const TileGeom* __restric
 // finest level's patches come first, then each coarser level's patches of the same band (a host
 // table of (level, patch) entries).  The XCD-contiguous mapping gives every XCD a contiguous run
 // of the table, so a band's lines are re-read from its L2 / the MALL instead of HBM.
-template <bool XFORM, int NB>
-__global__ void __launch_bounds__(256) k_targets_multi(const TileGeom* __restrict__ geom,
+// WAVE: the table is walked by waves, four consecutive entries per block, in the same order.
+template <bool XFORM, int NB, bool WAVE = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVE ? 4 : 1)))
+k_targets_multi(const TileGeom* __restrict__ geom,
                                                        int ntiles, const float* __restrict__ tiles,
                                                        long long tstride,
                                                        const float* __restrict__ coeffs,
                                                        TgtMulti M, const int2* __restrict__ order,
                                                        int batch)
 {
-    __shared__ float sv[NB][kTG];
     const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
-    const int e = (int)(lb % (unsigned)M.nentries), bgrp = (int)(lb / (unsigned)M.nentries);
-    const int2 ent = order[e];  // (level, patch)
-    const TgtLevel& T = M.lv[ent.x];
-    targets_patch<XFORM, NB>(geom, T.box, T.tb, ntiles, T.map, tiles, tstride, coeffs, T.L, T.npx,
-                             ent.y, bgrp, T.lnorm, T.lstride, batch, sv, T.tmask, T.nmw);
+    if constexpr (WAVE) {
+        const unsigned item =  // wave-uniform, and in scalar registers
+            lb * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        if (item >= (unsigned)M.nentries * (unsigned)((batch + NB - 1) / NB)) return;
+        const int2 ent = order[item % (unsigned)M.nentries];  // (level, patch)
+        const TgtLevel& T = M.lv[ent.x];
+        targets_wave<XFORM, NB>(geom, T.box, T.tb, ntiles, T.map, tiles, tstride, coeffs, T.L,
+                                T.npx, ent.y, (int)(item / (unsigned)M.nentries), T.lnorm, T.lstride, batch,
+                                T.tmask, T.nmw);
+    } else {
+        __shared__ float sv[NB][kTG];
+        const int e = (int)(lb % (unsigned)M.nentries), bgrp = (int)(lb / (unsigned)M.nentries);
+        const int2 ent = order[e];  // (level, patch)
+        const TgtLevel& T = M.lv[ent.x];
+        targets_patch<XFORM, NB>(geom, T.box, T.tb, ntiles, T.map, tiles, tstride, coeffs, T.L,
+                                 T.npx, ent.y, bgrp, T.lnorm, T.lstride, batch, sv, T.tmask, T.nmw);
+    }
 }
 
 // The two gathers under the validity rule (MASK): the same blocks, tables and order.
@@ -381,6 +604,17 @@ __global__ void __launch_bounds__(256) k_targets_multi_valid(
                                    T.nmw, vlo, vhi);
 }
 
+// PF_TGT_WAVE (read per call): 1 = the per-wave gather, 0 = the block form.  The validity-rule
+// kernels and k_targets_patch_partial have the block form only, and so have layouts of more than
+// 2^30 tile elements per panorama.
+static constexpr int kTgtWaveDefault = 1;
+static bool targets_wave_on(long long tstride)
+{
+    if (tstride > (1ll << 30)) return false;  // targets_wave's 32-bit byte offsets into a tile
+    const char* e = getenv("PF_TGT_WAVE");
+    return (e && *e ? atoi(e) : kTgtWaveDefault) != 0;
+}
+
 int targets_patch_w() { return kTPW; }
 int targets_patch_h() { return kTPH; }
 int targets_batch() { return kTNB; }
@@ -405,6 +639,22 @@ void launch_targets_multi(hipStream_t s, const TileGeom* geom, int ntiles, const
         else
             hipLaunchKernelGGL((k_targets_multi_valid<false, kTNB>), g, dim3(256), 0, s, geom,
                                ntiles, tiles, tstride, coeffs, M, order, batch, tv.lo, tv.hi);
+        return;
+    }
+    if (targets_wave_on(tstride)) {  // four work items (one per wave) to the block
+        const dim3 gw((g.x + 3) / 4);
+        if (nb == 1 && coeffs)
+            hipLaunchKernelGGL((k_targets_multi<true, 1, true>), gw, dim3(256), 0, s, geom, ntiles,
+                               tiles, tstride, coeffs, M, order, batch);
+        else if (nb == 1)
+            hipLaunchKernelGGL((k_targets_multi<false, 1, true>), gw, dim3(256), 0, s, geom,
+                               ntiles, tiles, tstride, coeffs, M, order, batch);
+        else if (coeffs)
+            hipLaunchKernelGGL((k_targets_multi<true, kTNB, true>), gw, dim3(256), 0, s, geom,
+                               ntiles, tiles, tstride, coeffs, M, order, batch);
+        else
+            hipLaunchKernelGGL((k_targets_multi<false, kTNB, true>), gw, dim3(256), 0, s, geom,
+                               ntiles, tiles, tstride, coeffs, M, order, batch);
         return;
     }
     if (nb == 1 && coeffs)
@@ -449,6 +699,26 @@ void launch_targets_patch(hipStream_t s, const TileGeom* geom, const TileBox* bo
             hipLaunchKernelGGL((k_targets_patch_valid<false, kTNB>), g, dim3(256), 0, s, geom, box,
                                tb, ntiles, map, tiles, tstride, coeffs, L, npx, npatch, lnorm,
                                lstride, batch, tmask, nmw, tv.lo, tv.hi);
+        return;
+    }
+    if (targets_wave_on(tstride)) {  // four work items (one per wave) to the block
+        const dim3 gw((g.x + 3) / 4);
+        if (nb == 1 && coeffs)
+            hipLaunchKernelGGL((k_targets_patch<true, 1, true>), gw, dim3(256), 0, s, geom, box, tb,
+                               ntiles, map, tiles, tstride, coeffs, L, npx, npatch, lnorm, lstride,
+                               batch, tmask, nmw);
+        else if (nb == 1)
+            hipLaunchKernelGGL((k_targets_patch<false, 1, true>), gw, dim3(256), 0, s, geom, box,
+                               tb, ntiles, map, tiles, tstride, coeffs, L, npx, npatch, lnorm,
+                               lstride, batch, tmask, nmw);
+        else if (coeffs)
+            hipLaunchKernelGGL((k_targets_patch<true, kTNB, true>), gw, dim3(256), 0, s, geom, box,
+                               tb, ntiles, map, tiles, tstride, coeffs, L, npx, npatch, lnorm,
+                               lstride, batch, tmask, nmw);
+        else
+            hipLaunchKernelGGL((k_targets_patch<false, kTNB, true>), gw, dim3(256), 0, s, geom,
+                               box, tb, ntiles, map, tiles, tstride, coeffs, L, npx, npatch, lnorm,
+                               lstride, batch, tmask, nmw);
         return;
     }
     if (nb == 1 && coeffs)
