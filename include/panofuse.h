@@ -312,6 +312,58 @@ int pf_register_consistent(pf_ctx* ctx, const float* emap, int ew, int eh, int e
                            int batch, float zr0, float zr1, double lambda, int apply,
                            float* coeffs, double* coeffs64, double* summary);
 
+/* ---- per-pixel tile weights ----------------------------------------------------------------------
+ *
+ * An extension: a confidence per tile pixel (a network's uncertainty map, a border falloff, a
+ * segmentation mask per panorama) for the registration and the fusion.  The reference carries the
+ * hook and never uses it: every registration functor multiplies its residual by a Weight
+ * (Depth.cpp:1044-1150) and the only call site passes 1.0f (Depth.cpp:1366-1375).
+ *
+ * weights   DEVICE floats in the tiles' own element layout (tile p at its offset, the same strides,
+ *           any channel count); only the channel-0 element of a pixel is read.  wbatch == 1: one
+ *           set of tile_elems floats for the whole batch; wbatch == batch: one set per panorama;
+ *           anything else, or NULL, is PF_EINVAL.
+ * usable    u(w) = w if 0 < w && w < +inf in fp32, else 0: NaN, negatives and zero mean "not here".
+ *
+ * Weights in {0, 1} are the validity rule (pf_set_tile_validity): with NaN written under the zeros
+ * the three calls equal their counterparts under the rule (-inf, +inf) bit for bit, and with every
+ * weight 1.0f they equal pf_register / pf_fuse / pf_merge bit for bit.
+ *
+ *   pf_tile_tent_weights  fills one set (tile_elems floats, 0 in the non-zero channels) with the
+ *     blending tent in tile pixel space: for a w x h tile at pixel (x, y), t = min(min(x + 1, w - x),
+ *     min(y + 1, h - y)), m = (min(w, h) + 1) / 2 in integers, weight = (float)min(t, m) / (float)m.
+ *   pf_register_weighted  weighted least squares, degree 3, by the reference's LM from the moment
+ *     sums (PF_SOLVER_LM only: PF_EINVAL otherwise).  A sample is used iff u(w) > 0 at its tile
+ *     element, its raw tile value is finite and its baseline value is finite; a used sample adds
+ *     (double)w times each of pf_register's 15 terms, in pf_register's order.  This is
+ *     Weight = sqrt(w) in the reference's FunctorDepth2Depth3.  Fewer than 4 used samples, or a
+ *     non-finite solution: four quiet NaNs.
+ *       summary  (optional) [batch][ntiles][2] doubles {used samples, sum of w}
+ *     apply != 0 then runs Depth2DepthTransform on the tiles, as pf_register's.
+ *   pf_fuse_weighted  SolveDepthAll with weighted Laplacian targets.  A tap counts iff u(w) > 0 and
+ *     its (transformed, if coeffs) value is finite; tile p contributes to a pixel iff all five taps
+ *     of its stencil count, with wmin = the smallest of their five weights; the target is
+ *     sum(wmin * Lp) * (1 / sum(wmin)) over the contributing tiles in index order (fp32, separate
+ *     multiply and add), and a pixel without a contributing tile has no target, as an uncovered
+ *     one.  Coverage then depends on the data, so the Jacobi levels take their general passes.
+ *   pf_merge_weighted  pf_register_weighted (no apply) + pf_fuse_weighted with its coefficients.
+ *
+ * All four return PF_ESTATE while the validity rule (pf_set_tile_validity), a loss
+ * (pf_set_register_loss) or PF_TILE_DEPTH_PLANAR (pf_set_tile_depth) is on.  Disparity tiles,
+ * smoothing, stitch, the joint, consistent and global registrations and the sharded fusion have no
+ * weighted form.  Layouts of more than 2^30 tile elements per panorama are PF_EINVAL in the two
+ * fusing calls.  No existing entry point changes. */
+int pf_tile_tent_weights(pf_ctx* ctx, float* weights);
+int pf_register_weighted(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, float* tiles,
+                         const float* weights, int wbatch, int batch, float zr0, float zr1,
+                         int apply, float* coeffs, double* coeffs64, double* summary);
+int pf_fuse_weighted(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, const float* tiles,
+                     const float* weights, int wbatch, const float* coeffs, int batch, int out_w,
+                     int out_h, float zr0, float zr1, uint16_t* out);
+int pf_merge_weighted(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, const float* tiles,
+                      const float* weights, int wbatch, int batch, int out_w, float zr0,
+                      float zr1, float* coeffs, uint16_t* out);
+
 /* ---- post-fusion calibration (no tile layout needed; all pointers are device pointers) ----
  *
  * SolveDepthToDepth2 (Depth.cpp:1158-1259): one cubic per panorama from the fused u16 result

@@ -361,6 +361,23 @@ bool SetRegistrationLoss(int kind, double a);
  * (panofuse_main --tile-depth), which holds for that call.  false (and a message) for another
  * kind. */
 bool SetTileDepth(int kind);
+/* EXTENSION (the reference's registration functors carry a Weight that its only call site sets to
+ * 1.0f, Depth.cpp:1044-1150, 1366-1375): per-pixel tile weights for every later MergeDepthMaps of
+ * this facade, process-wide (pf_register_weighted / pf_fuse_weighted, include/panofuse.h).  mode 0
+ * off (the default), 1 the blending tent of every tile (pf_tile_tent_weights), 2 files: the weight
+ * map of a tile file F is F + suffix: a PNG read as a tile is (samples in 0-1), or a PFM read raw
+ * (its floats as stored, rows in file order, top row first), channel 0 of either, and of the
+ * tile's width and height, else MergeDepthMaps names the file and returns false.  A weight that is
+ * not in (0, +inf) switches its pixel off; weights in {0, 1} are the validity rule.
+ * MergeDepthMaps then registers every tile by weighted least squares, fuses the weighted Laplacian
+ * targets and prints per tile "[weights] tile <i>: <n> of <N> samples used, sum w <s>".  It also
+ * reads PF_TILE_WEIGHTS=tent|files:SUFFIX (panofuse_main --tile-weights), which holds for that
+ * call.  With weights on it returns false, before any file is read, together with
+ * SetTileValidity, SetRegistrationLoss, SetTileDepth(1), PF_REG_CONSISTENT, PF_GLOBAL_ALIGN,
+ * PF_CHECK_LAPLACIAN or PF_FUSION=smoothing|stitch; MergeDisparityMaps does so always.  false (and
+ * a message) for another mode, or for mode 2 with an empty suffix or one that holds a path
+ * separator. */
+bool SetTileWeights(int mode, const std::string& suffix = "");
 /* EXTENSION (in the reference an `if (false)` block of MergeDepthMaps, Depth.cpp:817-865): the
  * direct stitch of the tiles as they are into data (width * height u16) -- every pixel takes the
  * first map whose range box contains it, no fusion -- on the GPU (pf_stitch), bit-exact. */

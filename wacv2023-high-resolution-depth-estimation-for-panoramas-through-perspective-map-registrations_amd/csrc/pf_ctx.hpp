@@ -1,6 +1,6 @@
 // pf_ctx.hpp -- private to the host units of libpanofuse (pf_ctx.hip, pf_layout.hip, pf_plan.hip,
 // pf_fuse.hip, pf_shard.hip, pf_warp_api.hip, pf_smooth_api.hip, pf_eval.hip, pf_disp_api.hip,
-// pf_global_api.hip, pf_stitch_api.hip, pf_consist_api.hip): the context struct
+// pf_global_api.hip, pf_stitch_api.hip, pf_consist_api.hip, pf_weight_api.hip): the context struct
 // behind the C-ABI's opaque pf_ctx, the error / allocation / upload helpers, the argument-check
 // prologues the entry points share, and the few functions that cross those units.  No kernel unit
 // includes it.
@@ -72,6 +72,12 @@ struct pf_ctx {
     // what the tiles hold (pf_set_tile_depth); PF_TILE_DEPTH_RAY: ray distance, as the reference
     // assumes, and every entry point launches what it always did
     int tile_depth = PF_TILE_DEPTH_RAY;
+    // per-pixel tile weights of the weighted call that is running (pf_fuse_weighted,
+    // pf_merge_weighted; pf_weight_api.hip sets and clears them): the device plane in the tiles'
+    // element layout and its panorama stride (0: one set for the batch).  nullptr: no weights,
+    // and the fusion gathers what it always did
+    const float* wts = nullptr;
+    long long wts_stride = 0;
     std::vector<pf_window> fov, rng;
     std::vector<int> tw_h, th_h;
     bool layout_ok = false;  // the stored layout was set completely
@@ -316,8 +322,12 @@ inline int check_ray_coeffs(pf_ctx* c, const char* entry, const void* coeffs)
 }
 
 // Whether level l may take the coverage shortcuts (the packed Jacobi form, the resident kernel):
-// it holds the separable-coverage certificate and coverage does not depend on the data.
-inline bool level_full(const pf_ctx* c, int l) { return c->lc.full[l] && !c->valid.on; }
+// it holds the separable-coverage certificate and coverage does not depend on the data (it does
+// under the validity rule and under per-pixel weights).
+inline bool level_full(const pf_ctx* c, int l)
+{
+    return c->lc.full[l] && !c->valid.on && !c->wts;
+}
 
 inline int check_tile_range(pf_ctx* c, int t0, int t1)
 {
@@ -388,6 +398,11 @@ PassPlan plan_band_pass(pf_ctx* c, const LevelDims& L, int T, int band_rows, boo
 JresPlan jres_plan(pf_ctx* c, const LevelDims& L, int batch, bool fast);
 
 // ---- pf_fuse.hip ----------------------------------------------------------------------------
+// SolveDepthAll for a batch on c->stream (pf_fuse's body after its checks); with c->wts set the
+// targets are the weighted gather's.
+int fuse_impl(pf_ctx* c, const float* emap, int ew, int eh, int ec, const float* tiles,
+              const float* coeffs, int batch, int out_w, int out_h, float zr0, float zr1,
+              uint16_t* out);
 // What run_jacobi sweeps.  The first pass reads `first` (SRC_SEED 2: emap, SRC_UPSAMPLE 1: prev
 // level, SRC_BUF 0: buffer a); passes ping-pong between a and b.  With out != nullptr the last
 // pass stores the u16 quantisation instead of floats.  hcol: the level's packed-form certificate

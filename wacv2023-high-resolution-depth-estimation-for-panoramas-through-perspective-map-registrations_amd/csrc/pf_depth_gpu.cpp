@@ -37,6 +37,14 @@ int tile_depth()
     return g_tile_depth;
 }
 
+static pfw::Spec g_tile_weights;
+
+pfw::Spec tile_weights()
+{
+    std::lock_guard<std::mutex> lk(g_rule_mu);
+    return g_tile_weights;
+}
+
 static pf_ctx* device_ctx();
 
 pf_ctx* facade_ctx()
@@ -241,6 +249,19 @@ bool SetRegistrationLoss(int kind, double a)
     }
     std::lock_guard<std::mutex> lk(pff::g_rule_mu);
     pff::g_loss = pff::RegLossRule{kind, kind == PF_LOSS_NONE ? 0.0 : a};
+    return true;
+}
+
+bool SetTileWeights(int mode, const std::string& suffix)
+{  // EXTENSION: MergeDepthMaps registers and fuses with per-pixel tile weights
+    pfw::Spec spec;
+    std::string err;
+    if (!pfw::make_spec(mode, suffix, spec, err)) {
+        std::cout << "[SetTileWeights] " << err << std::endl;
+        return false;
+    }
+    std::lock_guard<std::mutex> lk(pff::g_rule_mu);
+    pff::g_tile_weights = spec;
     return true;
 }
 

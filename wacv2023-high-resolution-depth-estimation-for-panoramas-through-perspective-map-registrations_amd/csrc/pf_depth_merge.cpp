@@ -6,6 +6,7 @@
 // file writes stay on the host (they are file formats), every per-pixel computation of the path
 // (registration, transform, fusion, quantisation, metrics) is a libpanofuse HIP kernel.
 #include "pf_facade.hpp"
+#include "pf_image.hpp"
 #include "pf_ray.hpp"
 #include "pf_valid.hpp"
 
@@ -42,6 +43,9 @@ struct MergeSwitches {
     // PF_REG_CONSISTENT=LAMBDA (panofuse_main --reg-consistent): the tiles are registered together,
     // to the baseline and to each other in their overlaps (pf_register_consistent); < 0: off
     double consistent = -1.0;
+    // PF_TILE_WEIGHTS=tent|files:SUFFIX (panofuse_main --tile-weights): the per-pixel tile weights
+    // of this call; without it SetTileWeights'
+    pfw::Spec weights;
 };
 
 // A finite LAMBDA >= 0, the whole string.
@@ -97,6 +101,14 @@ bool read_merge_switches(MergeSwitches& s)
         if (!parse_lambda(rc, s.consistent)) {
             std::cout << "[MergeDepthMaps] bad PF_REG_CONSISTENT " << rc
                       << " (want a finite LAMBDA >= 0)" << std::endl;
+            return false;
+        }
+    }
+    s.weights = tile_weights();
+    if (const char* tw = std::getenv("PF_TILE_WEIGHTS")) {
+        std::string err;
+        if (!pfw::parse_spec(tw, s.weights, err)) {
+            std::cout << "[MergeDepthMaps] PF_TILE_WEIGHTS: " << err << std::endl;
             return false;
         }
     }
@@ -272,6 +284,93 @@ bool register_consistent(const Job& j, float* d_coeffs, int ntiles, double lambd
     return true;
 }
 
+// What the weighted forms cannot be combined with (pf_register_weighted / pf_fuse_weighted have no
+// form for it), or nullptr.
+const char* weights_conflict(const MergeSwitches& s, bool disparity_tiles)
+{
+    if (disparity_tiles) return "disparity tiles";
+    if (s.rule.on) return "the tile validity rule (PF_TILE_VALID / SetTileValidity)";
+    if (s.loss.kind != PF_LOSS_NONE) return "a registration loss (PF_REG_LOSS / SetRegistrationLoss)";
+    if (s.tile_depth != PF_TILE_DEPTH_RAY) return "planar-depth tiles (PF_TILE_DEPTH / SetTileDepth)";
+    if (s.consistent >= 0.0) return "PF_REG_CONSISTENT";
+    if (s.global_align) return "PF_GLOBAL_ALIGN";
+    if (s.fusion == MergeSwitches::SMOOTHING) return "PF_FUSION=smoothing";
+    if (s.fusion == MergeSwitches::STITCH) return "PF_FUSION=stitch";
+    if (s.check_laplacian) return "PF_CHECK_LAPLACIAN";
+    return nullptr;
+}
+
+// The weight set of this call on the device, in the packed tiles' layout (one channel): the tent,
+// or channel 0 of every tile file's weight map F + SUFFIX, which must have the tile's size.
+DevMem weights_on_device(pf_ctx* c, const pfw::Spec& spec, const std::vector<std::string>& pmap_fns,
+                         const std::vector<PerspectiveMap>& pmaps)
+{
+    DevMem none(0);
+    none.ok = false;
+    size_t total = 0;
+    for (const PerspectiveMap& p : pmaps) total += (size_t)p.width * p.height;
+    if (spec.mode == pfw::TENT) {
+        DevMem dw(sizeof(float) * total);
+        if (!dw.ok || !pf_ok(c, pf_tile_tent_weights(c, dw.as<float>()), "pf_tile_tent_weights"))
+            return none;
+        return dw;
+    }
+    std::vector<float> packed(total);
+    size_t off = 0;
+    for (size_t i = 0; i < pmaps.size(); i++) {
+        std::string fn = pfw::weight_file(pmap_fns[i], spec), err;
+        // a PFM is read raw (its floats as stored, rows in file order: the map loaders would scale
+        // them as depth in metres), anything else as a tile is: a PNG's samples in 0-1
+        const bool pfm = fn.size() >= 3 && fn.compare(fn.size() - 3, 3, "pfm") == 0;
+        PerspectiveMap img;
+        int w = 0, h = 0, ch = 0;
+        float* raw = pfm ? pfio::load_pfm(fn, &w, &h, &ch, err) : nullptr;
+        if (pfm ? !raw : !img.Load(fn)) {
+            std::cout << "[MergeDepthMaps] cannot load the weight map " << fn
+                      << (err.empty() ? "" : ": ") << err << std::endl;
+            return none;
+        }
+        if (!pfm) w = img.width, h = img.height, ch = img.channels;
+        const float* px = pfm ? raw : img.data;
+        const bool fits = pfw::size_matches(fn, w, h, pmaps[i].width, pmaps[i].height, err);
+        if (fits) {
+            const size_t n = (size_t)w * h;
+            for (size_t k = 0; k < n; k++) packed[off + k] = px[k * ch];
+            off += n;
+        } else {
+            std::cout << "[MergeDepthMaps] " << err << std::endl;
+        }
+        std::free(raw);
+        if (!fits) return none;
+    }
+    return DevMem(packed.data(), packed.size());
+}
+
+// The weighted registration (pf_register_weighted, the tiles untouched) and one "[weights] tile
+// <i>: <n> of <N> samples used, sum w <s>" line per tile.
+bool register_weighted(const Job& j, float* d_coeffs, const float* d_weights, int ntiles)
+{
+    const EquirectangularMap& e = j.emap;
+    DevMem ds(sizeof(double) * 2 * ntiles), dn(sizeof(long long) * 2 * ntiles);
+    std::vector<double> sm((size_t)2 * ntiles);
+    std::vector<long long> total((size_t)2 * ntiles);
+    if (!ds.ok || !dn.ok ||
+        !pf_ok(j.c, pf_tile_valid_counts(j.c, j.d_tiles, j.d_emap, e.width, e.height, e.channels, 1,
+                                         j.zr[0], j.zr[1], dn.as<long long>()),
+               "pf_tile_valid_counts") ||
+        !call_sync(j.c, pf_register_weighted(j.c, j.d_emap, e.width, e.height, e.channels,
+                                             j.d_tiles, d_weights, 1, 1, j.zr[0], j.zr[1], 0,
+                                             d_coeffs, nullptr, ds.as<double>()),
+                   "pf_register_weighted") ||
+        !download(sm.data(), ds, sm.size()) || !download(total.data(), dn, total.size()))
+        return false;
+    for (int p = 0; p < ntiles; p++)
+        std::cout << pfw::weights_line(p, sm[(size_t)2 * p], total[(size_t)2 * p],
+                                       sm[(size_t)2 * p + 1])
+                  << std::endl;
+    return true;
+}
+
 // The fusion (Depth.cpp:904-913), or the smoothing (:919-922) / the stitch (:851) on the
 // registered tiles.
 bool fuse(const Job& j, const MergeSwitches& s)
@@ -435,6 +534,16 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
     const auto t_begin = std::chrono::steady_clock::now();
     MergeSwitches sw;
     if (!read_merge_switches(sw)) return false;
+    // the weighted forms stand alone: refused before any file is read
+    const bool weighted = sw.weights.mode != pfw::OFF;
+    if (weighted) {
+        if (const char* what = weights_conflict(sw, disparity_tiles)) {
+            std::cout << "[MergeDepthMaps] tile weights (PF_TILE_WEIGHTS / SetTileWeights) have no "
+                         "form for "
+                      << what << ": switch one of the two off" << std::endl;
+            return false;
+        }
+    }
     // the entry points that cannot honour the validity rule: refused before any file is read
     if (sw.rule.on && (disparity_tiles || sw.fusion == MergeSwitches::SMOOTHING)) {
         std::cout << "[MergeDepthMaps] "
@@ -522,8 +631,12 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
     if (planar && !print_tile_depth_line(c, pmaps)) return false;
 
     if (sw.rule.on && !print_mask_lines(j, (int)pmaps.size(), sw.rule)) return false;
+    DevMem dw = weighted ? weights_on_device(c, sw.weights, pmap_fns, pmaps) : DevMem(0);
+    if (!dw.ok) return false;
     auto t = std::chrono::steady_clock::now();
-    if (sw.consistent >= 0.0
+    // with weights nothing else is on (weights_conflict): the weighted pair of calls
+    if (weighted ? !register_weighted(j, dc.as<float>(), dw.as<float>(), (int)pmaps.size())
+        : sw.consistent >= 0.0
             ? !register_consistent(j, dc.as<float>(), (int)pmaps.size(), sw.consistent)
             : !register_tiles(j, dc.as<float>(), disparity_tiles, (int)pmaps.size(), sw.loss, planar))
         return false;
@@ -534,7 +647,12 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
         return false;
     if (time_Reg) *time_Reg = elapsed_ms(t);
     t = std::chrono::steady_clock::now();
-    if (!fuse(j, sw)) return false;
+    if (weighted ? !call_sync(c, pf_fuse_weighted(c, j.d_emap, emap.width, emap.height,
+                                                  emap.channels, j.d_tiles, dw.as<float>(), 1,
+                                                  j.d_coeffs, 1, j.w, j.h, zr[0], zr[1], j.d_out),
+                              "pf_fuse_weighted")
+                 : !fuse(j, sw))
+        return false;
     if (time_Laplacian) *time_Laplacian = elapsed_ms(t);
     if (sw.check_laplacian && !print_laplacian_check(j)) return false;
     if (sw.save_stitch && !save_stitch(j, out_fn)) return false;

@@ -170,6 +170,14 @@ float* pf::run_jacobi(pf_ctx* c, const LevelDims& L, const JacobiRun& r, int* np
     return src;
 }
 
+// PF_WTGT_LEVELS=1 (read per call): the weighted fusion gathers its targets level by level
+// (k_targets_patch_weighted) instead of in one launch; the planes are the same bit for bit.
+static bool weighted_per_level()
+{
+    const char* e = getenv("PF_WTGT_LEVELS");
+    return e && e[0] == '1';
+}
+
 // Floats of the per-level target planes of one panorama (fuse_range's lnorm workspace).
 static long long target_planes(const LevelCache& lc)
 {
@@ -225,9 +233,24 @@ static int fuse_range(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
             bytes += (double)batch * (4.0 * L.w * (L.h1 - L.h0 + 1) + 4.0 * (double)lc.taps[l]);
         }
         StageTimer t(c, PF_STAGE_TARGETS, bytes, 1);
-        launch_targets_multi(c->stream, (const TileGeom*)c->geom.p, c->ntiles, tiles,
-                             c->tile_elems, coeffs, M, (const int2*)lc.tgt_order.p, batch,
-                             c->valid);
+        if (c->wts && weighted_per_level()) {  // pf_fuse_weighted, one launch per level
+            t.set_launches(lc.nlevels);
+            for (int l = 0; l < lc.nlevels; l++) {
+                const TgtLevel& T = M.lv[l];
+                launch_targets_patch_weighted(c->stream, (const TileGeom*)c->geom.p, T.box, T.tb,
+                                              c->ntiles, T.map, tiles, c->tile_elems, c->wts,
+                                              c->wts_stride, coeffs, T.L, T.lnorm, T.lstride,
+                                              batch, T.tmask, T.nmw);
+            }
+        } else if (c->wts) {  // pf_fuse_weighted / pf_merge_weighted
+            launch_targets_multi_weighted(c->stream, (const TileGeom*)c->geom.p, c->ntiles, tiles,
+                                          c->tile_elems, c->wts, c->wts_stride, coeffs, M,
+                                          (const int2*)lc.tgt_order.p, batch);
+        } else {
+            launch_targets_multi(c->stream, (const TileGeom*)c->geom.p, c->ntiles, tiles,
+                                 c->tile_elems, coeffs, M, (const int2*)lc.tgt_order.p, batch,
+                                 c->valid);
+        }
     }
     for (int l = 0; l < lc.nlevels; l++) {
         const LevelDims& L = lc.dims[l];
@@ -317,9 +340,9 @@ static int fuse_range(pf_ctx* c, const float* emap, int ew, int eh, int ec, cons
 // streams, so that one half's coarse levels overlap the other's fine levels, was measured slower:
 // 10.4-10.6k vs 11.6k panoramas/s at batch 64 -- the half-size passes lose more than the
 // overlap wins.)
-static int fuse_impl(pf_ctx* c, const float* emap, int ew, int eh, int ec, const float* tiles,
-                     const float* coeffs, int batch, int out_w, int out_h, float zr0,
-                     float zr1, uint16_t* out)
+int pf::fuse_impl(pf_ctx* c, const float* emap, int ew, int eh, int ec, const float* tiles,
+                  const float* coeffs, int batch, int out_w, int out_h, float zr0, float zr1,
+                  uint16_t* out)
 {
     int rc;
     if ((rc = prepare_levels(c, out_w, out_h, zr0, zr1))) return rc;

@@ -315,6 +315,31 @@ int targets_batch();
 void launch_targets_multi(hipStream_t s, const TileGeom* geom, int ntiles, const float* tiles,
                           long long tstride, const float* coeffs, const TgtMulti& M,
                           const int2* order, int batch, TileValid tv = TileValid{0, 0.0f, 0.0f});
+// Per-pixel tile weights (pf_fuse_weighted): the two gathers with a weight plane in the tiles'
+// element layout (panorama b at weights + b * wstride; wstride 0: one set for the batch).  Wave
+// form only: tstride <= targets_weighted_max_elems().
+long long targets_weighted_max_elems();
+void launch_targets_multi_weighted(hipStream_t s, const TileGeom* geom, int ntiles,
+                                   const float* tiles, long long tstride, const float* weights,
+                                   long long wstride, const float* coeffs, const TgtMulti& M,
+                                   const int2* order, int batch);
+void launch_targets_patch_weighted(hipStream_t s, const TileGeom* geom, const TileBox* box,
+                                   const TapBox* tb, int ntiles, const int32_t* map,
+                                   const float* tiles, long long tstride, const float* weights,
+                                   long long wstride, const float* coeffs, LevelDims L,
+                                   float* lnorm, long long lstride, int batch,
+                                   const uint32_t* tmask, int nmw);
+// The weighted registration (pf_register_weighted, pf_register.hip): the 15 moment sums with every
+// term times (double)w, the count of used samples in a 16th; needs sidx.  summary (optional):
+// [batch][ntiles][2] doubles {used samples, sum of w}.
+void launch_register_weighted(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
+                              int ntiles, const float* emap, long long estride,
+                              const float* tiles, long long tstride, const float* weights,
+                              long long wstride, float* coeffs, double* coeffs64,
+                              double* summary, int batch, const int2* sidx);
+// pf_tile_tent_weights (pf_weight.hip): the blending tent of every tile, one set
+void launch_tent_weights(hipStream_t s, const TileGeom* geom, int ntiles, long long tile_pixels,
+                         float* weights);
 bool jstream_supported_T(int T);
 int jstream_waves_per_cu(int T, bool fast);
 void launch_jstream(hipStream_t s, const JacobiPass& P, int T, int batch, bool fast);

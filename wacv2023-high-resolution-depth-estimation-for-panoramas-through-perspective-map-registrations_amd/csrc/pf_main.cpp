@@ -83,6 +83,14 @@
 // Not with --tile-model disparity or --global-align (refused here), nor with --tile-valid,
 // --reg-loss or --tile-depth planar (refused with the library's message).  Carried in
 // PF_REG_CONSISTENT; not in the usage text either.
+// --tile-weights tent|files:SUFFIX (opt-in): per-pixel tile weights (pf_register_weighted,
+// pf_fuse_weighted).  tent is the blending tent of every tile; with files:SUFFIX the weight map of a
+// tile file F is F + SUFFIX (a PNG in 0-1 or a PFM of the tile's size, else the run names the file
+// and fails).  A weight outside (0, +inf) switches its pixel off.  The run prints per tile
+// "[weights] tile <i>: <n> of <N> samples used, sum w <s>".  Not with --tile-valid, --reg-loss,
+// --tile-depth planar, --reg-consistent, --tile-model disparity, --global-align, --check-laplacian
+// or --fusion smoothing|stitch (refused here).  Carried in PF_TILE_WEIGHTS; not in the usage text
+// either.
 #include "pf_facade.hpp"  // the inline to_window and load_pair; it includes the two public headers
 #include "pf_ray.hpp"
 #include "pf_valid.hpp"
@@ -346,6 +354,7 @@ static int mode0_command(int argc, char* argv[])
     std::string tiles = "test_images", ext = "auto", fusion;
     int width = 2048, device = 0, shard = 0, nshards = 1;
     bool check_laplacian = false, consistent = false, global_align = false, disparity = false;
+    bool weights = false, planar = false, tile_valid = false, reg_loss = false;
     const auto on_switch = [&](const std::string& k) {
         if (k == "--check-laplacian") check_laplacian = true;
         if (k == "--global-align") global_align = true;
@@ -361,15 +370,18 @@ static int mode0_command(int argc, char* argv[])
             float lo, hi;
             std::string err;
             if (!pfv::parse_range(v.c_str(), lo, hi, err)) return bad(k, v, "LO:HI, LO < HI");
+            tile_valid = true;
             setenv("PF_TILE_VALID", v.c_str(), 1);  // read by MergeDepthMaps
         }
         else if (k == "--reg-loss") {
             pff::RegLossRule r;
             if (!pff::parse_reg_loss(v.c_str(), r)) return bad(k, v, "huber:A or softl1:A, A > 0");
+            reg_loss = true;
             setenv("PF_REG_LOSS", v.c_str(), 1);  // read by MergeDepthMaps / MergeDisparityMaps
         }
         else if (k == "--tile-depth") {
             if (pf::parse_tile_depth(v.c_str()) < 0) return bad(k, v, "planar or ray");
+            planar = v == "planar";
             setenv("PF_TILE_DEPTH", v.c_str(), 1);  // read by MergeDepthMaps / MergeDisparityMaps
         }
         else if (k == "--reg-consistent") {
@@ -379,6 +391,14 @@ static int mode0_command(int argc, char* argv[])
                 return bad(k, v, "a finite LAMBDA >= 0");
             consistent = true;
             setenv("PF_REG_CONSISTENT", v.c_str(), 1);  // read by MergeDepthMaps
+        }
+        else if (k == "--tile-weights") {
+            pfw::Spec spec;
+            std::string err;
+            if (!pfw::parse_spec(v.c_str(), spec, err) || spec.mode == pfw::OFF)
+                return bad(k, v, "tent or files:SUFFIX");
+            weights = true;
+            setenv("PF_TILE_WEIGHTS", v.c_str(), 1);  // read by MergeDepthMaps
         }
         else if (k == "--shard") {  // R/N: one process per GPU over the sorted folder
             if (std::sscanf(v.c_str(), "%d/%d", &shard, &nshards) != 2 || nshards < 1 ||
@@ -404,6 +424,23 @@ static int mode0_command(int argc, char* argv[])
         std::cout << "--reg-consistent registers depth tiles by a linear solve: not with "
                   << (disparity ? "--tile-model disparity" : "--global-align") << std::endl;
         return 2;
+    }
+    if (weights) {  // the weighted forms stand alone: refused before any GPU call
+        const char* clash = tile_valid              ? "--tile-valid"
+                            : reg_loss              ? "--reg-loss"
+                            : planar                ? "--tile-depth planar"
+                            : consistent            ? "--reg-consistent"
+                            : disparity             ? "--tile-model disparity"
+                            : global_align          ? "--global-align"
+                            : fusion == "smoothing" ? "--fusion smoothing"
+                            : fusion == "stitch"    ? "--fusion stitch"
+                            : check_laplacian       ? "--check-laplacian"
+                                                    : nullptr;
+        if (clash) {
+            std::cout << "--tile-weights registers and fuses with per-pixel weights: not with "
+                      << clash << std::endl;
+            return 2;
+        }
     }
     if (!select_device(device)) return 1;
     return pf_create_depth_panoramas(argv[2], argv[3], argv[4], argv[5], tiles, ext, width, shard,

@@ -1,5 +1,5 @@
 // pf_register.hip -- the moment-form cubic registration: the 15 fp64 moment sums of a tile's samples
-// (k_register, k_register_valid), their solve by least squares or by the reference's Ceres 1.13
+// (k_register, k_register_valid; k_register_weighted with a weight per sample), their solve by least squares or by the reference's Ceres 1.13
 // trust-region LM (lm_moments over lm_solve, pf_lm.hpp), the joint and global solves on the same
 // sums (k_register_joint, k_global_solve), the cached sample indices (k_regidx) and
 // Depth2DepthTransform (k_apply_cubic, k_d2d_map); for planar-depth tiles (pf_set_tile_depth) the
@@ -342,6 +342,88 @@ __global__ void __launch_bounds__(kRegLanes) k_register_planar_valid(
                               vlo, vhi, part, kfs);
 }
 
+// The third form of register_tile (k_register_weighted, pf_register_weighted): per-pixel weights
+// in the tiles' element layout.  Sample s of tile p is used iff its weight w = weights[sidx[s].x]
+// is usable (0 < w < +inf), its raw tile value is finite and its baseline value is finite; a used
+// sample adds W * t_k to sum k, W = (double)w and t_k the term k_register forms, so acc[9] is the
+// sum of w and the count of used samples travels in a 16th sum.  These are J'J, J'y and y'y of
+// the residuals times sqrt(w): the reference's Weight = sqrt(w) in FunctorDepth2Depth3
+// (Depth.cpp:1122-1138).  The lane-to-sample order and the halving tree are k_register's, so with
+// every weight 1.0f the sums are k_register's bit for bit (1.0 * t is t).  Degree 3, the LM.
+__global__ void __launch_bounds__(kRegLanes) k_register_weighted(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, const float* __restrict__ weights, long long wstride,
+    float* __restrict__ coeffs, double* __restrict__ coeffs64, double* __restrict__ summary,
+    const int2* __restrict__ sidx)
+{
+    constexpr int kNS = kRegSums + 1;
+    __shared__ double part[kNS][kRegLanes];
+    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
+    const int p = (int)(lb % (unsigned)ntiles), b = (int)(lb / (unsigned)ntiles), l = threadIdx.x;
+    const TileGeom g = geom[p];
+    const RegGrid rg = grids[p];
+    const float* tile = tiles + b * tstride + g.off;
+    const float* wt = weights + b * wstride + g.off;
+    const float* em = emap + b * estride;
+    const int ns = (rg.cols + 1) * (rg.rows + 1);
+    double acc[kNS];
+#pragma unroll
+    for (int k = 0; k < kNS; k++) acc[k] = 0.0;
+    constexpr int kRegU = 4;  // the gathers of a group issue together, then add in sample order
+    for (int s0 = l; s0 < ns; s0 += kRegU * kRegLanes) {
+        float tv[kRegU], ev[kRegU], wv[kRegU];
+#pragma unroll
+        for (int u = 0; u < kRegU; u++) {
+            const int s = s0 + u * kRegLanes;
+            tv[u] = ev[u] = wv[u] = 0.0f;
+            if (s >= ns) continue;
+            const int2 ix = sidx[rg.soff + s];
+            tv[u] = tile[ix.x];
+            wv[u] = wt[ix.x];
+            ev[u] = em[ix.y];
+        }
+#pragma unroll
+        for (int u = 0; u < kRegU; u++) {
+            if (s0 + u * kRegLanes >= ns) break;
+            if (!(0.0f < wv[u] && wv[u] < __uint_as_float(0x7F800000u) && isfinite(tv[u]) &&
+                  isfinite(ev[u])))
+                continue;
+            const double W = (double)wv[u];
+            double X = clamp_sample((double)tv[u]);
+            double Yv = clamp_sample((double)ev[u]);
+            double X2 = X * X, X3 = X * X * X;
+            acc[0] = acc[0] + W * (X3 * X3); acc[1] = acc[1] + W * (X3 * X2);
+            acc[2] = acc[2] + W * (X3 * X);  acc[3] = acc[3] + W * X3;
+            acc[4] = acc[4] + W * (X2 * X2); acc[5] = acc[5] + W * (X2 * X);
+            acc[6] = acc[6] + W * X2;        acc[7] = acc[7] + W * (X * X);
+            acc[8] = acc[8] + W * X;         acc[9] = acc[9] + W * 1.0;
+            acc[10] = acc[10] + W * (X3 * Yv); acc[11] = acc[11] + W * (X2 * Yv);
+            acc[12] = acc[12] + W * (X * Yv);  acc[13] = acc[13] + W * Yv;
+            acc[14] = acc[14] + W * (Yv * Yv);
+            acc[15] = acc[15] + 1.0;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kNS; k++) part[k][l] = acc[k];
+    __syncthreads();
+    for (int stride = kRegLanes / 2; stride >= 1; stride >>= 1) {
+        if (l < stride)
+            for (int k = 0; k < kNS; k++) part[k][l] = part[k][l] + part[k][l + stride];
+        __syncthreads();
+    }
+    if (l == 0) {
+        double S[kNS];
+        for (int k = 0; k < kNS; k++) S[k] = part[k][0];
+        const long long o = (long long)b * ntiles + p;
+        solve_store_valid(S, 3, PF_SOLVER_LM, coeffs, coeffs64, o * 4, S[kRegSums]);
+        if (summary) {
+            summary[o * 2] = S[kRegSums];
+            summary[o * 2 + 1] = S[9];
+        }
+    }
+}
+
 // pf_tile_valid_counts: block (p, b) counts the registration samples k_register_valid keeps and
 // the tile's pixels that pass the rule (every one with the rule off), as wave ballots summed
 // through LDS.
@@ -557,6 +639,17 @@ void launch_register(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
         hipLaunchKernelGGL(k_register, grid, dim3(kRegLanes), 0, s, geom, grids, rcols, rrows,
                            ntiles, emap, ew, eh, ec, estride, tiles, tstride, degree, solver,
                            coeffs, coeffs64, sums, active, sidx);
+}
+
+void launch_register_weighted(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
+                              int ntiles, const float* emap, long long estride,
+                              const float* tiles, long long tstride, const float* weights,
+                              long long wstride, float* coeffs, double* coeffs64,
+                              double* summary, int batch, const int2* sidx)
+{
+    hipLaunchKernelGGL(k_register_weighted, dim3((unsigned)(ntiles * batch)), dim3(kRegLanes), 0,
+                       s, geom, grids, ntiles, emap, estride, tiles, tstride, weights, wstride,
+                       coeffs, coeffs64, summary, sidx);
 }
 
 void launch_valid_counts(hipStream_t s, const TileGeom* geom, const RegGrid* grids, int ntiles,

@@ -15,7 +15,8 @@
 //     five-point sums in std::map key order, then the normalisation of Depth.cpp:1626-1647.
 //     targets_wave (round 7, PF_TGT_WAVE=1, the default) is the same gather with one wave per
 //     patch and the grid rows in registers instead of LDS; targets_patch stays for the validity
-//     rule, the sharded partial sums and as the tests' reference.
+//     rule, the sharded partial sums and as the tests' reference.  targets_wave_weighted
+//     (pf_fuse_weighted) is targets_wave with a weight per tap beside the value.
 #include "pf_internal.hpp"
 
 #include <cstdlib>
@@ -604,6 +605,201 @@ __global__ void __launch_bounds__(256) k_targets_multi_valid(
                                    T.nmw, vlo, vhi);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Per-pixel tile weights (pf_fuse_weighted, pf_merge_weighted): targets_wave with a second plane.
+// `weights` has the tiles' element layout (panorama b at weights + b * wstride; wstride 0: one set
+// for the batch), so a tap's weight sits at the tap's own byte offset mi[r] / mr from a second
+// base pointer.  Staging: the usable weight u(w) = w if 0 < w < +inf, else 0; the tap's value is a
+// quiet NaN unless u(w) > 0 and its (transformed) value is finite.  Tile p contributes to a pixel
+// iff its five-point sum Lp, formed as ever, is not NaN, with wmin = the smallest of the five
+// staged weights (then > 0): acc = acc + wmin * Lp, ws = ws + wmin, a separate fp32 multiply and
+// add, tiles in index order.  The pixel is acc * (1.0f / ws), or the marker when ws == 0.  With
+// weights in {0, 1} that is targets_patch<MASK> under (-inf, +inf) bit for bit, and with every
+// weight 1.0f it is targets_wave.
+//
+// Registers: the value rows and the weight rows of one panorama are in flight (NP = 1) and a wave
+// owns kTWB = 4 panoramas (two accumulators per pixel and panorama): DESIGN.md section 12 has the
+// compiler's count.  The weights of a shared set are loaded once per tile, not once per panorama.
+static constexpr int kTWB = 4;
+
+__device__ __forceinline__ float usable_weight(float w)
+{
+    return (0.0f < w && w < __uint_as_float(0x7F800000u)) ? w : 0.0f;
+}
+
+template <bool XFORM, int NB>
+__device__ __forceinline__ void targets_wave_weighted(
+    const TileGeom* __restrict__ geom, const TileBox* __restrict__ box,
+    const TapBox* __restrict__ tb, int ntiles, const int32_t* __restrict__ map,
+    const float* __restrict__ tiles, long long tstride, const float* __restrict__ weights,
+    long long wstride, const float* __restrict__ coeffs, const LevelDims& L, int npx, int pid,
+    int bgrp, float* __restrict__ lnorm, long long lstride, int batch,
+    const uint32_t* __restrict__ tmask, int nmw)
+{
+    const int X0 = (pid % npx) * kTPW, Y0 = L.h0 + (pid / npx) * kTPH;
+    const int lane = threadIdx.x & 63;
+    const int X = X0 + lane;
+    const int bbeg = bgrp * NB;
+    float acc[kTPH][NB], ws[kTPH][NB];
+#pragma unroll
+    for (int j = 0; j < kTPH; j++) {
+#pragma unroll
+        for (int q = 0; q < NB; q++) acc[j][q] = ws[j][q] = 0.0f;
+    }
+    const int X1 = min(X0 + kTPW - 1, L.w - 1), Y1 = min(Y0 + kTPH - 1, L.h1);
+    // one tile's contribution (tiles come in index order)
+    auto tile = [&](const int p) {
+        // the tap-map byte offsets of the tile's grid and of this lane's ring point, clamped to
+        // the tap box as in targets_wave: shared by the value and the weight gathers
+        uint32_t mi[kTGH], mr;
+        {
+            const TapBox B = tb[p];
+            const int gx = max(min(X - B.xmin, B.nx - 1), 0);
+#pragma unroll
+            for (int r = 0; r < kTGH; r++) {
+                const int gy = max(min(Y0 - 1 + r - B.ymin, B.ny - 1), 0);  // wave-uniform
+                mi[r] = (uint32_t)map[B.off + (long long)gy * B.nx + gx] * 4u;
+            }
+            const bool reast = lane >= kRingE && lane < kRingE + kTPH;
+            const int rj = reast ? lane - kRingE : lane < kTPH ? lane : 0;
+            const int rX = reast ? X0 + kTPW : X0 - 1;
+            const int rgx = max(min(rX - B.xmin, B.nx - 1), 0);
+            const int rgy = max(min(Y0 + rj - B.ymin, B.ny - 1), 0);
+            mr = (uint32_t)map[B.off + (long long)rgy * B.nx + rgx] * 4u;
+        }
+        const long long toff = geom[p].off;
+        const TileBox bx = box[p];
+        uint32_t in = 0;  // bit j: the tile covers this lane's pixel of patch row j
+#pragma unroll
+        for (int j = 0; j < kTPH; j++) {
+            const int Y = Y0 + j;
+            if (X < L.w && Y <= L.h1 && Y > L.h0 && Y < L.h1 && in_box2(bx, X, Y)) in |= 1u << j;
+        }
+        float w[kTGH], wr;
+        auto load_weights = [&](const int b) {
+            const char* wv = reinterpret_cast<const char*>(weights + b * wstride + toff);
+#pragma unroll
+            for (int r = 0; r < kTGH; r++)
+                w[r] = usable_weight(*reinterpret_cast<const float*>(wv + mi[r]));
+            wr = usable_weight(*reinterpret_cast<const float*>(wv + mr));
+        };
+        if (wstride == 0) load_weights(0);  // wave-uniform
+#pragma unroll
+        for (int q = 0; q < NB; q++) {
+            const int b = bbeg + q < batch ? bbeg + q : batch - 1;
+            const char* tv = reinterpret_cast<const char*>(tiles + b * tstride + toff);
+            float v[kTGH], vr;
+#pragma unroll
+            for (int r = 0; r < kTGH; r++) v[r] = *reinterpret_cast<const float*>(tv + mi[r]);
+            vr = *reinterpret_cast<const float*>(tv + mr);
+            if (wstride != 0) load_weights(b);
+            if constexpr (XFORM) {
+                const float4 k =
+                    *reinterpret_cast<const float4*>(coeffs + ((long long)b * ntiles + p) * 4);
+#pragma unroll
+                for (int r = 0; r < kTGH; r++) v[r] = cubic_map(v[r], k.x, k.y, k.z, k.w);
+                vr = cubic_map(vr, k.x, k.y, k.z, k.w);
+            }
+            const float qnan = __uint_as_float(0x7FC00000u);
+#pragma unroll
+            for (int r = 0; r < kTGH; r++)
+                if (!(w[r] > 0.0f && isfinite(v[r]))) v[r] = qnan;
+            if (!(wr > 0.0f && isfinite(vr))) vr = qnan;
+#pragma unroll
+            for (int j = 0; j < kTPH; j++) {
+                // every lane runs the DPP moves: a lane switched off is no source lane
+                const float W = dpp_west(lane_value(vr, j), v[j + 1]);
+                const float E = dpp_east(lane_value(vr, kRingE + j), v[j + 1]);
+                const float wW = dpp_west(lane_value(wr, j), w[j + 1]);
+                const float wE = dpp_east(lane_value(wr, kRingE + j), w[j + 1]);
+                // taps in std::map key order: (X-1,Y), (X,Y-1), (X,Y), (X,Y+1), (X+1,Y)
+                float Lp = 0;
+                Lp += W * -0.25f;
+                Lp += v[j] * -0.25f;
+                Lp += v[j + 1] * 1.0f;
+                Lp += v[j + 2] * -0.25f;
+                Lp += E * -0.25f;
+                const float wmin = fminf(fminf(fminf(wW, w[j]), fminf(w[j + 1], w[j + 2])), wE);
+                if ((in & (1u << j)) && Lp == Lp) {
+                    acc[j][q] = acc[j][q] + wmin * Lp;
+                    ws[j][q] = ws[j][q] + wmin;
+                }
+            }
+        }
+    };
+    // the tiles whose box meets this patch, as mask words: the host's list, or the box tests
+    const int nw = (ntiles + 31) / 32;
+    for (int wd = 0; wd < nw; wd++) {
+        uint32_t m = 0;  // wave-uniform
+        if (tmask) {
+            m = tmask[(long long)pid * nmw + wd];
+        } else {
+            for (int p = wd * 32; p < min(wd * 32 + 32, ntiles); p++)
+                if (box_meets(box[p], X0, X1, Y0, Y1)) m |= 1u << (p & 31);
+        }
+        while (m) {
+            tile(wd * 32 + __builtin_ctz(m));
+            m &= m - 1;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kTPH; j++) {
+        const int Y = Y0 + j;
+        if (!(X < L.w && Y <= L.h1)) continue;
+        const long long o = (long long)Y * L.w + X;
+#pragma unroll
+        for (int q = 0; q < NB; q++) {
+            const int b = bbeg + q;
+            if (b >= batch) break;
+            const float out = ws[j][q] == 0.0f ? __uint_as_float(PF_NAN_MARKER)
+                                               : acc[j][q] * (1.0f / ws[j][q]);
+            __builtin_nontemporal_store(out, &lnorm[b * lstride + o]);
+        }
+    }
+}
+
+// The weighted gather of one level (k_targets_patch's wave form) and of every level in one launch
+// (k_targets_multi's): the same work items, tables and order.
+template <bool XFORM, int NB>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+k_targets_patch_weighted(const TileGeom* __restrict__ geom, const TileBox* __restrict__ box,
+                         const TapBox* __restrict__ tb, int ntiles,
+                         const int32_t* __restrict__ map, const float* __restrict__ tiles,
+                         long long tstride, const float* __restrict__ weights, long long wstride,
+                         const float* __restrict__ coeffs, LevelDims L, int npx, int npatch,
+                         float* __restrict__ lnorm, long long lstride, int batch,
+                         const uint32_t* __restrict__ tmask, int nmw)
+{
+    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
+    const unsigned item =  // wave-uniform, and in scalar registers
+        lb * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (item >= (unsigned)npatch * (unsigned)((batch + NB - 1) / NB)) return;
+    targets_wave_weighted<XFORM, NB>(geom, box, tb, ntiles, map, tiles, tstride, weights, wstride,
+                                     coeffs, L, npx, (int)(item % (unsigned)npatch),
+                                     (int)(item / (unsigned)npatch), lnorm, lstride, batch, tmask,
+                                     nmw);
+}
+
+template <bool XFORM, int NB>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+k_targets_multi_weighted(const TileGeom* __restrict__ geom, int ntiles,
+                         const float* __restrict__ tiles, long long tstride,
+                         const float* __restrict__ weights, long long wstride,
+                         const float* __restrict__ coeffs, TgtMulti M,
+                         const int2* __restrict__ order, int batch)
+{
+    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
+    const unsigned item =  // wave-uniform, and in scalar registers
+        lb * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (item >= (unsigned)M.nentries * (unsigned)((batch + NB - 1) / NB)) return;
+    const int2 ent = order[item % (unsigned)M.nentries];  // (level, patch)
+    const TgtLevel& T = M.lv[ent.x];
+    targets_wave_weighted<XFORM, NB>(geom, T.box, T.tb, ntiles, T.map, tiles, tstride, weights,
+                                     wstride, coeffs, T.L, T.npx, ent.y,
+                                     (int)(item / (unsigned)M.nentries), T.lnorm, T.lstride, batch,
+                                     T.tmask, T.nmw);
+}
+
 // PF_TGT_WAVE (read per call): 1 = the per-wave gather, 0 = the block form.  The validity-rule
 // kernels and k_targets_patch_partial have the block form only, and so have layouts of more than
 // 2^30 tile elements per panorama.
@@ -737,6 +933,61 @@ void launch_targets_patch(hipStream_t s, const TileGeom* geom, const TileBox* bo
         hipLaunchKernelGGL((k_targets_patch<false, kTNB>), g, dim3(256), 0, s, geom, box, tb,
                            ntiles, map, tiles, tstride, coeffs, L, npx, npatch, lnorm, lstride,
                            batch, tmask, nmw);
+}
+
+// The weighted gathers have the wave form only: the callers refuse layouts of more than 2^30 tile
+// elements per panorama (targets_weighted_max_elems).
+long long targets_weighted_max_elems() { return 1ll << 30; }
+
+void launch_targets_multi_weighted(hipStream_t s, const TileGeom* geom, int ntiles,
+                                   const float* tiles, long long tstride, const float* weights,
+                                   long long wstride, const float* coeffs, const TgtMulti& M,
+                                   const int2* order, int batch)
+{
+    const int nb = batch == 1 ? 1 : kTWB;
+    const dim3 gw((unsigned)(((long long)M.nentries * ((batch + nb - 1) / nb) + 3) / 4));
+    if (nb == 1 && coeffs)
+        hipLaunchKernelGGL((k_targets_multi_weighted<true, 1>), gw, dim3(256), 0, s, geom, ntiles,
+                           tiles, tstride, weights, wstride, coeffs, M, order, batch);
+    else if (nb == 1)
+        hipLaunchKernelGGL((k_targets_multi_weighted<false, 1>), gw, dim3(256), 0, s, geom, ntiles,
+                           tiles, tstride, weights, wstride, coeffs, M, order, batch);
+    else if (coeffs)
+        hipLaunchKernelGGL((k_targets_multi_weighted<true, kTWB>), gw, dim3(256), 0, s, geom,
+                           ntiles, tiles, tstride, weights, wstride, coeffs, M, order, batch);
+    else
+        hipLaunchKernelGGL((k_targets_multi_weighted<false, kTWB>), gw, dim3(256), 0, s, geom,
+                           ntiles, tiles, tstride, weights, wstride, coeffs, M, order, batch);
+}
+
+void launch_targets_patch_weighted(hipStream_t s, const TileGeom* geom, const TileBox* box,
+                                   const TapBox* tb, int ntiles, const int32_t* map,
+                                   const float* tiles, long long tstride, const float* weights,
+                                   long long wstride, const float* coeffs, LevelDims L,
+                                   float* lnorm, long long lstride, int batch,
+                                   const uint32_t* tmask, int nmw)
+{
+    const int npx = (L.w + kTPW - 1) / kTPW;
+    const int npy = (L.h1 - L.h0 + 1 + kTPH - 1) / kTPH;
+    const int npatch = npx * npy;
+    const int nb = batch == 1 ? 1 : kTWB;
+    const dim3 gw((unsigned)(((long long)npatch * ((batch + nb - 1) / nb) + 3) / 4));
+    if (nb == 1 && coeffs)
+        hipLaunchKernelGGL((k_targets_patch_weighted<true, 1>), gw, dim3(256), 0, s, geom, box, tb,
+                           ntiles, map, tiles, tstride, weights, wstride, coeffs, L, npx, npatch,
+                           lnorm, lstride, batch, tmask, nmw);
+    else if (nb == 1)
+        hipLaunchKernelGGL((k_targets_patch_weighted<false, 1>), gw, dim3(256), 0, s, geom, box,
+                           tb, ntiles, map, tiles, tstride, weights, wstride, coeffs, L, npx,
+                           npatch, lnorm, lstride, batch, tmask, nmw);
+    else if (coeffs)
+        hipLaunchKernelGGL((k_targets_patch_weighted<true, kTWB>), gw, dim3(256), 0, s, geom, box,
+                           tb, ntiles, map, tiles, tstride, weights, wstride, coeffs, L, npx,
+                           npatch, lnorm, lstride, batch, tmask, nmw);
+    else
+        hipLaunchKernelGGL((k_targets_patch_weighted<false, kTWB>), gw, dim3(256), 0, s, geom, box,
+                           tb, ntiles, map, tiles, tstride, weights, wstride, coeffs, L, npx,
+                           npatch, lnorm, lstride, batch, tmask, nmw);
 }
 
 void launch_layout_audit(hipStream_t s, const TileGeom* geom, const TileBox* box, int ntiles,

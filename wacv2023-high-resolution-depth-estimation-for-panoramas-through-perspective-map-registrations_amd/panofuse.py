@@ -40,6 +40,7 @@ EXPORTS = [
     "pf_tile_valid_counts", "pf_set_register_loss", "pf_register_ex",
     "pf_set_tile_depth", "pf_tile_ray_tables", "pf_tile_ray_factor",
     "pf_overlap_pairs", "pf_overlap_table", "pf_overlap_stats", "pf_register_consistent",
+    "pf_tile_tent_weights", "pf_register_weighted", "pf_fuse_weighted", "pf_merge_weighted",
 ]
 NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
           "pf_debug_smooth_fault", "pf_fuse_partial_rows", "pf_fuse_coverage_rows",
@@ -145,6 +146,10 @@ def load():
     L.pf_overlap_stats.argtypes = [vp, vp, vp, ip, fp, fp, vp]
     L.pf_register_consistent.argtypes = [vp, vp, ip, ip, ip, vp, ip, fp, fp, C.c_double, ip, vp,
                                          vp, vp]
+    L.pf_tile_tent_weights.argtypes = [vp, vp]
+    L.pf_register_weighted.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, ip, fp, fp, ip, vp, vp, vp]
+    L.pf_fuse_weighted.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, vp, ip, ip, ip, fp, fp, vp]
+    L.pf_merge_weighted.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, ip, ip, fp, fp, vp, vp]
     L.pf_fuse_normalize.argtypes = [vp, vp, vp, ip, ip, fp, fp, ip, vp]
     L.pf_fuse_multicover.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, ip, vp,
                                      C.POINTER(C.c_int)]
@@ -446,6 +451,65 @@ class Fuser:
             raise ValueError("MergeDepthMaps output height is out_w/2")
         self._check(self.L.pf_merge(self.h, _ptr(emap), ew, eh, ec, _ptr(tiles), B, ow,
                                     float(zr[0]), float(zr[1]), _ptr(coeffs), _ptr(out)))
+
+    # ---- per-pixel tile weights (pf_*_weighted) ----
+    def tent_weights(self, out=None):
+        """pf_tile_tent_weights: one weight set, float32 [tile_elems] device tensor in the tiles'
+        element layout (made when None): the blending tent min(t, m) / m of every tile, 0 in the
+        non-zero channels.  No sync."""
+        import torch
+        if out is None:
+            out = torch.empty(self.tile_elems, dtype=torch.float32,
+                              device=f"cuda:{self.device}")
+        if out.numel() != self.tile_elems or out.dtype != torch.float32:
+            raise ValueError(f"out must hold {self.tile_elems} float32 values")
+        self._check(self.L.pf_tile_tent_weights(self.h, _ptr(out)))
+        return out
+
+    def _wbatch(self, weights, B):
+        # weights: None (the library refuses it), [tile_elems] or [wbatch, tile_elems]
+        if weights is None:
+            return 1
+        if weights.numel() % self.tile_elems or weights.shape[-1] != self.tile_elems:
+            raise ValueError(f"weights must be [tile_elems] or [B, tile_elems] with tile_elems = "
+                             f"{self.tile_elems}")
+        return weights.numel() // self.tile_elems
+
+    def register_weighted(self, emap, tiles, weights, zr, apply=True, coeffs=None, coeffs64=None,
+                          summary=None):
+        """pf_register_weighted: register's degree-3 LM fit as weighted least squares.  weights:
+        float32 [tile_elems] (one set for the batch) or [B, tile_elems] in the tiles' element
+        layout, channel 0 read; a weight that is not in (0, +inf) switches its pixel off, and
+        weights in {0, 1} are the validity rule.  summary: float64 [B, ntiles, 2] device tensor of
+        {used samples, sum of w}.  No sync."""
+        ew, eh, ec = _emap_dims(emap)
+        B = emap.shape[0]
+        self._check(self.L.pf_register_weighted(self.h, _ptr(emap), ew, eh, ec, _ptr(tiles),
+                                                _ptr(weights), self._wbatch(weights, B), B,
+                                                float(zr[0]), float(zr[1]), 1 if apply else 0,
+                                                _ptr(coeffs), _ptr(coeffs64),
+                                                self._summary_ptr(summary, B, 2)))
+
+    def fuse_weighted(self, emap, tiles, weights, out, zr, coeffs=None):
+        """pf_fuse_weighted: fuse with every tile's Laplacian weighted by the smallest weight of
+        its five taps; weights as register_weighted's."""
+        ew, eh, ec = _emap_dims(emap)
+        B, oh, ow = out.shape
+        self._check(self.L.pf_fuse_weighted(self.h, _ptr(emap), ew, eh, ec, _ptr(tiles),
+                                            _ptr(weights), self._wbatch(weights, B),
+                                            _ptr(coeffs), B, ow, oh, float(zr[0]), float(zr[1]),
+                                            _ptr(out)))
+
+    def merge_weighted(self, emap, tiles, weights, out, zr, coeffs=None):
+        """pf_merge_weighted: register_weighted (tiles untouched) + fuse_weighted."""
+        ew, eh, ec = _emap_dims(emap)
+        B, oh, ow = out.shape
+        if oh != ow // 2:
+            raise ValueError("MergeDepthMaps output height is out_w/2")
+        self._check(self.L.pf_merge_weighted(self.h, _ptr(emap), ew, eh, ec, _ptr(tiles),
+                                             _ptr(weights), self._wbatch(weights, B), B, ow,
+                                             float(zr[0]), float(zr[1]), _ptr(coeffs),
+                                             _ptr(out)))
 
     def register_disparity(self, emap, tiles, zr, apply=True, coeffs=None, coeffs64=None,
                            summary=None):
