@@ -512,7 +512,11 @@ int pf_fuse_multicover_patch(pf_ctx* ctx, int out_w, int out_h, float zr0, float
  *   into both ping-pong buffers a and b, or into the u16 out on the last level (and then, if
  *   a / b are given, their rows h0-1 and h1+1, which the passes' halo lanes read).
  * pf_fuse_band_plan: the sweep depths T[0..n) of the level's passes (returns n), a function of
- *   (level, nbands) only, so every rank derives the same plan.
+ *   (level, nbands) only, so every rank derives the same plan.  A level whose zenith band
+ *   touches rows 1 / h-2, or whose width is odd or too narrow for a strip, has no band passes
+ *   (the one-call path sweeps it launch by launch): PF_EINVAL, naming the reason.  T == NULL with
+ *   cap == 0 asks for the count alone and returns 0 for such a level, with no error -- a
+ *   sharded flow replicates it (pf_fuse_level) instead of sweeping it in bands.
  * pf_fuse_band_pass: one pass of depth T over rows [row0, row1): reads rows row0-T-1 .. row1+T
  *   of src (src_mode 0), or of the upsample of prev (1) or the emap seed (2, level 0) for the
  *   first pass; writes rows [row0, row1) of dst, or of the u16 out (when out != NULL: the last
@@ -531,7 +535,8 @@ int pf_fuse_band_pass(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, co
 /* Row-restricted pieces of the sharded fusion (round 5): a rank computes only the rows it sweeps
  * plus their halo, and the rows its own tiles contribute to its neighbours'.
  * pf_fuse_partial_rows: pf_fuse_partial's sums of tiles [t0, t1) on rows [row0, row1) of the
- *   level only (clipped to the band [h0, h1]; nothing is zeroed elsewhere).
+ *   level only (rows of the range outside the band [h0, h1] get zero sums and counts; nothing is
+ *   written outside the range).
  * pf_fuse_coverage_rows: the coverage count n of ALL tiles on rows [row0, row1) (layout-only:
  *   a rank counts its rows itself instead of receiving the other ranks' counts).
  * pf_fuse_normalize_rows: pf_fuse_normalize on rows [row0, row1) only.

@@ -9,8 +9,6 @@ too, including the pixels covered by four tiles), and likewise the tiles-only fl
 (fuse_tile_sharded, 8 ranks).  Rank 0 holds the gathered u16 result.  The collectives
 themselves are covered over gloo in tests/test_dist.py.
 """
-import threading
-
 import numpy as np
 import pytest
 
@@ -22,63 +20,10 @@ import panofuse  # noqa: E402
 import pf_dist  # noqa: E402
 import pf_layouts as PL  # noqa: E402
 import pf_synth  # noqa: E402
+from shard_sim import run_ranks  # noqa: E402
 
 ZR = PL.ZENITH_RANGE
 DEV = "cuda:0"
-
-
-class ThreadComm:
-    """In-process stand-in for pf_dist.TorchComm among `world` threads."""
-
-    def __init__(self, world):
-        self.world = world
-        self.bar = threading.Barrier(world, timeout=120)
-        self.box = {}
-
-    def rank(self, r):
-        outer = self
-
-        class RankComm:
-            def all_reduce_sum(self, t):
-                outer.box[("ar", r)] = t
-                torch.cuda.current_stream().synchronize()
-                outer.bar.wait()
-                if r == 0:
-                    acc = outer.box[("ar", 0)].clone()
-                    for k in range(1, outer.world):
-                        acc += outer.box[("ar", k)]
-                    outer.box["ar"] = acc
-                torch.cuda.current_stream().synchronize()
-                outer.bar.wait()
-                t.copy_(outer.box["ar"])
-                torch.cuda.current_stream().synchronize()
-                outer.bar.wait()
-
-            def reduce_sum(self, t, dst):
-                self.all_reduce_sum(t)
-
-            def exchange(self, sends, recvs):
-                # several messages per pair arrive in the order they were sent (as batched
-                # isend/irecv pairs match); the clones are complete before another thread's
-                # stream reads them (a rank may exchange on its side stream)
-                for peer, t in sends:
-                    outer.box.setdefault(("x", r, peer), []).append(t.clone())
-                torch.cuda.current_stream().synchronize()
-                outer.bar.wait()
-                for peer, t in recvs:
-                    t.copy_(outer.box[("x", peer, r)].pop(0))
-                outer.bar.wait()
-
-            def broadcast(self, t, src):
-                if r == src:
-                    outer.box["bc"] = t.clone()
-                torch.cuda.current_stream().synchronize()
-                outer.bar.wait()
-                if r != src:
-                    t.copy_(outer.box["bc"])
-                outer.bar.wait()
-
-        return RankComm()
 
 
 def _run(cfg, world, seed, flow="rows", rep=0, side=False):
@@ -97,39 +42,28 @@ def _run(cfg, world, seed, flow="rows", rep=0, side=False):
     fz.fuse(emap, tiles, ref, ZR, coeffs=coeffs)
     torch.cuda.synchronize()
 
-    comm = ThreadComm(world)
-    outs, errs = [None] * world, []
+    def rank_main(r, comm):
+        f = panofuse.Fuser(0)
+        f.set_tiles(lay)
+        out = torch.zeros(out_w * (out_w // 2), dtype=torch.int16, device=DEV)
+        if flow == "rows":
+            be = pf_dist.HipRowShardBackend(f, emap, tiles, coeffs[0], out_w, ZR, out)
+            if side:  # the row-sharded levels' tile sums on a second stream
+                fs = panofuse.Fuser(0, stream=torch.cuda.Stream(DEV))
+                fs.set_tiles(lay)
+                be.enable_side(fs)
+            pf_dist.fuse_row_sharded(be, be.nlevels, lay.ntiles, r, world, comm, rep_levels=rep)
+        else:  # tiles only: rank 0 sweeps
+            be = pf_dist.HipTileShardBackend(f, emap, tiles, coeffs[0], out_w, ZR,
+                                             out.view(out_w // 2, out_w))
+            nlev = panofuse.level_info(out_w, out_w // 2, ZR, 0)[5]
+            pf_dist.fuse_tile_sharded(be, nlev, lay.ntiles, r, world, comm)
+        torch.cuda.synchronize()
+        f.close()
+        return out
 
-    def rank_main(r):
-        try:
-            f = panofuse.Fuser(0)
-            f.set_tiles(lay)
-            out = torch.zeros(out_w * (out_w // 2), dtype=torch.int16, device=DEV)
-            if flow == "rows":
-                be = pf_dist.HipRowShardBackend(f, emap, tiles, coeffs[0], out_w, ZR, out)
-                if side:  # the row-sharded levels' tile sums on a second stream
-                    fs = panofuse.Fuser(0, stream=torch.cuda.Stream(DEV))
-                    fs.set_tiles(lay)
-                    be.enable_side(fs)
-                pf_dist.fuse_row_sharded(be, be.nlevels, lay.ntiles, r, world, comm.rank(r),
-                                         rep_levels=rep)
-            else:  # tiles only: rank 0 sweeps
-                be = pf_dist.HipTileShardBackend(f, emap, tiles, coeffs[0], out_w, ZR,
-                                                 out.view(out_w // 2, out_w))
-                nlev = panofuse.level_info(out_w, out_w // 2, ZR, 0)[5]
-                pf_dist.fuse_tile_sharded(be, nlev, lay.ntiles, r, world, comm.rank(r))
-            torch.cuda.synchronize()
-            outs[r] = out
-            f.close()
-        except BaseException as e:  # surfaced by the main thread
-            errs.append(e)
-            comm.bar.abort()
-
-    th = [threading.Thread(target=rank_main, args=(r,)) for r in range(world)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(300)
+    outs, errs = run_ranks(world, rank_main)
+    errs = [e for e in errs if e is not None]
     assert not errs, errs
     for r in range(1):  # the u16 result is gathered to rank 0 (both flows)
         diff = (outs[r].view(out_w // 2, out_w) != ref[0]).sum(1)

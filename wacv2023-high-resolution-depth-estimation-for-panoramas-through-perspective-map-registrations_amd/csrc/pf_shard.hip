@@ -35,8 +35,8 @@ static int level_rows(pf_ctx* c, int out_w, int out_h, float zr0, float zr1, int
     if ((rc = level_at(c, out_w, out_h, zr0, zr1, level, L))) return rc;
     if (row0 < 0 || row1 > (*L)->h || row0 > row1)
         return fail(c, PF_EINVAL, "rows [%d,%d) outside [0,%d)", row0, row1, (*L)->h);
-    row0 = std::max(row0, (*L)->h0);  // the band: rows outside it are never targets
-    row1 = std::min(row1, (*L)->h1 + 1);
+    // rows of the range outside the band [h0, h1] are written too: no targets there (zero sums and
+    // counts, the un-windowed marker), as in the whole-plane calls
     return PF_OK;
 }
 
@@ -399,14 +399,26 @@ int pf_fuse_band_plan(pf_ctx* c, int out_w, int out_h, float zr0, float zr1, int
     int rc;
     const LevelDims* L = nullptr;
     if ((rc = check_common(c, 1))) return rc;
-    if (!T || cap < 1 || nbands < 1) return fail(c, PF_EINVAL, "pf_fuse_band_plan: bad arguments");
+    const bool count_only = !T && cap == 0;  // the number of passes; 0, not an error, where none
+    if ((!count_only && (!T || cap < 1)) || nbands < 1)
+        return fail(c, PF_EINVAL, "pf_fuse_band_plan: bad arguments");
     if ((rc = level_at(c, out_w, out_h, zr0, zr1, level, &L))) return rc;
-    if (jacobi_tcap(*L) < 1)
-        return fail(c, PF_EINVAL, "level %d: the zenith band leaves no room for band passes", level);
+    if (jacobi_tcap(*L) < 1) {
+        if (count_only) return 0;
+        // jacobi_tcap: the halo rows of a pass must stay inside [1, h-2], and a strip inside a row
+        if (std::min(L->h0 - 1, L->h - 2 - L->h1) < 1)
+            return fail(c, PF_EINVAL, "level %d: the zenith band leaves no room for band passes",
+                        level);
+        return fail(c, PF_EINVAL,
+                    "level %d: no band passes at width %d (odd, or too narrow for a strip): the "
+                    "level runs on the per-sweep engine (pf_fuse_level, pf_fuse_finish_level)",
+                    level, L->w);
+    }
     const int band = L->h1 - L->h0 + 1;
     // the sweep depths depend only on (level, nbands): every rank derives the same plan
     std::vector<PassPlan> plan = plan_level(c, *L, jacobi_tcap(*L), 1, level_full(c, level),
                                             (band + nbands - 1) / nbands);
+    if (count_only) return (int)plan.size();
     if ((int)plan.size() > cap) return fail(c, PF_EINVAL, "plan of %zu passes > cap %d", plan.size(), cap);
     for (size_t i = 0; i < plan.size(); i++) T[i] = plan[i].T;
     return (int)plan.size();

@@ -795,27 +795,31 @@ class Fuser:
                                            _out_h(out_w, out_h), float(zr[0]), float(zr[1]),
                                            level, _ptr(lsum), _ptr(cnt)))
 
-    def fuse_partial_rows(self, tiles, coeffs, t0, t1, out_w, zr, level, row0, row1, lsum, cnt):
-        """pf_fuse_partial on rows [row0, row1) only (no zeroing elsewhere)."""
+    def fuse_partial_rows(self, tiles, coeffs, t0, t1, out_w, zr, level, row0, row1, lsum, cnt,
+                          out_h=None):
+        """pf_fuse_partial on rows [row0, row1) only (zeros on their rows outside the band, nothing
+        written elsewhere)."""
         self._check(self.L.pf_fuse_partial_rows(self.h, _ptr(tiles), _ptr(coeffs), t0, t1, out_w,
-                                                out_w // 2, float(zr[0]), float(zr[1]), level,
-                                                int(row0), int(row1), _ptr(lsum), _ptr(cnt)))
+                                                _out_h(out_w, out_h), float(zr[0]), float(zr[1]),
+                                                level, int(row0), int(row1), _ptr(lsum),
+                                                _ptr(cnt)))
 
-    def fuse_coverage_rows(self, out_w, zr, level, row0, row1, cnt):
+    def fuse_coverage_rows(self, out_w, zr, level, row0, row1, cnt, out_h=None):
         """Coverage count of every tile on rows [row0, row1) (layout-only)."""
-        self._check(self.L.pf_fuse_coverage_rows(self.h, out_w, out_w // 2, float(zr[0]),
-                                                 float(zr[1]), level, int(row0), int(row1),
-                                                 _ptr(cnt)))
+        self._check(self.L.pf_fuse_coverage_rows(self.h, out_w, _out_h(out_w, out_h),
+                                                 float(zr[0]), float(zr[1]), level, int(row0),
+                                                 int(row1), _ptr(cnt)))
 
-    def fuse_normalize_rows(self, lsum, cnt, out_w, zr, level, row0, row1, lnorm):
+    def fuse_normalize_rows(self, lsum, cnt, out_w, zr, level, row0, row1, lnorm, out_h=None):
         self._check(self.L.pf_fuse_normalize_rows(self.h, _ptr(lsum), _ptr(cnt), out_w,
-                                                  out_w // 2, float(zr[0]), float(zr[1]), level,
-                                                  int(row0), int(row1), _ptr(lnorm)))
+                                                  _out_h(out_w, out_h), float(zr[0]),
+                                                  float(zr[1]), level, int(row0), int(row1),
+                                                  _ptr(lnorm)))
 
-    def fuse_tile_rows(self, out_w, zr, level, t0, t1):
+    def fuse_tile_rows(self, out_w, zr, level, t0, t1, out_h=None):
         """(ymin, ymax): rows where tiles [t0, t1) have non-zero partial sums (ymin > ymax: none)."""
         lo, hi = C.c_int(), C.c_int()
-        self._check(self.L.pf_fuse_tile_rows(self.h, out_w, out_w // 2, float(zr[0]),
+        self._check(self.L.pf_fuse_tile_rows(self.h, out_w, _out_h(out_w, out_h), float(zr[0]),
                                              float(zr[1]), level, int(t0), int(t1), C.byref(lo),
                                              C.byref(hi)))
         return lo.value, hi.value
@@ -863,49 +867,62 @@ class Fuser:
                                            _out_h(out_w, out_h), float(zr[0]), float(zr[1]),
                                            level, _ptr(lnorm)))
 
-    def multicover_count(self, out_w, zr, level):
+    def multicover_count(self, out_w, zr, level, out_h=None):
         n = C.c_int(0)
-        self._check(self.L.pf_fuse_multicover(self.h, None, None, 0, 0, out_w, out_w // 2,
-                                              float(zr[0]), float(zr[1]), level, None,
-                                              C.byref(n)))
+        self._check(self.L.pf_fuse_multicover(self.h, None, None, 0, 0, out_w,
+                                              _out_h(out_w, out_h), float(zr[0]), float(zr[1]),
+                                              level, None, C.byref(n)))
         return n.value
 
-    def multicover(self, tiles, coeffs, t0, t1, out_w, zr, level, contrib):
+    def multicover(self, tiles, coeffs, t0, t1, out_w, zr, level, contrib, out_h=None):
         n = C.c_int(0)
         self._check(self.L.pf_fuse_multicover(self.h, _ptr(tiles), _ptr(coeffs), t0, t1, out_w,
-                                              out_w // 2, float(zr[0]), float(zr[1]), level,
-                                              _ptr(contrib), C.byref(n)))
+                                              _out_h(out_w, out_h), float(zr[0]), float(zr[1]),
+                                              level, _ptr(contrib), C.byref(n)))
 
-    def multicover_patch(self, out_w, zr, level, contrib, lsum):
-        self._check(self.L.pf_fuse_multicover_patch(self.h, out_w, out_w // 2, float(zr[0]),
-                                                    float(zr[1]), level, _ptr(contrib),
-                                                    _ptr(lsum)))
+    def multicover_patch(self, out_w, zr, level, contrib, lsum, out_h=None):
+        self._check(self.L.pf_fuse_multicover_patch(self.h, out_w, _out_h(out_w, out_h),
+                                                    float(zr[0]), float(zr[1]), level,
+                                                    _ptr(contrib), _ptr(lsum)))
 
     # ---- row-band sharding of a level's sweeps (pf_dist.fuse_row_sharded) ----
-    def fuse_normalize(self, lsum, cnt, out_w, zr, level, lnorm):
-        self._check(self.L.pf_fuse_normalize(self.h, _ptr(lsum), _ptr(cnt), out_w, out_w // 2,
-                                             float(zr[0]), float(zr[1]), level, _ptr(lnorm)))
+    def fuse_normalize(self, lsum, cnt, out_w, zr, level, lnorm, out_h=None):
+        self._check(self.L.pf_fuse_normalize(self.h, _ptr(lsum), _ptr(cnt), out_w,
+                                             _out_h(out_w, out_h), float(zr[0]), float(zr[1]),
+                                             level, _ptr(lnorm)))
 
-    def fuse_border(self, prev, out_w, zr, level, a=None, b=None, out=None):
-        self._check(self.L.pf_fuse_border(self.h, _ptr(prev), out_w, out_w // 2, float(zr[0]),
-                                          float(zr[1]), level, _ptr(a), _ptr(b), _ptr(out)))
+    def fuse_border(self, prev, out_w, zr, level, a=None, b=None, out=None, out_h=None):
+        self._check(self.L.pf_fuse_border(self.h, _ptr(prev), out_w, _out_h(out_w, out_h),
+                                          float(zr[0]), float(zr[1]), level, _ptr(a), _ptr(b),
+                                          _ptr(out)))
 
-    def fuse_band_plan(self, out_w, zr, level, nbands):
+    def band_pass_count(self, out_w, zr, level, nbands=1, out_h=None):
+        """How many passes fuse_band_plan gives the level; 0 where it has no band passes (a zenith
+        band at rows 1 / h-2, an odd or narrow width: the per-sweep engine of fuse_level), where
+        fuse_band_plan raises."""
+        n = self.L.pf_fuse_band_plan(self.h, out_w, _out_h(out_w, out_h), float(zr[0]),
+                                     float(zr[1]), level, nbands, None, 0)
+        if n < 0:
+            self._check(n)
+        return n
+
+    def fuse_band_plan(self, out_w, zr, level, nbands, out_h=None):
         """Sweep depths of the level's passes (identical on every rank for the same nbands)."""
         T = (C.c_int * 256)()
-        n = self.L.pf_fuse_band_plan(self.h, out_w, out_w // 2, float(zr[0]), float(zr[1]),
-                                     level, nbands, T, 256)
+        n = self.L.pf_fuse_band_plan(self.h, out_w, _out_h(out_w, out_h), float(zr[0]),
+                                     float(zr[1]), level, nbands, T, 256)
         if n < 0:
             self._check(n)
         return [T[i] for i in range(n)]
 
     def fuse_band_pass(self, lnorm, src_mode, out_w, zr, level, T, row0, row1, src=None,
-                       dst=None, prev=None, emap=None, out=None):
+                       dst=None, prev=None, emap=None, out=None, out_h=None):
         ew, eh, ec = _emap_dims(emap) if emap is not None else (0, 0, 0)
         self._check(self.L.pf_fuse_band_pass(self.h, _ptr(emap), ew, eh, ec, _ptr(prev),
                                              _ptr(lnorm), int(src_mode), _ptr(src), _ptr(dst),
-                                             _ptr(out), out_w, out_w // 2, float(zr[0]),
-                                             float(zr[1]), level, int(T), int(row0), int(row1)))
+                                             _ptr(out), out_w, _out_h(out_w, out_h),
+                                             float(zr[0]), float(zr[1]), level, int(T), int(row0),
+                                             int(row1)))
 
     def profile(self, on=True):
         """Enable/disable per-stage hipEvent timing (resets the accumulators)."""

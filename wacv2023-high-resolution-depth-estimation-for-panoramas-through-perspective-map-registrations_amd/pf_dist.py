@@ -39,12 +39,13 @@ class HipTileShardBackend:
     of the full layout (only [t0, t1) is read); coeffs: [ntiles, 4] or None; out: the int16
     [out_h, out_w] result written by the last level on rank 0."""
 
-    def __init__(self, fuser, emap, tiles, coeffs, out_w, zr, out=None):
+    def __init__(self, fuser, emap, tiles, coeffs, out_w, zr, out=None, out_h=None):
         import panofuse
         self.fz, self.emap, self.tiles, self.coeffs = fuser, emap, tiles, coeffs
         self.out_w, self.zr, self.out = out_w, zr, out
-        n = panofuse.level_info(out_w, out_w // 2, zr, 0)[5]
-        self.levels = [panofuse.level_info(out_w, out_w // 2, zr, lv) for lv in range(n)]
+        self.out_h = out_w // 2 if out_h is None else int(out_h)
+        n = panofuse.level_info(out_w, self.out_h, zr, 0)[5]
+        self.levels = [panofuse.level_info(out_w, self.out_h, zr, lv) for lv in range(n)]
 
     def _plane(self, level):
         import torch
@@ -54,31 +55,32 @@ class HipTileShardBackend:
     def partial(self, level, t0, t1):
         lsum, cnt = self._plane(level), self._plane(level)
         self.fz.fuse_partial(self.tiles, self.coeffs, t0, t1, self.out_w, self.zr, level,
-                             lsum, cnt)
+                             lsum, cnt, out_h=self.out_h)
         return lsum, cnt
 
     def multicover_count(self, level):
-        return self.fz.multicover_count(self.out_w, self.zr, level)
+        return self.fz.multicover_count(self.out_w, self.zr, level, out_h=self.out_h)
 
     def multicover(self, level, t0, t1):
         import torch
         c = torch.zeros(max(1, self.multicover_count(level)), dtype=torch.float32,
                         device=self.tiles.device)
-        self.fz.multicover(self.tiles, self.coeffs, t0, t1, self.out_w, self.zr, level, c)
+        self.fz.multicover(self.tiles, self.coeffs, t0, t1, self.out_w, self.zr, level, c,
+                           out_h=self.out_h)
         return c
 
     def multicover_patch(self, level, contrib, lsum):
-        self.fz.multicover_patch(self.out_w, self.zr, level, contrib, lsum)
+        self.fz.multicover_patch(self.out_w, self.zr, level, contrib, lsum, out_h=self.out_h)
 
     def seed(self, level, prev):
         buf = self._plane(level)
         self.fz.fuse_seed(self.emap if level == 0 else None, prev, self.out_w, self.zr, level,
-                          buf)
+                          buf, out_h=self.out_h)
         return buf
 
     def finish(self, level, lsum, cnt, buf, last):
         self.fz.fuse_finish_level(lsum, cnt, self.out_w, self.zr, level, buf,
-                                  self.out if last else None)
+                                  self.out if last else None, out_h=self.out_h)
         return buf
 
 
@@ -361,6 +363,11 @@ def fuse_row_sharded(backend, nlevels, ntiles, rank, world, comm=None, log=None,
     and sweeps the whole level itself, with no halo exchange per pass; the next level then has
     every previous row locally.  Worth it where a rank's band is thin against the halo (many
     short passes, each an exchange on the critical path): C5's 1024-wide level at 8 ranks.
+    A level without band passes (plan() == []: a width the streamed engine does not take, which
+    the one-call fusion sweeps launch by launch) is replicated whatever rep_levels says; at world
+    1 every level is, so world 1 fuses every size pf_fuse accepts.  A ValueError -- such a level
+    after a row-sharded one, or bands thinner than the halo -- comes on every rank, from the
+    agreed plans, before any exchange.
 
     backend (one rank's device):
       dims(level) -> (w, h, h0, h1)
@@ -377,7 +384,7 @@ def fuse_row_sharded(backend, nlevels, ntiles, rank, world, comm=None, log=None,
                                                a replicated level: normalise + seeded sweeps
                                                (cnt None: lsum holds normalised targets)
       targets(level) -> the level's normalised targets from every tile (world 1)
-      plan(level, nbands) -> [T, ...]          identical on every rank
+      plan(level, nbands) -> [T, ...]          identical on every rank; [] = no band passes
       border(level, prev, a, b)               rows outside [h0, h1] (u16 `out` on the last level)
       band_pass(level, lnorm, src_mode, src, dst, T, row0, row1, last, prev)
                                                src_mode 0: src, 1: upsample prev, 2: emap seed
@@ -410,10 +417,19 @@ def fuse_row_sharded(backend, nlevels, ntiles, rank, world, comm=None, log=None,
                 # count, occupancy, PF_J* overrides -- and mismatched passes would hang the
                 # exchanges)
                 plan = comm.agree(plan, 0, getattr(backend, "device", None))
+            if not rep and not plan:
+                # no band passes here (an empty plan: the per-sweep engine, which only a whole
+                # level runs): replicated too, on the word of the agreed plan, so on every rank.
+                # Such levels are the coarsest ones (widths double), and a replicated level
+                # needs the whole level before it on every rank
+                if not all(r_ for r_, _ in G):
+                    raise ValueError(f"level {level} has no band passes and cannot be replicated "
+                                     f"after the row-sharded level {level - 1}")
+                rep = True
             ext = [backend.tile_rows(level, *shard_range(ntiles, r, world)) for r in range(world)]
             group = 1
             if rep:
-                K = max(plan) + 1
+                K = max(plan) + 1 if plan else 0  # (read by no one: a replicated level)
                 bnd = [h0] + [h1 + 1] * world  # rank 0's band is the level; all sweep it
                 need = [(h0, h1 + 1)] * world
             else:
@@ -423,8 +439,8 @@ def fuse_row_sharded(backend, nlevels, ntiles, rank, world, comm=None, log=None,
                                      f"leave bands thinner than the {K}-row halo")
                 need = [(max(h0, bnd[d] - K), min(h1 + 1, bnd[d + 1] + K))
                         for d in range(world)]
-            geo[key] = (plan, K, ext, bnd, need, group)
-        G.append((rep, geo[key]))
+            geo[key] = (rep, (plan, K, ext, bnd, need, group))
+        G.append(geo[key])
     if world == 1:  # nothing travels: each level's normalised targets from every tile
         for level in range(nlevels):
             prev = backend.level(level, prev, backend.targets(level), None,
@@ -621,7 +637,8 @@ def exchange_model(dims, plans, ext, world, multicover=None, rep_levels=0):
     as the flow, from the layout alone (tests/test_dist.py checks it against
     the bytes a gloo run logs).  dims[l] = (w, h, h0, h1); plans[l] = the pass depths of level l;
     ext[l][r] = (ymin, ymax) of rank r's tiles at level l; multicover[l] = that level's count of
-    (pixel, tile) pairs covered three or more times (one fp32 each, all-reduced)."""
+    (pixel, tile) pairs covered three or more times (one fp32 each, all-reduced).  A level with an
+    empty plan (no band passes) counts as replicated, as fuse_row_sharded runs it."""
     res = [dict() for _ in range(world)]
 
     def add(r, kind, n):
@@ -631,6 +648,11 @@ def exchange_model(dims, plans, ext, world, multicover=None, rep_levels=0):
         return res
     pb = None
     for lv, (w, h, h0, h1) in enumerate(dims):
+        if lv >= rep_levels and not plans[lv]:  # no band passes: replicated, as in the flow
+            if lv > rep_levels:
+                raise ValueError(f"level {lv} has no band passes and cannot be replicated after "
+                                 f"the row-sharded level {lv - 1}")
+            rep_levels = lv + 1
         if lv < rep_levels:  # replicated: every rank's tile rows to every other rank
             for r in range(world):
                 lo, hi = ext[lv][r][0], ext[lv][r][1] + 1
@@ -677,16 +699,23 @@ def exchange_model(dims, plans, ext, world, multicover=None, rep_levels=0):
 
 def auto_rep_levels(backend, nlevels, world, ratio=10, comm=None):
     """The coarse levels worth replicating at `world` ranks: the leading levels whose band per
-    rank is under `ratio` halos deep (each of their many short passes would wait for an exchange).
+    rank is under `ratio` halos deep (each of their many short passes would wait for an exchange),
+    and every level up to the last one without band passes (plan() == []).
     The pass plans behind the choice depend on per-process state (CU count, occupancy, PF_J*
     overrides), so with a `comm` every rank takes rank 0's answer: ranks with different rep_levels
     would build different level geometries and their exchanges would not pair up."""
     if world <= 1:
         return 0
     n = 0
-    for lv in range(nlevels - 1):  # the finest level stays sharded
+    for lv in range(nlevels):
+        plan = backend.plan(lv, world)
+        if not plan:  # no band passes: only a replicated level sweeps it (fuse_row_sharded)
+            n = lv + 1
+            continue
+        if lv == nlevels - 1:  # the finest level stays sharded
+            break
         w, h, h0, h1 = backend.dims(lv)
-        K = max(backend.plan(lv, world)) + 1
+        K = max(plan) + 1
         if (h1 - h0 + 1) / world < ratio * K:
             n = lv + 1
         else:
@@ -701,12 +730,13 @@ class HipRowShardBackend:
     panofuse.Fuser bound to this rank's GPU.  tiles: [1, tile_elems] of the full layout (only
     [t0, t1) is read); coeffs: [ntiles, 4] or None; out: flat int16 [out_h * out_w]."""
 
-    def __init__(self, fuser, emap, tiles, coeffs, out_w, zr, out):
+    def __init__(self, fuser, emap, tiles, coeffs, out_w, zr, out, out_h=None):
         import panofuse
         self.fz, self.emap, self.tiles, self.coeffs = fuser, emap, tiles, coeffs
         self.out_w, self.zr, self.out = out_w, zr, out
-        n = panofuse.level_info(out_w, out_w // 2, zr, 0)[5]
-        self.levels = [panofuse.level_info(out_w, out_w // 2, zr, lv) for lv in range(n)]
+        self.out_h = out_w // 2 if out_h is None else int(out_h)
+        n = panofuse.level_info(out_w, self.out_h, zr, 0)[5]
+        self.levels = [panofuse.level_info(out_w, self.out_h, zr, lv) for lv in range(n)]
         self.nlevels = n
 
     def dims(self, level):
@@ -727,18 +757,19 @@ class HipRowShardBackend:
         return torch.empty(n, dtype=torch.float32, device=self.tiles.device)
 
     def tile_rows(self, level, t0, t1):
-        return self.fz.fuse_tile_rows(self.out_w, self.zr, level, t0, t1)
+        return self.fz.fuse_tile_rows(self.out_w, self.zr, level, t0, t1, out_h=self.out_h)
 
     def partial_rows(self, level, t0, t1, row0, row1, lsum, cnt):
         self.fz.fuse_partial_rows(self.tiles, self.coeffs, t0, t1, self.out_w, self.zr, level,
-                                  row0, row1, lsum, cnt)
+                                  row0, row1, lsum, cnt, out_h=self.out_h)
 
     def coverage_plane(self, level):
         cov = self.__dict__.setdefault("_cov", {})
         if level not in cov:
             w, h, h0, h1 = self.levels[level][:4]
             cov[level] = self.plane(level)
-            self.fz.fuse_coverage_rows(self.out_w, self.zr, level, h0, h1 + 1, cov[level])
+            self.fz.fuse_coverage_rows(self.out_w, self.zr, level, h0, h1 + 1, cov[level],
+                                       out_h=self.out_h)
         return cov[level]
 
     def rows_add(self, dst, src):
@@ -785,11 +816,13 @@ class HipRowShardBackend:
     multicover_patch = HipTileShardBackend.multicover_patch
 
     def normalize_rows(self, level, lsum, cnt, row0, row1, lnorm):
-        self.fz.fuse_normalize_rows(lsum, cnt, self.out_w, self.zr, level, row0, row1, lnorm)
+        self.fz.fuse_normalize_rows(lsum, cnt, self.out_w, self.zr, level, row0, row1, lnorm,
+                                    out_h=self.out_h)
 
     def targets(self, level):
         lnorm = self.plane(level)
-        self.fz.fuse_targets(self.tiles, self.coeffs, self.out_w, self.zr, level, lnorm)
+        self.fz.fuse_targets(self.tiles, self.coeffs, self.out_w, self.zr, level, lnorm,
+                             out_h=self.out_h)
         return lnorm
 
     def level(self, level, prev, lsum, cnt, last):
@@ -798,17 +831,23 @@ class HipRowShardBackend:
         buf = self.plane(level)
         self.fz.fuse_level(self.emap if level == 0 else None, prev, lsum, cnt, self.out_w,
                            self.zr, level, buf,
-                           self.out.view(self.levels[level][1], -1) if last else None)
+                           self.out.view(self.levels[level][1], -1) if last else None,
+                           out_h=self.out_h)
         return None if last else buf
 
     def plan(self, level, nbands):
-        return self.fz.fuse_band_plan(self.out_w, self.zr, level, nbands)
+        """The level's pass depths; [] where it has no band passes (the per-sweep engine of
+        pf_fuse_level: fuse_row_sharded replicates such a level)."""
+        if not self.fz.band_pass_count(self.out_w, self.zr, level, nbands, out_h=self.out_h):
+            return []
+        return self.fz.fuse_band_plan(self.out_w, self.zr, level, nbands, out_h=self.out_h)
 
     def border(self, level, prev, a, b):
         if level == self.nlevels - 1:
-            self.fz.fuse_border(prev, self.out_w, self.zr, level, a=a, b=b, out=self.out)
+            self.fz.fuse_border(prev, self.out_w, self.zr, level, a=a, b=b, out=self.out,
+                                out_h=self.out_h)
         else:
-            self.fz.fuse_border(prev, self.out_w, self.zr, level, a=a, b=b)
+            self.fz.fuse_border(prev, self.out_w, self.zr, level, a=a, b=b, out_h=self.out_h)
 
     def band_pass(self, level, lnorm, src_mode, src, dst, T, row0, row1, last, prev):
         self.fz.fuse_band_pass(lnorm, src_mode, self.out_w, self.zr, level, T, row0, row1,
@@ -816,4 +855,4 @@ class HipRowShardBackend:
                                dst=None if last else dst,
                                prev=prev if src_mode == 1 else None,
                                emap=self.emap if src_mode == 2 else None,
-                               out=self.out if last else None)
+                               out=self.out if last else None, out_h=self.out_h)
