@@ -349,10 +349,10 @@ int pf_register_consistent(pf_ctx* ctx, const float* emap, int ew, int eh, int e
  *   pf_merge_weighted  pf_register_weighted (no apply) + pf_fuse_weighted with its coefficients.
  *
  * All four return PF_ESTATE while the validity rule (pf_set_tile_validity), a loss
- * (pf_set_register_loss) or PF_TILE_DEPTH_PLANAR (pf_set_tile_depth) is on.  Disparity tiles,
- * smoothing, stitch, the joint, consistent and global registrations and the sharded fusion have no
- * weighted form.  Layouts of more than 2^30 tile elements per panorama are PF_EINVAL in the two
- * fusing calls.  No existing entry point changes. */
+ * (pf_set_register_loss) or PF_TILE_DEPTH_PLANAR (pf_set_tile_depth) is on.  Disparity tiles have
+ * their own weighted forms (below).  Smoothing, stitch, the joint, consistent and global
+ * registrations and the sharded fusion have no weighted form.  Layouts of more than 2^30 tile
+ * elements per panorama are PF_EINVAL in the two fusing calls.  No existing entry point changes. */
 int pf_tile_tent_weights(pf_ctx* ctx, float* weights);
 int pf_register_weighted(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, float* tiles,
                          const float* weights, int wbatch, int batch, float zr0, float zr1,
@@ -363,6 +363,49 @@ int pf_fuse_weighted(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, con
 int pf_merge_weighted(pf_ctx* ctx, const float* emap, int ew, int eh, int ec, const float* tiles,
                       const float* weights, int wbatch, int batch, int out_w, float zr0,
                       float zr1, float* coeffs, uint16_t* out);
+
+/* ---- per-pixel weights for disparity tiles ------------------------------------------------------
+ *
+ * The weighted forms of pf_register_disparity / pf_merge_disparity: weights, wbatch and u(w) as
+ * above.  A network writes sky as disparity ~ 0, which the fit clamps to 1e-4 and which then bends
+ * y = 1/(a x + b) + d for the whole tile; weights say "this pixel does not count".
+ *
+ *   pf_tile_range_weights  the validity rule written as a weight set per panorama: weights
+ *     (DEVICE output, [batch][tile_elems] floats) gets 1.0f at the channel-0 element of a pixel
+ *     whose raw value has lo < v && v < hi in fp32 (NaN fails), 0.0f everywhere else, the other
+ *     channels included.  Stream-ordered; refuses nothing but bad arguments.
+ *   pf_register_disparity_weighted  pf_register_disparity's fit (same samples, clamps, start
+ *     (1, 1, 1) and LM) as weighted least squares.  A sample is used iff u(w) > 0 at its tile
+ *     element, its raw tile value is finite and its baseline value is finite; a used sample adds
+ *     W = (double)u(w) times each of the ten terms of a Jacobian evaluation (W * (0.5 * (r * r)) in
+ *     a trial), multiply and add apart in fp64; any other sample adds nothing.  Lane l of 256 owns
+ *     samples l, l + 256, ... used or not, then pf_register_disparity's halving tree, so with every
+ *     weight 1.0f and finite data coeffs, coeffs64 and the first four summary entries are
+ *     pf_register_disparity's bit for bit.  Fewer than 3 used samples (no fit is run: both costs
+ *     are NaN, 0 iterations), or a solution that is not finite: four quiet NaNs in coeffs and
+ *     coeffs64 and termination 5.
+ *       summary  (optional) [batch][ntiles][6] doubles {initial cost, final cost, iterations,
+ *                termination, used samples, sum of W (fp64, the same lane order and tree)}
+ *     apply != 0 then runs D2DTransform on every pixel of the tiles, as pf_register_disparity's.
+ *   pf_merge_disparity_weighted  copies the tiles into a context-owned buffer, runs the call above
+ *     with apply on the copy and fuses the copy as pf_fuse_weighted does with coeffs == NULL and
+ *     the same weights.  The caller's tiles stay untouched; a tile left with NaN coefficients
+ *     transforms to NaN and drops out of every pixel.
+ *
+ * Under PF_TILE_DEPTH_PLANAR (pf_set_tile_depth) the terms are the planar fit's, K (q + d) with the
+ * sample's ray factor K, times W, and apply composes D2DTransform with the ray factor.  The
+ * validity rule (pf_set_tile_validity) or a loss (pf_set_register_loss) is PF_ESTATE in the two
+ * fitting calls, checked before anything else; NULL weights, a wbatch that is neither 1 nor batch
+ * and, for the merge, more than 2^30 tile elements are PF_EINVAL. */
+int pf_tile_range_weights(pf_ctx* ctx, const float* tiles, int batch, float lo, float hi,
+                          float* weights);
+int pf_register_disparity_weighted(pf_ctx* ctx, const float* emap, int ew, int eh, int ec,
+                                   float* tiles, const float* weights, int wbatch, int batch,
+                                   float zr0, float zr1, int apply, float* coeffs,
+                                   double* coeffs64, double* summary);
+int pf_merge_disparity_weighted(pf_ctx* ctx, const float* emap, int ew, int eh, int ec,
+                                const float* tiles, const float* weights, int wbatch, int batch,
+                                int out_w, float zr0, float zr1, float* coeffs, uint16_t* out);
 
 /* ---- post-fusion calibration (no tile layout needed; all pointers are device pointers) ----
  *

@@ -378,6 +378,20 @@ bool SetTileDepth(int kind);
  * a message) for another mode, or for mode 2 with an empty suffix or one that holds a path
  * separator. */
 bool SetTileWeights(int mode, const std::string& suffix = "");
+/* EXTENSION: per-pixel weights for the disparity tiles of every later MergeDisparityMaps of this
+ * facade, process-wide (pf_register_disparity_weighted / pf_merge_disparity_weighted,
+ * include/panofuse.h).  mode 0 off (the default), 1 the blending tent, 2 files: arg is the SUFFIX of
+ * SetTileWeights' weight files, 3 range: arg is "LO:HI" and a pixel counts iff LO < v < HI
+ * (pf_tile_range_weights on the uploaded tiles; "0:inf" drops the disparity-0 sky a network
+ * writes).  MergeDisparityMaps then fits every tile by weighted least squares, fuses the weighted
+ * Laplacian targets of the transformed tiles and prints SetTileWeights' "[weights] tile <i>: ..."
+ * lines.  It also reads PF_DISPARITY_WEIGHTS=tent|files:SUFFIX|range:LO:HI (panofuse_main
+ * --disparity-weights), which holds for that call.  Accepted with SetTileDepth(1).  With the switch
+ * on, MergeDisparityMaps returns false, before any file is read, together with SetTileValidity,
+ * SetRegistrationLoss, PF_REG_CONSISTENT, PF_GLOBAL_ALIGN, PF_CHECK_LAPLACIAN,
+ * PF_FUSION=smoothing|stitch or SetTileWeights, and MergeDepthMaps (depth tiles) does so always.
+ * false (and a message) for another mode or a malformed arg. */
+bool SetDisparityWeights(int mode, const std::string& arg = "");
 /* EXTENSION (in the reference an `if (false)` block of MergeDepthMaps, Depth.cpp:817-865): the
  * direct stitch of the tiles as they are into data (width * height u16) -- every pixel takes the
  * first map whose range box contains it, no fusion -- on the GPU (pf_stitch), bit-exact. */

@@ -125,6 +125,9 @@ struct pf_ctx {
     // pf_merge_disparity, pf_merge under PF_TILE_DEPTH_PLANAR: the transformed copy of the
     // caller's tiles
     pf::DevBuf disp_tiles;
+    // pf_register_disparity_weighted: the samples' usable weights, [batch][samples] floats in
+    // sample order (k_disp_sample_weights), rewritten by every call
+    pf::DevBuf disp_ws;
     // pf_register_global: ValueAtCoord's column / row terms for one (result size, baseline size)
     // key, the chunk partials with the coefficients after them; pf_median_scale: bins and states
     pf::DevBuf glob_ecol, glob_erow, glob_ws, med_ws;

@@ -45,6 +45,14 @@ pfw::Spec tile_weights()
     return g_tile_weights;
 }
 
+static pfdw::Spec g_disp_weights;
+
+pfdw::Spec disparity_weights()
+{
+    std::lock_guard<std::mutex> lk(g_rule_mu);
+    return g_disp_weights;
+}
+
 static pf_ctx* device_ctx();
 
 pf_ctx* facade_ctx()
@@ -262,6 +270,19 @@ bool SetTileWeights(int mode, const std::string& suffix)
     }
     std::lock_guard<std::mutex> lk(pff::g_rule_mu);
     pff::g_tile_weights = spec;
+    return true;
+}
+
+bool SetDisparityWeights(int mode, const std::string& arg)
+{  // EXTENSION: MergeDisparityMaps fits and fuses with per-pixel weights
+    pfdw::Spec spec;
+    std::string err;
+    if (!pfdw::make_spec(mode, arg, spec, err)) {
+        std::cout << "[SetDisparityWeights] " << err << std::endl;
+        return false;
+    }
+    std::lock_guard<std::mutex> lk(pff::g_rule_mu);
+    pff::g_disp_weights = spec;
     return true;
 }
 

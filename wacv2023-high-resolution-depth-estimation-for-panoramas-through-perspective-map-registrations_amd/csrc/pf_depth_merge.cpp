@@ -5,6 +5,7 @@
 // a ground truth, ErrorEmap/ErrorData plus the .res.png/.giv.png masks.  Here the loads and the
 // file writes stay on the host (they are file formats), every per-pixel computation of the path
 // (registration, transform, fusion, quantisation, metrics) is a libpanofuse HIP kernel.
+#include "pf_disp_weights.hpp"
 #include "pf_facade.hpp"
 #include "pf_image.hpp"
 #include "pf_ray.hpp"
@@ -46,6 +47,9 @@ struct MergeSwitches {
     // PF_TILE_WEIGHTS=tent|files:SUFFIX (panofuse_main --tile-weights): the per-pixel tile weights
     // of this call; without it SetTileWeights'
     pfw::Spec weights;
+    // PF_DISPARITY_WEIGHTS=tent|files:SUFFIX|range:LO:HI (panofuse_main --disparity-weights): the
+    // per-pixel weights of this call's disparity tiles; without it SetDisparityWeights'
+    pfdw::Spec disp_weights;
 };
 
 // A finite LAMBDA >= 0, the whole string.
@@ -109,6 +113,14 @@ bool read_merge_switches(MergeSwitches& s)
         std::string err;
         if (!pfw::parse_spec(tw, s.weights, err)) {
             std::cout << "[MergeDepthMaps] PF_TILE_WEIGHTS: " << err << std::endl;
+            return false;
+        }
+    }
+    s.disp_weights = disparity_weights();
+    if (const char* dw = std::getenv("PF_DISPARITY_WEIGHTS")) {
+        std::string err;
+        if (!pfdw::parse_spec(dw, s.disp_weights, err)) {
+            std::cout << "[MergeDepthMaps] PF_DISPARITY_WEIGHTS: " << err << std::endl;
             return false;
         }
     }
@@ -371,6 +383,57 @@ bool register_weighted(const Job& j, float* d_coeffs, const float* d_weights, in
     return true;
 }
 
+// What stands beside PF_DISPARITY_WEIGHTS / SetDisparityWeights in this call (pfdw::clash names
+// the first it has no form for).
+pfdw::Others disp_weights_others(const MergeSwitches& s, bool disparity_tiles)
+{
+    pfdw::Others o;
+    o.disparity_tiles = disparity_tiles;
+    o.tile_valid = s.rule.on;
+    o.reg_loss = s.loss.kind != PF_LOSS_NONE;
+    o.consistent = s.consistent >= 0.0;
+    o.global_align = s.global_align;
+    o.check_laplacian = s.check_laplacian;
+    o.tile_weights = s.weights.mode != pfw::OFF;
+    o.smoothing = s.fusion == MergeSwitches::SMOOTHING;
+    o.stitch = s.fusion == MergeSwitches::STITCH;
+    return o;
+}
+
+// The weighted disparity merge (pf_merge_disparity_weighted: the fit with apply on the library's
+// copy, then the weighted fusion of that copy), then the fit once more for its summary: one
+// "[weights] tile <i>: <n> of <N> samples used, sum w <s>" line per tile.  The merge has no
+// summary of its own, so the lines cost a second fit; with apply_after it transforms the uploaded
+// tiles as well, which is what PF_SAVE_STITCH stitches.
+bool merge_disparity_weighted(const Job& j, float* d_coeffs, const float* d_weights, int ntiles,
+                              bool apply_after)
+{
+    const EquirectangularMap& e = j.emap;
+    DevMem ds(sizeof(double) * 6 * ntiles), dn(sizeof(long long) * 2 * ntiles);
+    std::vector<double> sm((size_t)6 * ntiles);
+    std::vector<long long> total((size_t)2 * ntiles);
+    if (!ds.ok || !dn.ok ||
+        !pf_ok(j.c, pf_tile_valid_counts(j.c, j.d_tiles, j.d_emap, e.width, e.height, e.channels, 1,
+                                         j.zr[0], j.zr[1], dn.as<long long>()),
+               "pf_tile_valid_counts") ||
+        !pf_ok(j.c, pf_merge_disparity_weighted(j.c, j.d_emap, e.width, e.height, e.channels,
+                                                j.d_tiles, d_weights, 1, 1, j.w, j.zr[0], j.zr[1],
+                                                d_coeffs, j.d_out),
+               "pf_merge_disparity_weighted") ||
+        !call_sync(j.c, pf_register_disparity_weighted(j.c, j.d_emap, e.width, e.height,
+                                                       e.channels, j.d_tiles, d_weights, 1, 1,
+                                                       j.zr[0], j.zr[1], apply_after ? 1 : 0,
+                                                       nullptr, nullptr, ds.as<double>()),
+                   "pf_register_disparity_weighted") ||
+        !download(sm.data(), ds, sm.size()) || !download(total.data(), dn, total.size()))
+        return false;
+    for (int p = 0; p < ntiles; p++)
+        std::cout << pfw::weights_line(p, sm[(size_t)6 * p + 4], total[(size_t)2 * p],
+                                       sm[(size_t)6 * p + 5])
+                  << std::endl;
+    return true;
+}
+
 // The fusion (Depth.cpp:904-913), or the smoothing (:919-922) / the stitch (:851) on the
 // registered tiles.
 bool fuse(const Job& j, const MergeSwitches& s)
@@ -534,6 +597,14 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
     const auto t_begin = std::chrono::steady_clock::now();
     MergeSwitches sw;
     if (!read_merge_switches(sw)) return false;
+    // the disparity tiles' weights stand alone too: refused before any file is read
+    const bool disp_weighted = sw.disp_weights.mode != pfdw::OFF;
+    if (disp_weighted) {
+        if (const char* what = pfdw::clash(disp_weights_others(sw, disparity_tiles), false)) {
+            std::cout << "[MergeDepthMaps] " << pfdw::clash_message(what, false) << std::endl;
+            return false;
+        }
+    }
     // the weighted forms stand alone: refused before any file is read
     const bool weighted = sw.weights.mode != pfw::OFF;
     if (weighted) {
@@ -633,27 +704,49 @@ bool merge_maps(std::string& emap_fn, std::vector<std::string>& pmap_fns, std::s
     if (sw.rule.on && !print_mask_lines(j, (int)pmaps.size(), sw.rule)) return false;
     DevMem dw = weighted ? weights_on_device(c, sw.weights, pmap_fns, pmaps) : DevMem(0);
     if (!dw.ok) return false;
-    auto t = std::chrono::steady_clock::now();
-    // with weights nothing else is on (weights_conflict): the weighted pair of calls
-    if (weighted ? !register_weighted(j, dc.as<float>(), dw.as<float>(), (int)pmaps.size())
-        : sw.consistent >= 0.0
-            ? !register_consistent(j, dc.as<float>(), (int)pmaps.size(), sw.consistent)
-            : !register_tiles(j, dc.as<float>(), disparity_tiles, (int)pmaps.size(), sw.loss, planar))
-        return false;
-    // the transformed planar tiles carry NaN at their invalid pixels: what follows reads them
-    // under (-inf, +inf), not under the caller's lo / hi (a value clamped to exactly 0 is valid)
-    if (planar && sw.rule.on &&
-        !pf_ok(c, apply_rule(c, TileRule{true, -INFINITY, INFINITY}), "pf_set_tile_validity"))
-        return false;
-    if (time_Reg) *time_Reg = elapsed_ms(t);
-    t = std::chrono::steady_clock::now();
-    if (weighted ? !call_sync(c, pf_fuse_weighted(c, j.d_emap, emap.width, emap.height,
-                                                  emap.channels, j.d_tiles, dw.as<float>(), 1,
-                                                  j.d_coeffs, 1, j.w, j.h, zr[0], zr[1], j.d_out),
-                              "pf_fuse_weighted")
-                 : !fuse(j, sw))
-        return false;
-    if (time_Laplacian) *time_Laplacian = elapsed_ms(t);
+    if (disp_weighted) {  // nothing else is on (pfdw::clash): the weighted disparity merge
+        size_t total = 0;
+        for (const PerspectiveMap& p : pmaps) total += (size_t)p.width * p.height;
+        DevMem dd = sw.disp_weights.mode == pfdw::RANGE
+                        ? DevMem(sizeof(float) * total)
+                        : weights_on_device(c, pfdw::as_tile_spec(sw.disp_weights), pmap_fns, pmaps);
+        if (!dd.ok) return false;
+        if (sw.disp_weights.mode == pfdw::RANGE &&
+            !pf_ok(c, pf_tile_range_weights(c, j.d_tiles, 1, sw.disp_weights.lo,
+                                            sw.disp_weights.hi, dd.as<float>()),
+                   "pf_tile_range_weights"))
+            return false;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (!merge_disparity_weighted(j, dc.as<float>(), dd.as<float>(), (int)pmaps.size(),
+                                      sw.save_stitch))
+            return false;
+        if (time_Reg) *time_Reg = 0;  // one call fits and fuses
+        if (time_Laplacian) *time_Laplacian = elapsed_ms(t0);
+    } else {
+        auto t = std::chrono::steady_clock::now();
+        // with weights nothing else is on (weights_conflict): the weighted pair of calls
+        if (weighted ? !register_weighted(j, dc.as<float>(), dw.as<float>(), (int)pmaps.size())
+            : sw.consistent >= 0.0
+                ? !register_consistent(j, dc.as<float>(), (int)pmaps.size(), sw.consistent)
+                : !register_tiles(j, dc.as<float>(), disparity_tiles, (int)pmaps.size(), sw.loss,
+                                  planar))
+            return false;
+        // the transformed planar tiles carry NaN at their invalid pixels: what follows reads them
+        // under (-inf, +inf), not under the caller's lo / hi (a value clamped to exactly 0 is valid)
+        if (planar && sw.rule.on &&
+            !pf_ok(c, apply_rule(c, TileRule{true, -INFINITY, INFINITY}), "pf_set_tile_validity"))
+            return false;
+        if (time_Reg) *time_Reg = elapsed_ms(t);
+        t = std::chrono::steady_clock::now();
+        if (weighted ? !call_sync(c, pf_fuse_weighted(c, j.d_emap, emap.width, emap.height,
+                                                      emap.channels, j.d_tiles, dw.as<float>(), 1,
+                                                      j.d_coeffs, 1, j.w, j.h, zr[0], zr[1],
+                                                      j.d_out),
+                                  "pf_fuse_weighted")
+                     : !fuse(j, sw))
+            return false;
+        if (time_Laplacian) *time_Laplacian = elapsed_ms(t);
+    }
     if (sw.check_laplacian && !print_laplacian_check(j)) return false;
     if (sw.save_stitch && !save_stitch(j, out_fn)) return false;
     Vec4f g;

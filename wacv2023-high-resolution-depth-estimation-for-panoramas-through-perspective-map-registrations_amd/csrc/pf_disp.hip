@@ -101,6 +101,53 @@ __device__ __forceinline__ void disp_cost_term(double X, double Y, const double 
     }
     acc = acc + 0.5 * (r * r);
 }
+
+// The weighted form (pf_register_disparity_weighted): W times each of disp_terms' ten terms in
+// their order, multiply and add apart, so W = 1.0 leaves every bit of the unweighted sums.
+template <bool PLANAR>
+__device__ __forceinline__ void disp_terms_weighted(double X, double Y, double W,
+                                                    const double p[3], double acc[kDispSums],
+                                                    double K)
+{
+    const double q = 1.0 / (p[0] * X + p[1]);
+    const double qq = q * q;
+    if constexpr (PLANAR) {
+        const double r = K * (q + p[2]) - Y;
+        const double k0 = K * -(X * qq), k1 = K * -qq, k2 = K;
+        acc[0] = acc[0] + W * (0.5 * (r * r));
+        acc[1] = acc[1] + W * (k0 * r);
+        acc[2] = acc[2] + W * (k1 * r);
+        acc[3] = acc[3] + W * (k2 * r);
+        acc[4] = acc[4] + W * (k0 * k0);
+        acc[5] = acc[5] + W * (k0 * k1);
+        acc[6] = acc[6] + W * (k0 * k2);
+        acc[7] = acc[7] + W * (k1 * k1);
+        acc[8] = acc[8] + W * (k1 * k2);
+        acc[9] = acc[9] + W * (k2 * k2);
+        return;
+    }
+    const double r = (q + p[2]) - Y;
+    const double j0 = -(X * qq), j1 = -qq;
+    acc[0] = acc[0] + W * (0.5 * (r * r));
+    acc[1] = acc[1] + W * (j0 * r);
+    acc[2] = acc[2] + W * (j1 * r);
+    acc[3] = acc[3] + W * r;
+    acc[4] = acc[4] + W * (j0 * j0);
+    acc[5] = acc[5] + W * (j0 * j1);
+    acc[6] = acc[6] + W * j0;
+    acc[7] = acc[7] + W * (j1 * j1);
+    acc[8] = acc[8] + W * j1;
+    acc[9] = acc[9] + W * 1.0;
+}
+
+template <bool PLANAR>
+__device__ __forceinline__ void disp_cost_term_weighted(double X, double Y, double W,
+                                                        const double p[3], double& acc, double K)
+{
+    const double q = 1.0 / (p[0] * X + p[1]);
+    const double r = PLANAR ? K * (q + p[2]) - Y : (q + p[2]) - Y;
+    acc = acc + W * (0.5 * (r * r));
+}
 }  // namespace
 
 // One block's fit of tile p of panorama b.  LOSS: under the robust loss L, with the 6-entry
@@ -109,14 +156,23 @@ __device__ __forceinline__ void disp_cost_term(double X, double Y, const double 
 // cached table in every pass (coalesced: lane l reads kfs[l + 256 u]), widened to fp64 -- a third
 // resident value per sample does not fit the register file, and the load replaces nothing that
 // was in registers.  The lane-to-sample order is unchanged.
-template <bool LOSS, bool PLANAR = false>
+// WEIGHTED (pf_register_disparity_weighted; never with LOSS): ws is panorama b's row (wsstride
+// floats each) of the usable sample weights (k_disp_sample_weights: u(w) of a used sample, 0.0f
+// of any other), read like kfs in every pass: lane l reads ws[l + 256 u] and branches over a
+// sample whose W is not > 0, so such a sample's terms (NaN, perhaps) are never formed.  The count
+// of used samples and the sum of W are reduced first; fewer than 3 used samples, or a solution
+// that is not finite, store quiet NaNs and termination 5.  Both decisions read block-reduced
+// values: every exit is block-uniform.
+template <bool LOSS, bool PLANAR = false, bool WEIGHTED = false>
 __device__ __forceinline__ void register_disp_tile(
     const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
     const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
     long long tstride, const int2* __restrict__ sidx, float* __restrict__ coeffs,
     double* __restrict__ coeffs64, double* __restrict__ summary, const RegLoss L,
-    double (*part)[kDispLanes], double* tot, const float* __restrict__ kfs = nullptr)
+    double (*part)[kDispLanes], double* tot, const float* __restrict__ kfs = nullptr,
+    const float* __restrict__ wsb = nullptr, long long wsstride = 0)
 {
+    static_assert(!(LOSS && WEIGHTED), "the weighted fit has no robust form");
     // k_register's block order: the tiles of one panorama on one XCD
     const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
     const int p = (int)(lb % (unsigned)ntiles), b = (int)(lb / (unsigned)ntiles), l = threadIdx.x;
@@ -127,6 +183,7 @@ __device__ __forceinline__ void register_disp_tile(
     const int ns = (rg.cols + 1) * (rg.rows + 1);
     const float* kf = PLANAR ? kfs + rg.soff : nullptr;
     auto Kof = [&](int s) { return PLANAR ? (double)kf[s] : 1.0; };
+    const float* ws = WEIGHTED ? wsb + b * wsstride + rg.soff : nullptr;
 
     // the lane's resident samples l, l + 256, ...: gathered once (independent loads)
     float xs[kDispPerLane], ys[kDispPerLane];
@@ -148,10 +205,29 @@ __device__ __forceinline__ void register_disp_tile(
         for (int k = 0; k < kDispSums; k++) S[k] = 0.0;
 #pragma unroll
         for (int u = 0; u < kDispPerLane; u++)
-            if (l + u * kDispLanes < ns)
-                disp_terms<LOSS, PLANAR>(clamp_sample((double)xs[u]), clamp_sample((double)ys[u]),
-                                         q, S, L, Kof(l + u * kDispLanes));
+            if (l + u * kDispLanes < ns) {
+                if constexpr (WEIGHTED) {
+                    const double W = (double)ws[l + u * kDispLanes];
+                    if (W > 0.0)
+                        disp_terms_weighted<PLANAR>(clamp_sample((double)xs[u]),
+                                                    clamp_sample((double)ys[u]), W, q, S,
+                                                    Kof(l + u * kDispLanes));
+                } else {
+                    disp_terms<LOSS, PLANAR>(clamp_sample((double)xs[u]),
+                                             clamp_sample((double)ys[u]), q, S, L,
+                                             Kof(l + u * kDispLanes));
+                }
+            }
         for (int s = l + kDispResident; s < ns; s += kDispLanes) {  // past the capacity
+            if constexpr (WEIGHTED) {
+                const double W = (double)ws[s];
+                if (W > 0.0) {
+                    const int2 i2 = ix[s];
+                    disp_terms_weighted<PLANAR>(clamp_sample((double)tile[i2.x]),
+                                                clamp_sample((double)em[i2.y]), W, q, S, Kof(s));
+                }
+                continue;
+            }
             const int2 i2 = ix[s];
             disp_terms<LOSS, PLANAR>(clamp_sample((double)tile[i2.x]),
                                      clamp_sample((double)em[i2.y]), q, S, L, Kof(s));
@@ -170,11 +246,30 @@ __device__ __forceinline__ void register_disp_tile(
         double c = 0.0;
 #pragma unroll
         for (int u = 0; u < kDispPerLane; u++)
-            if (l + u * kDispLanes < ns)
-                disp_cost_term<LOSS, PLANAR>(clamp_sample((double)xs[u]),
-                                             clamp_sample((double)ys[u]), q, c, L,
-                                             Kof(l + u * kDispLanes));
+            if (l + u * kDispLanes < ns) {
+                if constexpr (WEIGHTED) {
+                    const double W = (double)ws[l + u * kDispLanes];
+                    if (W > 0.0)
+                        disp_cost_term_weighted<PLANAR>(clamp_sample((double)xs[u]),
+                                                        clamp_sample((double)ys[u]), W, q, c,
+                                                        Kof(l + u * kDispLanes));
+                } else {
+                    disp_cost_term<LOSS, PLANAR>(clamp_sample((double)xs[u]),
+                                                 clamp_sample((double)ys[u]), q, c, L,
+                                                 Kof(l + u * kDispLanes));
+                }
+            }
         for (int s = l + kDispResident; s < ns; s += kDispLanes) {
+            if constexpr (WEIGHTED) {
+                const double W = (double)ws[s];
+                if (W > 0.0) {
+                    const int2 i2 = ix[s];
+                    disp_cost_term_weighted<PLANAR>(clamp_sample((double)tile[i2.x]),
+                                                    clamp_sample((double)em[i2.y]), W, q, c,
+                                                    Kof(s));
+                }
+                continue;
+            }
             const int2 i2 = ix[s];
             disp_cost_term<LOSS, PLANAR>(clamp_sample((double)tile[i2.x]),
                                          clamp_sample((double)em[i2.y]), q, c, L, Kof(s));
@@ -188,6 +283,36 @@ __device__ __forceinline__ void register_disp_tile(
     const double start[3] = {1.0, 1.0, 1.0};  // Depth.cpp:1270-1274
     double best[3];
     LmSummary sm;
+    double used[2] = {0.0, 0.0};  // WEIGHTED: the used samples and the sum of W
+    if constexpr (WEIGHTED) {
+        for (int s = l; s < ns; s += kDispLanes) {
+            const double W = (double)ws[s];
+            if (W > 0.0) {
+                used[0] = used[0] + 1.0;
+                used[1] = used[1] + W;
+            }
+        }
+        disp_reduce<2>(used, part, tot, l);
+        if (used[0] < 3.0) {  // block-uniform: no fit
+            if (l == 0) {
+                const double qnan = __longlong_as_double(0x7FF8000000000000LL);
+                const long long o = (long long)b * ntiles + p;
+                for (int i = 0; i < 4; i++) {
+                    if (coeffs) coeffs[o * 4 + i] = __uint_as_float(0x7FC00000u);
+                    if (coeffs64) coeffs64[o * 4 + i] = qnan;
+                }
+                if (summary) {
+                    summary[o * 6 + 0] = qnan;
+                    summary[o * 6 + 1] = qnan;
+                    summary[o * 6 + 2] = 0.0;
+                    summary[o * 6 + 3] = (double)kTermFailure;
+                    summary[o * 6 + 4] = used[0];
+                    summary[o * 6 + 5] = used[1];
+                }
+            }
+            return;
+        }
+    }
     lm_solve<3, true>(start, eval_full, eval_cost, best, sm);
     double inliers = 0.0;
     if constexpr (LOSS) {
@@ -211,14 +336,19 @@ __device__ __forceinline__ void register_disp_tile(
     }
     if (l == 0) {
         // abcd = (a, b, 1, d): the order D2DTransform reads (Depth.cpp:216-219, 233)
-        const double full[4] = {best[0], best[1], 1.0, best[2]};
+        double full[4] = {best[0], best[1], 1.0, best[2]};
+        if constexpr (WEIGHTED)
+            if (!(isfinite(best[0]) && isfinite(best[1]) && isfinite(best[2]))) {
+                for (int i = 0; i < 4; i++) full[i] = __longlong_as_double(0x7FF8000000000000LL);
+                sm.termination = kTermFailure;
+            }
         const long long o = (long long)b * ntiles + p;
         for (int i = 0; i < 4; i++) {
             if (coeffs) coeffs[o * 4 + i] = (float)full[i];
             if (coeffs64) coeffs64[o * 4 + i] = full[i];
         }
         if (summary) {
-            constexpr int kN = LOSS ? 6 : 4;
+            constexpr int kN = LOSS || WEIGHTED ? 6 : 4;
             summary[o * kN + 0] = sm.initial_cost;
             summary[o * kN + 1] = sm.final_cost;
             summary[o * kN + 2] = (double)sm.iterations;
@@ -226,6 +356,10 @@ __device__ __forceinline__ void register_disp_tile(
             if constexpr (LOSS) {
                 summary[o * kN + 4] = (double)ns;
                 summary[o * kN + 5] = inliers;
+            }
+            if constexpr (WEIGHTED) {
+                summary[o * kN + 4] = used[0];
+                summary[o * kN + 5] = used[1];
             }
         }
     }
@@ -279,6 +413,76 @@ __global__ void __launch_bounds__(kDispLanes) k_register_disp_planar_loss(
     __shared__ double tot[kDispSums];
     register_disp_tile<true, true>(geom, grids, ntiles, emap, estride, tiles, tstride, sidx,
                                    coeffs, coeffs64, summary, loss, part, tot, kfs);
+}
+
+__global__ void __launch_bounds__(kDispLanes) k_register_disp_weighted(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, const int2* __restrict__ sidx, const float* __restrict__ ws,
+    long long wsstride, float* __restrict__ coeffs, double* __restrict__ coeffs64,
+    double* __restrict__ summary)
+{
+    __shared__ double part[kDispSums][kDispLanes];
+    __shared__ double tot[kDispSums];
+    register_disp_tile<false, false, true>(geom, grids, ntiles, emap, estride, tiles, tstride,
+                                           sidx, coeffs, coeffs64, summary,
+                                           RegLoss{PF_LOSS_NONE, 0.0, 0.0, 0.0}, part, tot,
+                                           nullptr, ws, wsstride);
+}
+
+__global__ void __launch_bounds__(kDispLanes) k_register_disp_planar_weighted(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids, int ntiles,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, const int2* __restrict__ sidx, const float* __restrict__ kfs,
+    const float* __restrict__ ws, long long wsstride, float* __restrict__ coeffs,
+    double* __restrict__ coeffs64, double* __restrict__ summary)
+{
+    __shared__ double part[kDispSums][kDispLanes];
+    __shared__ double tot[kDispSums];
+    register_disp_tile<false, true, true>(geom, grids, ntiles, emap, estride, tiles, tstride, sidx,
+                                          coeffs, coeffs64, summary,
+                                          RegLoss{PF_LOSS_NONE, 0.0, 0.0, 0.0}, part, tot, kfs,
+                                          ws, wsstride);
+}
+
+// The usable weight of every registration sample, in sample order: ws[b][soff + s] = u(w) of the
+// element sample s reads when the raw tile value and the baseline value are finite, else 0.0f
+// (u(w) = w for 0 < w < +inf in fp32, else 0).  Per panorama even with one weight set (wstride 0):
+// the finiteness tests read the panorama's data.
+__global__ void __launch_bounds__(256) k_disp_sample_weights(
+    const TileGeom* __restrict__ geom, const RegGrid* __restrict__ grids,
+    const float* __restrict__ emap, long long estride, const float* __restrict__ tiles,
+    long long tstride, const float* __restrict__ weights, long long wstride,
+    const int2* __restrict__ sidx, float* __restrict__ ws, long long wsstride)
+{
+    const int p = blockIdx.y, b = blockIdx.z;
+    const RegGrid rg = grids[p];
+    const long long off = geom[p].off;
+    const float* tile = tiles + b * tstride + off;
+    const float* wt = weights + b * wstride + off;
+    const float* em = emap + b * estride;
+    const int ns = (rg.cols + 1) * (rg.rows + 1);
+    for (int s = blockIdx.x * 256 + threadIdx.x; s < ns; s += gridDim.x * 256) {
+        const int2 i2 = sidx[rg.soff + s];
+        const float w = wt[i2.x];
+        const bool used = 0.0f < w && w < __uint_as_float(0x7F800000u) && isfinite(tile[i2.x]) &&
+                          isfinite(em[i2.y]);
+        ws[b * wsstride + rg.soff + s] = used ? w : 0.0f;
+    }
+}
+
+// pf_tile_range_weights: the validity rule lo < v < hi (fp32; NaN fails) written as a weight set
+// per panorama: 1.0f / 0.0f at channel 0, 0.0f in the other channels.
+__global__ void __launch_bounds__(256) k_range_weights(const float* __restrict__ tiles,
+                                                       long long npx, int c, float lo,
+                                                       float hi, float* __restrict__ weights)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < npx;
+         i += (long long)gridDim.x * 256) {
+        const float v = tiles[i * c];
+        weights[i * c] = (lo < v && v < hi) ? 1.0f : 0.0f;
+        for (int ch = 1; ch < c; ch++) weights[i * c + ch] = 0.0f;
+    }
 }
 
 // D2DTransform's per-pixel map (Depth.cpp:225-240).  The X clamps compare the float against the
@@ -377,6 +581,46 @@ void launch_register_disp_planar(hipStream_t s, const TileGeom* geom, const RegG
     else
         hipLaunchKernelGGL(k_register_disp_planar, grid, block, 0, s, geom, grids, ntiles, emap,
                            estride, tiles, tstride, sidx, kfs, coeffs, coeffs64, summary);
+}
+
+void launch_disp_sample_weights(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
+                                int ntiles, int max_samples, const float* emap, long long estride,
+                                const float* tiles, long long tstride, const float* weights,
+                                long long wstride, const int2* sidx, float* ws, long long wsstride,
+                                int batch)
+{
+    unsigned gx = (unsigned)((max_samples + 255) / 256);
+    if (gx < 1) gx = 1;
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(k_disp_sample_weights, dim3(gx, (unsigned)ntiles, (unsigned)batch),
+                       dim3(256), 0, s, geom, grids, emap, estride, tiles, tstride, weights,
+                       wstride, sidx, ws, wsstride);
+}
+
+void launch_register_disp_weighted(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
+                                   int ntiles, const float* emap, long long estride,
+                                   const float* tiles, long long tstride, const int2* sidx,
+                                   const float* kfs, const float* ws, long long wsstride,
+                                   float* coeffs, double* coeffs64, double* summary, int batch)
+{
+    const dim3 grid((unsigned)(ntiles * batch)), block(kDispLanes);
+    if (kfs)
+        hipLaunchKernelGGL(k_register_disp_planar_weighted, grid, block, 0, s, geom, grids, ntiles,
+                           emap, estride, tiles, tstride, sidx, kfs, ws, wsstride, coeffs,
+                           coeffs64, summary);
+    else
+        hipLaunchKernelGGL(k_register_disp_weighted, grid, block, 0, s, geom, grids, ntiles, emap,
+                           estride, tiles, tstride, sidx, ws, wsstride, coeffs, coeffs64, summary);
+}
+
+void launch_range_weights(hipStream_t s, const float* tiles, long long npx, int c, float lo,
+                          float hi, float* weights)
+{
+    long long gx = (npx + 255) / 256;
+    if (gx > 4096) gx = 4096;
+    if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(k_range_weights, dim3((unsigned)gx), dim3(256), 0, s, tiles, npx, c, lo,
+                       hi, weights);
 }
 
 void launch_apply_disp_planar(hipStream_t s, const TileGeom* geom, const RayTile* ray,

@@ -7,6 +7,7 @@
 
 #include "../../include/pf_depth.h"
 #include "../../include/panofuse.h"
+#include "pf_disp_weights.hpp"
 #include "pf_weights.hpp"
 
 #include <hip/hip_runtime.h>
@@ -53,6 +54,8 @@ inline int apply_loss(pf_ctx* c, const RegLossRule& r)
 int tile_depth();
 // The per-pixel tile weights of MergeDepthMaps (SetTileWeights), carried the same way.
 pfw::Spec tile_weights();
+// The disparity tiles' weights of MergeDisparityMaps (SetDisparityWeights), carried the same way.
+pfdw::Spec disparity_weights();
 // "huber:A" or "softl1:A" with a finite A > 0 (PF_REG_LOSS / --reg-loss).
 inline bool parse_reg_loss(const char* s, RegLossRule& r)
 {

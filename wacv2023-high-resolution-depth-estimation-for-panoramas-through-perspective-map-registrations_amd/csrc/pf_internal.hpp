@@ -484,6 +484,24 @@ void launch_overlap_stats(hipStream_t s, const TileGeom* geom, const int* pairs,
 void launch_apply_disp(hipStream_t s, const TileGeom* geom, int ntiles, long long tile_pixels,
                        float* tiles, long long tstride, const float* coeffs, int batch);
 void launch_disp_map(hipStream_t s, float* data, long long npx, int c, const float* abcd);
+// The weighted disparity registration (pf_register_disparity_weighted, pf_disp.hip).  First the
+// samples' usable weights in sample order, ws [batch][wsstride]: u(w) of the element a sample
+// reads when its tile and baseline values are finite, else 0.0f (weights: the tiles' element
+// layout, panorama b at weights + b * wstride).  Then launch_register_disp's fit with every used
+// sample's terms times (double)ws; kfs != nullptr: the planar form.  summary: [batch][ntiles][6].
+void launch_disp_sample_weights(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
+                                int ntiles, int max_samples, const float* emap, long long estride,
+                                const float* tiles, long long tstride, const float* weights,
+                                long long wstride, const int2* sidx, float* ws, long long wsstride,
+                                int batch);
+void launch_register_disp_weighted(hipStream_t s, const TileGeom* geom, const RegGrid* grids,
+                                   int ntiles, const float* emap, long long estride,
+                                   const float* tiles, long long tstride, const int2* sidx,
+                                   const float* kfs, const float* ws, long long wsstride,
+                                   float* coeffs, double* coeffs64, double* summary, int batch);
+// pf_tile_range_weights: 1.0f at channel 0 of a pixel with lo < v < hi, 0.0f everywhere else
+void launch_range_weights(hipStream_t s, const float* tiles, long long npx, int c, float lo,
+                          float hi, float* weights);
 // Global result-to-baseline fit (pf_global.hip, SolveDepthToDepth2): per (panorama, chunk of
 // kGlobalChunk consecutive band samples) the 15 moment sums to partials [batch][nchunks][15];
 // ecol / erow: ValueAtCoord's column term per X and row term per Y (element offsets).  Then the

@@ -91,6 +91,14 @@
 // --tile-depth planar, --reg-consistent, --tile-model disparity, --global-align, --check-laplacian
 // or --fusion smoothing|stitch (refused here).  Carried in PF_TILE_WEIGHTS; not in the usage text
 // either.
+// --disparity-weights tent|files:SUFFIX|range:LO:HI (opt-in, with --tile-model disparity): per-pixel
+// weights for disparity tiles (pf_register_disparity_weighted, pf_merge_disparity_weighted).  tent
+// and files:SUFFIX as --tile-weights'; range:LO:HI counts a pixel iff LO < v < HI (range:0:inf
+// drops the disparity-0 sky a network writes).  Prints --tile-weights' "[weights]" lines.  Works
+// with --tile-depth planar.  Not without --tile-model disparity, nor with --tile-valid, --reg-loss,
+// --reg-consistent, --global-align, --check-laplacian, --fusion smoothing|stitch or --tile-weights
+// (refused here).  Carried in PF_DISPARITY_WEIGHTS; not in the usage text either.
+#include "pf_disp_weights.hpp"
 #include "pf_facade.hpp"  // the inline to_window and load_pair; it includes the two public headers
 #include "pf_ray.hpp"
 #include "pf_valid.hpp"
@@ -355,6 +363,7 @@ static int mode0_command(int argc, char* argv[])
     int width = 2048, device = 0, shard = 0, nshards = 1;
     bool check_laplacian = false, consistent = false, global_align = false, disparity = false;
     bool weights = false, planar = false, tile_valid = false, reg_loss = false;
+    bool disp_weights = false;
     const auto on_switch = [&](const std::string& k) {
         if (k == "--check-laplacian") check_laplacian = true;
         if (k == "--global-align") global_align = true;
@@ -400,6 +409,14 @@ static int mode0_command(int argc, char* argv[])
             weights = true;
             setenv("PF_TILE_WEIGHTS", v.c_str(), 1);  // read by MergeDepthMaps
         }
+        else if (k == "--disparity-weights") {
+            pfdw::Spec spec;
+            std::string err;
+            if (!pfdw::parse_spec(v.c_str(), spec, err) || spec.mode == pfdw::OFF)
+                return bad(k, v, "tent, files:SUFFIX or range:LO:HI");
+            disp_weights = true;
+            setenv("PF_DISPARITY_WEIGHTS", v.c_str(), 1);  // read by MergeDisparityMaps
+        }
         else if (k == "--shard") {  // R/N: one process per GPU over the sorted folder
             if (std::sscanf(v.c_str(), "%d/%d", &shard, &nshards) != 2 || nshards < 1 ||
                 shard < 0 || shard >= nshards)
@@ -419,6 +436,22 @@ static int mode0_command(int argc, char* argv[])
         std::cout << "--check-laplacian needs --fusion laplacian (got " << fusion << ")"
                   << std::endl;
         return 2;
+    }
+    if (disp_weights) {  // the weighted disparity forms stand alone: refused before any GPU call
+        pfdw::Others o;
+        o.disparity_tiles = disparity;
+        o.tile_valid = tile_valid;
+        o.reg_loss = reg_loss;
+        o.consistent = consistent;
+        o.global_align = global_align;
+        o.check_laplacian = check_laplacian;
+        o.tile_weights = weights;
+        o.smoothing = fusion == "smoothing";
+        o.stitch = fusion == "stitch";
+        if (const char* what = pfdw::clash(o, true)) {
+            std::cout << pfdw::clash_message(what, true) << std::endl;
+            return 2;
+        }
     }
     if (consistent && (disparity || global_align)) {
         std::cout << "--reg-consistent registers depth tiles by a linear solve: not with "

@@ -1,6 +1,8 @@
 // pf_weight_api.hip -- the entry points of the per-pixel tile weights: pf_tile_tent_weights,
-// pf_register_weighted, pf_fuse_weighted, pf_merge_weighted (include/panofuse.h has the contract).
-// New entry points only: pf_register / pf_fuse / pf_merge launch what they always did.
+// pf_register_weighted, pf_fuse_weighted, pf_merge_weighted, and the disparity path's weighted
+// forms pf_tile_range_weights, pf_register_disparity_weighted, pf_merge_disparity_weighted
+// (include/panofuse.h has the contract).  New entry points only: pf_register / pf_fuse / pf_merge /
+// pf_register_disparity / pf_merge_disparity launch what they always did.
 #include "pf_ctx.hpp"
 
 using namespace pf;
@@ -95,9 +97,139 @@ int fuse_weighted(pf_ctx* c, const float* emap, int ew, int eh, int ec, const fl
     return rc;
 }
 
+// The disparity path's weighted forms run under plain least squares without the validity rule
+// (which weights in {0, 1} restate); planar-depth tiles are honoured.  Checked before anything else.
+int check_disp_weight_modes(pf_ctx* c, const char* entry)
+{
+    if (!c) return PF_EINVAL;
+    if (c->valid.on)
+        return fail(c, PF_ESTATE,
+                    "%s does not run under the tile validity rule: call pf_set_tile_validity(ctx, "
+                    "PF_VALID_ALL, 0, 0) first and pass the rule as weights (pf_tile_range_weights)",
+                    entry);
+    if (c->loss_kind != PF_LOSS_NONE)
+        return fail(c, PF_ESTATE,
+                    "%s has no robust form: call pf_set_register_loss(ctx, PF_LOSS_NONE, 0) first",
+                    entry);
+    return PF_OK;
+}
+
+// pf_register_disparity's fit with a weight per sample (k_register_disp_weighted): the samples'
+// usable weights go to the context's table first (k_disp_sample_weights), one row per panorama.
+int register_disparity_weighted(pf_ctx* c, const float* emap, int ew, int eh, int ec, float* tiles,
+                                const float* weights, long long wstride, int batch, float zr0,
+                                float zr1, int apply, float* coeffs, double* coeffs64,
+                                double* summary)
+{
+    int rc;
+    if ((rc = prepare_registration(c, zr0, zr1))) return rc;
+    if ((rc = check_reg_grids(c, nullptr))) return rc;
+    float* cf = coeffs;
+    if (!cf) {
+        if ((rc = ensure(c, c->coeffs, sizeof(float) * 4 * c->ntiles * batch))) return rc;
+        cf = (float*)c->coeffs.p;
+    }
+    long long nsamp = 0;
+    int maxn = 0;
+    for (const RegGrid& g : c->reg_h) {
+        const int k = (g.cols + 1) * (g.rows + 1);
+        nsamp += k;
+        maxn = k > maxn ? k : maxn;
+    }
+    const int2* sidx = reg_sample_index(c, ew, eh, ec);  // before the stage timer: built once
+    if (!sidx) return fail(c, PF_EHIP, "pf_register_disparity_weighted: no sample-index table");
+    const bool planar = c->tile_depth == PF_TILE_DEPTH_PLANAR;
+    const float* kfs = nullptr;
+    if (planar && !(kfs = reg_sample_kf(c, ew, eh, ec)))
+        return fail(c, PF_EHIP, "pf_register_disparity_weighted: no sample ray-factor table");
+    if ((rc = ensure(c, c->disp_ws, sizeof(float) * (size_t)nsamp * batch))) return rc;
+    float* ws = (float*)c->disp_ws.p;
+    const TileGeom* geom = (const TileGeom*)c->geom.p;
+    const RegGrid* grids = (const RegGrid*)c->reg.p;
+    const long long estride = (long long)ew * eh * ec;
+    StageTimer t(c, PF_STAGE_REGISTER,
+                 batch * ((planar ? 24.0 : 20.0) * (double)nsamp +
+                          (apply ? 8.0 * (double)c->tile_elems / c->tile_c : 0.0)),
+                 apply ? 3 : 2);
+    launch_disp_sample_weights(c->stream, geom, grids, c->ntiles, maxn, emap, estride, tiles,
+                               c->tile_elems, weights, wstride, sidx, ws, nsamp, batch);
+    launch_register_disp_weighted(c->stream, geom, grids, c->ntiles, emap, estride, tiles,
+                                  c->tile_elems, sidx, kfs, ws, nsamp, cf, coeffs64, summary,
+                                  batch);
+    if (apply) {
+        if (planar)
+            launch_apply_disp_planar(c->stream, geom, (const RayTile*)c->ray.p,
+                                     (const double*)c->ray_tab.p, c->ntiles,
+                                     c->tile_elems / c->tile_c, tiles, tiles, c->tile_elems, cf,
+                                     batch);
+        else
+            launch_apply_disp(c->stream, geom, c->ntiles, c->tile_elems / c->tile_c, tiles,
+                              c->tile_elems, cf, batch);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PF_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int pf_tile_range_weights(pf_ctx* c, const float* tiles, int batch, float lo, float hi,
+                          float* weights)
+{
+    int rc;
+    if ((rc = check_common(c, batch))) return rc;
+    if (!tiles || !weights)
+        return fail(c, PF_EINVAL, "pf_tile_range_weights: tiles/weights is NULL");
+    launch_range_weights(c->stream, tiles, c->tile_elems / c->tile_c * batch, c->tile_c, lo, hi,
+                         weights);
+    HIPCHK(c, hipGetLastError());
+    return PF_OK;
+}
+
+int pf_register_disparity_weighted(pf_ctx* c, const float* emap, int ew, int eh, int ec,
+                                   float* tiles, const float* weights, int wbatch, int batch,
+                                   float zr0, float zr1, int apply, float* coeffs,
+                                   double* coeffs64, double* summary)
+{
+    int rc;
+    long long wstride = 0;
+    if ((rc = check_disp_weight_modes(c, "pf_register_disparity_weighted"))) return rc;
+    if ((rc = check_common(c, batch))) return rc;
+    if ((rc = check_emap(c, emap, ew, eh, ec))) return rc;
+    if (!tiles) return fail(c, PF_EINVAL, "tiles is NULL");
+    if ((rc = check_weights(c, "pf_register_disparity_weighted", weights, wbatch, batch, &wstride)))
+        return rc;
+    return register_disparity_weighted(c, emap, ew, eh, ec, tiles, weights, wstride, batch, zr0,
+                                       zr1, apply, coeffs, coeffs64, summary);
+}
+
+int pf_merge_disparity_weighted(pf_ctx* c, const float* emap, int ew, int eh, int ec,
+                                const float* tiles, const float* weights, int wbatch, int batch,
+                                int out_w, float zr0, float zr1, float* coeffs, uint16_t* out)
+{
+    int rc;
+    long long wstride = 0;
+    if ((rc = check_disp_weight_modes(c, "pf_merge_disparity_weighted"))) return rc;
+    if ((rc = check_common(c, batch))) return rc;
+    if ((rc = check_emap(c, emap, ew, eh, ec))) return rc;
+    if (!tiles || !out) return fail(c, PF_EINVAL, "tiles/out is NULL");
+    if ((rc = check_weights(c, "pf_merge_disparity_weighted", weights, wbatch, batch, &wstride)))
+        return rc;
+    if ((rc = check_fusable(c, "pf_merge_disparity_weighted"))) return rc;
+    if ((rc = jres_check(c))) return rc;
+    const size_t bytes = sizeof(float) * (size_t)c->tile_elems * batch;
+    if ((rc = ensure(c, c->disp_tiles, bytes))) return rc;
+    float* copy = (float*)c->disp_tiles.p;
+    HIPCHK(c, hipMemcpyAsync(copy, tiles, bytes, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = register_disparity_weighted(c, emap, ew, eh, ec, copy, weights, wstride, batch, zr0,
+                                          zr1, 1, coeffs, nullptr, nullptr)))
+        return rc;
+    // the transformed copy is ray distance: fused without coefficients, a tile left with NaN
+    // coefficients is all NaN and drops out of every pixel (the staged-NaN rule of the gather)
+    return fuse_weighted(c, emap, ew, eh, ec, copy, weights, wstride, nullptr, batch, out_w,
+                         out_w / 2, zr0, zr1, out);
+}
 
 int pf_tile_tent_weights(pf_ctx* c, float* weights)
 {

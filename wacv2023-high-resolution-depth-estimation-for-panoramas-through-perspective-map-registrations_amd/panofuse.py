@@ -41,6 +41,7 @@ EXPORTS = [
     "pf_set_tile_depth", "pf_tile_ray_tables", "pf_tile_ray_factor",
     "pf_overlap_pairs", "pf_overlap_table", "pf_overlap_stats", "pf_register_consistent",
     "pf_tile_tent_weights", "pf_register_weighted", "pf_fuse_weighted", "pf_merge_weighted",
+    "pf_tile_range_weights", "pf_register_disparity_weighted", "pf_merge_disparity_weighted",
 ]
 NEW_R4 = {"pf_debug_jres_fault", "pf_probe_warp_coords", "pf_probe_rgb_taps",
           "pf_debug_smooth_fault", "pf_fuse_partial_rows", "pf_fuse_coverage_rows",
@@ -150,6 +151,11 @@ def load():
     L.pf_register_weighted.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, ip, fp, fp, ip, vp, vp, vp]
     L.pf_fuse_weighted.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, vp, ip, ip, ip, fp, fp, vp]
     L.pf_merge_weighted.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, ip, ip, fp, fp, vp, vp]
+    L.pf_tile_range_weights.argtypes = [vp, vp, ip, fp, fp, vp]
+    L.pf_register_disparity_weighted.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, ip, fp, fp, ip,
+                                                 vp, vp, vp]
+    L.pf_merge_disparity_weighted.argtypes = [vp, vp, ip, ip, ip, vp, vp, ip, ip, ip, fp, fp, vp,
+                                              vp]
     L.pf_fuse_normalize.argtypes = [vp, vp, vp, ip, ip, fp, fp, ip, vp]
     L.pf_fuse_multicover.argtypes = [vp, vp, vp, ip, ip, ip, ip, fp, fp, ip, vp,
                                      C.POINTER(C.c_int)]
@@ -510,6 +516,49 @@ class Fuser:
                                              _ptr(weights), self._wbatch(weights, B), B, ow,
                                              float(zr[0]), float(zr[1]), _ptr(coeffs),
                                              _ptr(out)))
+
+    # ---- per-pixel weights for disparity tiles ----
+    def range_weights(self, tiles, lo, hi, out=None):
+        """pf_tile_range_weights: the validity rule lo < v < hi as one weight set per panorama,
+        float32 [B, tile_elems] (made when None): 1.0 at channel 0 of a passing pixel, 0.0
+        everywhere else.  tiles: [B, tile_elems].  No sync."""
+        import torch
+        B = tiles.numel() // self.tile_elems
+        if B < 1 or tiles.numel() != B * self.tile_elems or tiles.dtype != torch.float32:
+            raise ValueError(f"tiles must hold [B, {self.tile_elems}] float32 values")
+        if out is None:
+            out = torch.empty((B, self.tile_elems), dtype=torch.float32, device=tiles.device)
+        if out.numel() != tiles.numel() or out.dtype != torch.float32:
+            raise ValueError(f"out must hold [{B}, {self.tile_elems}] float32 values")
+        self._check(self.L.pf_tile_range_weights(self.h, _ptr(tiles), B, float(lo), float(hi),
+                                                 _ptr(out)))
+        return out
+
+    def register_disparity_weighted(self, emap, tiles, weights, zr, apply=True, coeffs=None,
+                                    coeffs64=None, summary=None):
+        """pf_register_disparity_weighted: register_disparity's fit as weighted least squares;
+        weights as register_weighted's.  summary: float64 [B, ntiles, 6] device tensor of {initial
+        cost, final cost, iterations, termination code, used samples, sum of w}.  A tile with
+        fewer than 3 used samples gets NaN coefficients and termination 5.  Honours planar-depth
+        tiles (set_tile_depth).  No sync."""
+        ew, eh, ec = _emap_dims(emap)
+        B = emap.shape[0]
+        self._check(self.L.pf_register_disparity_weighted(
+            self.h, _ptr(emap), ew, eh, ec, _ptr(tiles), _ptr(weights), self._wbatch(weights, B),
+            B, float(zr[0]), float(zr[1]), 1 if apply else 0, _ptr(coeffs), _ptr(coeffs64),
+            self._summary_ptr(summary, B, 6)))
+
+    def merge_disparity_weighted(self, emap, tiles, weights, out, zr, coeffs=None):
+        """pf_merge_disparity_weighted: register_disparity_weighted with apply on a copy of the
+        tiles (the caller's stay untouched), then fuse_weighted on the copy with the same
+        weights."""
+        ew, eh, ec = _emap_dims(emap)
+        B, oh, ow = out.shape
+        if oh != ow // 2:
+            raise ValueError("MergeDepthMaps output height is out_w/2")
+        self._check(self.L.pf_merge_disparity_weighted(
+            self.h, _ptr(emap), ew, eh, ec, _ptr(tiles), _ptr(weights), self._wbatch(weights, B),
+            B, ow, float(zr[0]), float(zr[1]), _ptr(coeffs), _ptr(out)))
 
     def register_disparity(self, emap, tiles, zr, apply=True, coeffs=None, coeffs64=None,
                            summary=None):
