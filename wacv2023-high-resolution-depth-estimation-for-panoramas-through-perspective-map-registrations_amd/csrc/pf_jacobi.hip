@@ -4,7 +4,9 @@
 // (Depth.cpp:1680-1717).  Here one launch ("pass") advances the band by T sweeps:
 //
 //  * A wave owns a vertical strip of 128 virtual columns (two per lane, kJC) and streams down a
-//    chunk of rows.  At step k it loads row k and, for every sweep level t = 1..T, produces row
+//    chunk of rows.  Step k consumes input row k - 1 (loaded 2-3 steps ahead; the L rows up to 3
+//    steps ahead, straight into their ring: "Load schedule" below) and, for every sweep level t
+//    = 1..T, produces row
 //    k-2t of level t from rows k-2t-1..k-2t+1 of level t-1, which it keeps in registers (a 3-row
 //    ring per level).  Horizontal neighbours cross lanes with DPP wave_shr/wave_shl moves.  L rows
 //    come through a ring as well: in registers (JLag) or in per-stage LDS (JPipe); no barriers
@@ -66,11 +68,16 @@
 #define PF_JPIPE_FILL 3  // fill groups of the pipelined engine (PF_JFILL = -1)
 #endif
 #ifndef PF_JLAG_PF
-// steps of lead for the input and L row loads: 1 or 2 -- the step loop is unrolled by 6, so the
-// load-buffer period PF + 1 must divide 6 (PF = 3 would need a 12-step unroll)
-#define PF_JLAG_PF 2
+// steps of lead of JLag's input row loads, at most: 2 or 3.  The PF + 1 load buffers are
+// indexed by ring group plus phase, so their period has to divide the L ring's R rows, not the
+// 6-step unroll; a depth whose R it does not divide keeps 3 buffers (JLag::NB)
+#define PF_JLAG_PF 3
 #endif
-static_assert(6 % (PF_JLAG_PF + 1) == 0, "the 6-step unroll needs a load-buffer period dividing 6");
+// JPipe's lead for the input and L row loads: its buffers are indexed by phase alone, so the
+// period PF + 1 must divide the 6-step unroll
+#define PF_JPIPE_PF 2
+static_assert(6 % (PF_JPIPE_PF + 1) == 0, "the 6-step unroll needs a load-buffer period dividing 6");
+static_assert(PF_JLAG_PF == 2 || PF_JLAG_PF == 3, "JLag's input lead");
 
 namespace pf {
 
@@ -102,12 +109,21 @@ enum { SRC_BUF = 0, SRC_UPSAMPLE = 1, SRC_SEED = 2 };
 // ---------------------------------------------------------------------------------------------
 // Lagged streaming: sweep level t produces row k-2t at step k (two rows behind level t-1), so
 // every level reads only rows finished in earlier steps and the 2T updates of a step are
-// independent (no intra-step dependency chain).  Level t keeps a 3-row ring; input rows and L rows
-// are loaded PF steps ahead.  The step loop is unrolled by 6 (lcm of the ring period 3 and the
-// load-buffer period PF+1) so every register ring index is a compile-time constant.
+// independent (no intra-step dependency chain).  Level t keeps a 3-row ring.  The step loop is
+// unrolled by 6, over the R/6 groups of the L ring's period, so every register ring index is a
+// compile-time constant.
 //
 // L rows live in a ring of R >= 2T+1 rows (row r in slot r % R): each L row is loaded from memory
 // once and read T times from the ring.
+//
+// Load schedule.  Step k issues two 512-B row loads per wave: L row k + LL straight into its ring
+// slot (LL = min(3, R - 2T - 1): that slot's old row was last read a step ago or earlier) and
+// input row k + PF - 1 into one of NB = PF + 1 buffers indexed by ring group plus phase (PF = 3
+// where 4 divides R, else 2).  The step's first instructions consume input row k - 1 and sanitise
+// L row k - 2 in place, so both loads have had PF / LL + 2 steps.  Loads return in order, so the
+// wait for the input row also waits for every load issued before it: at T = 10 a wave has 6 rows
+// (3 KB) in flight at that wait (s_waitcnt vmcnt(6) in the ISA).  No L staging buffers: the
+// T = 10 packed passes fit 3 waves per SIMD without scratch.  Measurements: DESIGN.md §3.
 //
 // Two arithmetic forms of the same update (bit-identical results):
 //  * FAST (packed): the two columns of a lane are one v_pk_* operand pair; the taps that cross
@@ -118,8 +134,9 @@ enum { SRC_BUF = 0, SRC_UPSAMPLE = 1, SRC_SEED = 2 };
 //    the host's separable-coverage certificate (prepare_levels in pf_layout.hip): a band pixel is
 //    covered iff its row is in h0+1..h1-1 and its column in a fixed set that excludes column 0
 //    (true of the reference's layouts: column 0 and the columns past the 359.9-degree cap are
-//    uncovered).  L rows are sanitised (non-finite -> 0) as they enter the ring so that d stays
-//    finite where H = 0.
+//    uncovered).  L rows are sanitised in the ring so that d stays finite where H = 0: L is set
+//    to 0 exactly there (the un-windowed marker is a NaN), and kept as loaded where H = 0.5, so
+//    an infinite target on a covered pixel saturates the pixel to 0 or 1 as in the reference.
 //  * general: scalar ops, mask from the marker in L (cmp + cndmask per pixel), any coverage.  It
 //    runs where the certificate is missing, and under PF_JSLOW.
 __device__ __forceinline__ f2 pk_add_clamp01(f2 a, f2 b)
@@ -160,10 +177,25 @@ template <int T, int SRC, bool OUT16, bool FAST>
 struct JLag {
     static constexpr int C = kJacobiCols;
     static_assert(C == 2, "a lane's columns are one pair: Row, the vector loads and stores, the wrap");
-    static constexpr int PF = PF_JLAG_PF, NB = PF_JLAG_PF + 1;
     // ring of R >= 2T+1 rows, R a multiple of 6: the loop body is unrolled over the R/6 groups
     // of 6 steps so every ring slot is a compile-time constant
     static constexpr int R = (2 * T + 1 + 5) / 6 * 6, NG = R / 6;
+    // Input rows land in NB = PF + 1 buffers, PF steps ahead of the step that consumes them.  The
+    // buffer of a row is a compile-time constant of the unrolled step if NB divides R (the index
+    // is ring group plus phase): 4 buffers at T = 4, 5, 10 (R = 12, 24), 3 where 4 do not divide
+    // R (R = 6 at T = 1, 2; R = 18 at T = 8), and in the seeded passes, whose gather holds more
+    // address registers (T = 10: a 4th buffer puts 28-32 B per lane of scratch into their step
+    // loop, 3 buffers none)
+    static constexpr int NB =
+        SRC != SRC_SEED && R % (PF_JLAG_PF + 1) == 0 ? PF_JLAG_PF + 1 : 3;
+    static constexpr int PF = NB - 1;
+    static_assert(R % NB == 0, "the input buffers' period must divide the ring's");
+    // L row k + LL is loaded at step k, straight into its ring slot.  The slot held row
+    // k + LL - R, which level T read for the last time at step k + LL - R + 2T <= k - 1, so the
+    // slot is dead if LL <= R - 2T - 1: 3 steps at T = 1, 4, 10 and 1 step at T = 2, 5, 8.
+    // Level 1 reads the row at step k + LL + 2, so an L load has LL + 2 steps to land
+    static constexpr int LL = 3 < R - 2 * T - 1 ? 3 : R - 2 * T - 1;
+    static_assert(LL >= 1 && LL <= R - 2 * T - 1, "the ring slot of L row k + LL must be dead at step k");
     // The L ring is in registers -- every slot index is a compile-time constant of the unrolled
     // step -- so no LDS store / load latency sits on a step's dependency chain.  Round 4: at
     // T = 10 the register ring took the packed pass from 132 VGPRs + 48 KB of LDS per 4-wave
@@ -173,8 +205,7 @@ struct JLag {
     // tools/gpu_round.sh ab).  JPipe keeps an LDS ring of its own.
     Row Lr[R];        // ring slot s = Lr[s]
     Row H[T][3];      // H[t][r % 3] = level t row r
-    Row In[NB];       // input row r lands in In[r % NB] (issued at step r + 1 - PF)
-    Row Lin[NB];      // L row r lands in Lin[r % NB] (issued at step r - PF), to the ring at step r
+    Row In[NB];       // input row k0 + s lands in In[s % NB] (issued at step k0 + s + 1 - PF)
     float hcol[C];  // FAST: H of the lane's columns: 0.5 (covered column) or 0
     float vq;       // -1/4 in a VGPR (the folded-DPP FMA takes its second operand from a VGPR)
     const JacobiPass* P;
@@ -238,16 +269,20 @@ struct JLag {
 
     static constexpr int slot(int ph, int a) { return ((ph - a) % 3 + 3) % 3; }
 
-    // the L ring: row k of the group (slot GB + PH, with GB = group base mod R, compile-time)
-    // enters, sanitised for the packed form (above); level t reads row k - 2t
-    template <int GB, int PH>
-    __device__ __forceinline__ void ring_put(Row r)
+    // the L ring: row k of the group sits in slot GB + PH (GB = group base mod R, compile-time);
+    // level t reads row k - 2t.  The packed form sanitises a row (above) in its slot at step
+    // row + 2, the step of its first read (level 1): the load has had LL + 2 steps by then, and
+    // this is the only place that waits for it.  H = 0 in the lane's un-windowed columns (hcol)
+    // and, in a pass that reaches them (ROWS), on rows h0 / h1; the rows past them are clamped
+    // copies of those two (load_row), never stored, and are zeroed alike
+    template <int GB, int PH, bool ROWS>
+    __device__ __forceinline__ void ring_sanitise(int k)
     {
-        if constexpr (FAST) {
+        Row& r = Lr[((GB + PH - 2) % R + R) % R];
+        bool edge = false;
+        if constexpr (ROWS) edge = k - 2 <= h0 || k - 2 >= h1;
 #pragma unroll
-            for (int j = 0; j < C; j++) r.v[j] = __builtin_isfinite(r.v[j]) ? r.v[j] : 0.0f;
-        }
-        Lr[((GB + PH) % R + R) % R] = r;
+        for (int j = 0; j < C; j++) r.v[j] = (edge || hcol[j] == 0.0f) ? 0.0f : r.v[j];
     }
     template <int GB, int PH, int TT>
     __device__ __forceinline__ Row ring_get() const
@@ -422,14 +457,15 @@ struct JLag {
     template <int PH, bool ROWS, int GB, int NA = T, int LA = 1>
     __device__ __forceinline__ void step(int k)
     {
-        // level-0 row k-1 (loaded last step) joins the ring
-        H[0][slot(PH, 1)] = In[(PH + NB - 1) % NB];
-        // L row k (landed in Lin last step) goes to its ring slot; fetch L row k+PF.  The slot
-        // is reused by row k+R > k, after every level has read row k (last read at k + 2T).
-        ring_put<GB, PH>(Lin[PH % NB]);
-        Lin[(PH + PF) % NB] = load_row(lnorm, k + PF);
-        // input row k + PF - 1 for a later step
-        In[(PH + PF - 1) % NB] = load_input(k + PF - 1);
+        // level-0 row k-1 (loaded PF steps ago) joins the ring
+        H[0][slot(PH, 1)] = In[(GB + PH + NB - 1) % NB];
+        // L row k-2, which level 1 reads in this step, is sanitised in its slot (rows before k0
+        // are zero slots: harmless)
+        if constexpr (FAST) ring_sanitise<GB, PH, ROWS>(k);
+        // L row k + LL straight into its ring slot, which is dead by now (at LL above)
+        Lr[(GB + PH + LL) % R] = load_row(lnorm, k + LL);
+        // input row k + PF - 1 for a later step; its buffer held row k - 2, consumed last step
+        In[(GB + PH + PF - 1) % NB] = load_input(k + PF - 1);
         Row nw[T];
         if constexpr (FAST) {
             sweep_packed<PH, GB, 0, ROWS, NA, LA>(nw, k);
@@ -551,6 +587,9 @@ struct JLag {
     // the drain code is written for ring group 0: the L ring is rotated so that the drain's
     // first group sits at slot 0 (a register permutation once per chunk), instead of one copy of
     // the drain per ring group (which took the T = 10 pass from 166 to 214 VGPRs)
+    // Up to LL of the permuted slots have their load in flight: the register dependency orders
+    // that (one wait per chunk).  The input buffers are brought to the same phase: SH % NB is 0,
+    // or 2 where the drain starts at an odd ring group with 4 buffers
     template <int SH>
     __device__ __forceinline__ void ring_rotate()
     {
@@ -559,6 +598,13 @@ struct JLag {
         for (int x = 0; x < R; x++) t[x] = Lr[(x + SH) % R];
 #pragma unroll
         for (int x = 0; x < R; x++) Lr[x] = t[x];
+        if constexpr (SH % NB != 0) {
+            Row u[NB];
+#pragma unroll
+            for (int x = 0; x < NB; x++) u[x] = In[(x + SH) % NB];
+#pragma unroll
+            for (int x = 0; x < NB; x++) In[x] = u[x];
+        }
     }
     template <int G>
     __device__ __forceinline__ void ring_to_zero(int g)
@@ -649,7 +695,7 @@ k_jlag(JacobiPass P)
 #pragma unroll
     for (int q = 0; q < S_t::NB; q++)
 #pragma unroll
-        for (int j = 0; j < C; j++) { S.In[q].v[j] = 0.0f; S.Lin[q].v[j] = 0.0f; }
+        for (int j = 0; j < C; j++) S.In[q].v[j] = 0.0f;
 #pragma unroll
     for (int q = 0; q < S_t::R; q++)
 #pragma unroll
@@ -659,13 +705,13 @@ k_jlag(JacobiPass P)
     const int k0 = S.r0 - T - 1;
     const int kend = S.r1 + 2 * T;
     // prime the rows the first steps consume before their in-loop loads land (the rest are
-    // loaded PF steps ahead inside step()).  The ring slots of rows before k0 stay unwritten:
-    // they only feed halo/stale cells, like the zero-initialised level rows.  Row k0 + r sits
-    // in buffer r (buffers count from k0, like the ring slots).
+    // loaded PF / LL steps ahead inside step()).  The ring slots of rows before k0 stay zero:
+    // they only feed halo/stale cells, like the zero-initialised level rows.  Input row k0 + r
+    // sits in buffer r and L row k0 + r in ring slot r (both count from k0).
 #pragma unroll
     for (int r = 0; r + 1 < S_t::PF; r++) S.In[r] = S.load_input(k0 + r);
 #pragma unroll
-    for (int r = 0; r < S_t::PF; r++) S.Lin[r] = S.load_row(S.lnorm, k0 + r);
+    for (int r = 0; r < S_t::LL; r++) S.Lr[r] = S.load_row(S.lnorm, k0 + r);
     // rows computed by some level of this pass: k - 2t for k in [k0, kend + 5], t in [1, T]
     const int wlo = k0 - 2 * T, whi = kend + 3;
     const bool rows = (S.h0 >= wlo && S.h0 <= whi) || (S.h1 >= wlo && S.h1 <= whi);
@@ -689,7 +735,7 @@ struct JPipe {
     static constexpr int C = kJacobiCols;
     static constexpr int T = TS * S;
     static constexpr int TB = SI * TS + 1, TE = TB + TS - 1;  // own levels
-    static constexpr int PF = PF_JLAG_PF, NB = PF_JLAG_PF + 1;
+    static constexpr int PF = PF_JPIPE_PF, NB = PF_JPIPE_PF + 1;
     static constexpr int R = (2 * TS + 1 + 5) / 6 * 6;  // L ring rows (multiple of 6)
     static constexpr int NG = R / 6;
     static constexpr int G = PF_JPK_GROUP;
